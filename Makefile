@@ -1,6 +1,6 @@
 # Convenience targets (the driver uses __graft_entry__.build() and the
 # pytest/bench contracts directly; this Makefile just wraps them).
-.PHONY: build test test-gpu bench clean
+.PHONY: build test test-gpu bench bench-full clean
 
 build:
 	python -c "import __graft_entry__ as g; g.build()"
@@ -13,6 +13,10 @@ test-gpu:
 
 bench:
 	python bench.py
+
+# plain run plus the cpu_baseline leg
+bench-full:
+	python bench.py --full
 
 clean:
 	rm -f neutronstarlite_amd/libnts_hip.so oracle/liboracle.so

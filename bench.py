@@ -12,6 +12,12 @@ loops), seed 7, feat=602, fp32, weights = 1/sqrt(outdeg*indeg), features
 seeded U(-1,1) (seed 42), random-init-equivalent synthetic data (no datasets
 on the box).  config #1 (Cora) is a parity-test case, not a bench line.
 
+A plain run sets up, warms up, times the K steps and prints the result line;
+`--dump-outputs DIR` additionally writes what the last timed step returned as
+DIR/<name>.npy (float32, a fixed seeded row sample when an output is large).
+Everything that needs work beyond the timed steps (today: the cpu_baseline
+leg) runs only under `--full`.
+
 Rank 0 prints ONE JSON line, including:
   roofline     — the dominant kernel (forward CSC aggregation): ALGORITHMIC
                  bytes/launch = E*(4f+8) + V*8f (SURVEY.md §8d byte model,
@@ -23,7 +29,8 @@ Rank 0 prints ONE JSON line, including:
                  --traffic-bytes-per-launch; null when not provided.
   cpu_baseline — the CPU oracle (oracle/oracle.c, kind "port") timed on this
                  box's host cores over a bounded sample of the same workload
-                 (~10-30 s of CPU work), rank 0 at N=1 only.
+                 (~10-30 s of CPU work), rank 0 at N=1 under --full only;
+                 null otherwise.
 """
 import argparse
 import json
@@ -146,6 +153,38 @@ def cpu_baseline_leg(chunks, f, target_sec=15.0):
     }
 
 
+# names of what one step() of each --model returns, in order
+OUTPUT_NAMES = {
+    "gcn": ["y", "gx"],
+    "gat": ["grad_h", "grad_score_src", "grad_score_dst"],
+    "gcn-layer": ["gw", "gx"],
+    "gcn-sample": ["h", "g"],
+    "gcn-sample-train": ["loss"],
+    "gcn-train": ["loss"],
+}
+
+DUMP_BYTES = 60_000_000  # all dumped arrays together stay under 64 MB
+
+
+def dump_outputs(out_dir, named):
+    """Write each tensor as out_dir/<name>.npy (float32).  An output whose
+    share of DUMP_BYTES is too small for it is reduced to a fixed, seeded,
+    sorted sample of its rows — the same rows on every run and build."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(named))
+    for name, t in named.items():
+        t = t.detach()
+        if t.numel() * 4 > share:
+            rows = t.shape[0]
+            keep = max(1, share // (4 * (t.numel() // rows)))
+            idx = np.sort(np.random.default_rng(0).choice(
+                rows, size=min(keep, rows), replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.float().cpu().numpy())
+
+
 def main(argv=None, _test_engine_factory=None, _test_backend=None,
          _test_device=None):
     """Product entry point: HIP engine, RCCL, cuda devices.  The _test_*
@@ -187,7 +226,16 @@ def main(argv=None, _test_engine_factory=None, _test_backend=None,
                     help="projection width for --model gcn-layer")
     ap.add_argument("--graph", default="reddit",
                     choices=["reddit", "rmat26", "small"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that are not needed for the "
+                         "headline figure (the cpu_baseline oracle timing)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the arrays the last "
+                         "timed step returned as DIR/<name>.npy (float32; a "
+                         "fixed seeded row sample of outputs too large to "
+                         "keep whole, 64 MB in all at most)")
     ap.add_argument("--cache-dir", default=None,
                     help="cache built graph/chunk arrays (npz) to skip the "
                          "~1 min host-side setup on repeated runs")
@@ -310,6 +358,7 @@ def main(argv=None, _test_engine_factory=None, _test_backend=None,
         setup_mirror_lists(rg)
 
     rng = np.random.default_rng(42 + rank)
+    torch.manual_seed(42 + rank)  # gcn-sample draws its inputs on device
     x_np = None
     if args.cfg:
         # use the cfg's FEATURE_FILE when it exists (GNNDatum text format);
@@ -507,8 +556,11 @@ def main(argv=None, _test_engine_factory=None, _test_backend=None,
     engine.stream.timing_reset()
 
     t0 = time.time()
-    for _ in range(args.steps):
+    last = None
+    for _ in range(args.steps - 1):
         step()
+    if args.steps > 0:
+        last = step()  # kept only for --dump-outputs
     device_sync()
     if distributed:
         dist.barrier()
@@ -548,8 +600,18 @@ def main(argv=None, _test_engine_factory=None, _test_backend=None,
         "traffic": args.traffic_bytes_per_launch,
     }
 
+    if args.dump_outputs:
+        named = dict(zip(OUTPUT_NAMES[args.model],
+                         last if isinstance(last, (tuple, list)) else [last]))
+        if args.model in ("gcn-train", "gcn-sample-train"):
+            named.update(W0=W0, W1=W1)
+        if distributed:
+            named = {f"{k}.rank{rank}": t for k, t in named.items()}
+        dump_outputs(args.dump_outputs, named)
+    del last
+
     cpu_baseline = None
-    if rank == 0 and n == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and n == 1 and not args.no_cpu_baseline:
         log("cpu baseline (oracle, bounded sample)")
         cpu_baseline = cpu_baseline_leg(chunks, f)
 

@@ -19,10 +19,60 @@ neighbor-aggregation path (all citations into /root/reference):
 This module is pure host-side plumbing (numpy); the compute path is the HIP
 extension (csrc/nts_hip.hip behind include/nts_hip.h).
 """
+import os
+from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
 from typing import List
 
 import numpy as np
+
+
+def _parallel_blocks(fn, n: int, block: int):
+    """Run fn(lo, hi) over [0, n) in `block`-sized pieces on a small thread
+    pool (numpy releases the GIL inside its loops)."""
+    spans = [(lo, min(lo + block, n)) for lo in range(0, n, block)]
+    workers = min(16, len(os.sched_getaffinity(0)), len(spans))
+    if workers <= 1:
+        for lo, hi in spans:
+            fn(lo, hi)
+        return
+    with ThreadPoolExecutor(workers) as pool:
+        for _ in pool.map(lambda s: fn(*s), spans):
+            pass
+
+
+def _take(a: np.ndarray, idx: np.ndarray, dtype=None) -> np.ndarray:
+    """a[idx] (optionally cast to dtype), gathered blockwise in parallel."""
+    out = np.empty(len(idx), dtype=dtype or a.dtype)
+
+    def block(lo, hi):
+        out[lo:hi] = a[idx[lo:hi]]
+
+    _parallel_blocks(block, len(idx), 1 << 22)
+    return out
+
+
+def _stable_order(key: np.ndarray) -> np.ndarray:
+    """argsort(key, kind="stable") for u32-ranged integer keys: sort the
+    unique composite (key << 32 | position) — one plain u64 sort instead of
+    a stable argsort — and take the positions back out."""
+    n = len(key)
+    assert n < (1 << 32)
+    comp = np.empty(n, dtype=np.uint64)
+    order = np.empty(n, dtype=np.int64)
+
+    def pack(lo, hi):
+        comp[lo:hi] = key[lo:hi]
+        comp[lo:hi] <<= np.uint64(32)
+        comp[lo:hi] |= np.arange(lo, hi, dtype=np.uint64)
+
+    def unpack(lo, hi):
+        order[lo:hi] = comp[lo:hi] & np.uint64(0xFFFFFFFF)
+
+    _parallel_blocks(pack, n, 1 << 22)
+    comp.sort()
+    _parallel_blocks(unpack, n, 1 << 22)
+    return order
 
 
 def load_gemini_edges(path: str) -> np.ndarray:
@@ -40,22 +90,37 @@ def rmat_edges(v: int, e: int, seed: int = 7,
 
     Vectorized: for each of ceil(log2(v)) levels, draw one quadrant choice
     per edge. Returns (E',2) u32 with E' = e (+v if self-loops)."""
-    rng = np.random.default_rng(seed)
     scale = int(np.ceil(np.log2(max(v, 2))))
-    src = np.zeros(e, dtype=np.uint64)
-    dst = np.zeros(e, dtype=np.uint64)
-    thresholds = np.cumsum([a, b, c])  # quadrant split by one uniform draw
-    for level in range(scale):
-        q = np.searchsorted(thresholds, rng.random(e))
-        bit = np.uint64(1) << np.uint64(scale - 1 - level)
-        src += bit * (q >= 2)
-        dst += bit * ((q == 1) | (q == 3))
-    src %= np.uint64(v)
-    dst %= np.uint64(v)
-    edges = np.stack([src.astype(np.uint32), dst.astype(np.uint32)], axis=1)
+    t0, t1, t2 = np.cumsum([a, b, c])  # quadrant split by one uniform draw
+    edges = np.empty((e + (v if add_self_loops else 0), 2), dtype=np.uint32)
+    base = np.random.PCG64(seed).state
+
+    # The draws are those of ONE default_rng(seed) stream taken level by
+    # level (level L, edge i = draw L*e + i; random() uses one 64-bit draw
+    # per double), so blocks of edges are generated independently by
+    # advancing a copy of the stream — cache-sized blocks on a thread pool
+    # instead of `scale` passes over e-sized temporaries.
+    def block(lo, hi):
+        src = np.zeros(hi - lo, dtype=np.uint64)
+        dst = np.zeros(hi - lo, dtype=np.uint64)
+        bg = np.random.PCG64()
+        for level in range(scale):
+            bg.state = base
+            bg.advance(level * e + lo)
+            r = np.random.Generator(bg).random(hi - lo)
+            bit = np.uint64(1) << np.uint64(scale - 1 - level)
+            # quadrant q = #thresholds < r: src bit for q>=2, dst for q in {1,3}
+            upper = r > t1
+            src += bit * upper
+            dst += bit * (((r > t0) & ~upper) | (r > t2))
+        src %= np.uint64(v)
+        dst %= np.uint64(v)
+        edges[lo:hi, 0] = src
+        edges[lo:hi, 1] = dst
+
+    _parallel_blocks(block, e, 1 << 18)
     if add_self_loops:
-        loops = np.arange(v, dtype=np.uint32)
-        edges = np.concatenate([edges, np.stack([loops, loops], axis=1)], axis=0)
+        edges[e:] = np.arange(v, dtype=np.uint32)[:, None]
     return edges
 
 
@@ -135,10 +200,10 @@ class Chunk:
 
 
 def _csc(src, dst, w, dst_s, dst_n, key_minor=None):
-    order = np.argsort(dst.astype(np.int64), kind="stable")
-    s, d, wv = src[order], dst[order], w[order]
+    order = _stable_order(dst)
+    s, wv = _take(src, order), _take(w, order)
     col_off = np.zeros(dst_n + 1, dtype=np.uint32)
-    counts = np.bincount((d - dst_s).astype(np.int64), minlength=dst_n)
+    counts = np.bincount((dst - dst_s).astype(np.int64), minlength=dst_n)
     col_off[1:] = np.cumsum(counts).astype(np.uint32)
     return col_off, s, wv
 
@@ -152,14 +217,20 @@ def build_chunks(edges: np.ndarray, weights: np.ndarray, offs: np.ndarray,
     parts = len(offs) - 1
     dst_s, dst_e = int(offs[rank]), int(offs[rank + 1])
     dst_n = dst_e - dst_s
-    owned = (edges[:, 1] >= dst_s) & (edges[:, 1] < dst_e)
-    e_src, e_dst, e_w = edges[owned, 0], edges[owned, 1], weights[owned]
+    if parts == 1:
+        e_src, e_dst, e_w = edges[:, 0], edges[:, 1], weights
+    else:
+        owned = (edges[:, 1] >= dst_s) & (edges[:, 1] < dst_e)
+        e_src, e_dst, e_w = edges[owned, 0], edges[owned, 1], weights[owned]
     src_part = np.searchsorted(offs[1:-1], e_src, side="right") if parts > 1 \
         else np.zeros(len(e_src), dtype=np.int64)
     chunks = []
     for k in range(parts):
-        sel = src_part == k
-        s, d, w = e_src[sel], e_dst[sel], e_w[sel]
+        if parts == 1:
+            s, d, w = e_src, e_dst, e_w
+        else:
+            sel = src_part == k
+            s, d, w = e_src[sel], e_dst[sel], e_w[sel]
         src_s, src_e = int(offs[k]), int(offs[k + 1])
         src_n = src_e - src_s
         col_off, rows, wf = _csc(s, d, w, dst_s, dst_n)
@@ -167,21 +238,20 @@ def build_chunks(edges: np.ndarray, weights: np.ndarray, offs: np.ndarray,
         # csr_edge[i] == csc_edge[argsort_stable(src_of_csc)[i]] — the
         # edge-valued (GAT) path relies on this to carry per-edge attention
         # weights from CSC to CSR order (gat.py csr_from_csc).
-        d_csc = np.repeat(np.arange(dst_n, dtype=np.int64),
-                          np.diff(col_off.astype(np.int64))) + dst_s
-        order = np.argsort(rows.astype(np.int64), kind="stable")
+        d_csc = np.repeat(np.arange(dst_s, dst_e, dtype=np.uint32),
+                          np.diff(col_off.astype(np.int64)))
+        order = _stable_order(rows)
         row_off = np.zeros(src_n + 1, dtype=np.uint32)
-        counts = np.bincount((rows[order] - src_s).astype(np.int64),
-                             minlength=src_n)
+        counts = np.bincount((rows - src_s).astype(np.int64), minlength=src_n)
         row_off[1:] = np.cumsum(counts).astype(np.uint32)
         chunks.append(Chunk(
             src_s=src_s, src_e=src_e, dst_s=dst_s, dst_e=dst_e,
-            column_offset=col_off.astype(np.uint32),
-            row_indices=rows.astype(np.uint32),
-            edge_weight_forward=wf.astype(np.float32),
-            row_offset=row_off.astype(np.uint32),
-            column_indices=d_csc[order].astype(np.uint32),
-            edge_weight_backward=wf[order].astype(np.float32),
+            column_offset=col_off,
+            row_indices=rows.astype(np.uint32, copy=False),
+            edge_weight_forward=wf.astype(np.float32, copy=False),
+            row_offset=row_off,
+            column_indices=_take(d_csc, order, np.uint32),
+            edge_weight_backward=_take(wf, order, np.float32),
         ))
     return chunks
 

@@ -1,14 +1,15 @@
 """GNNDatum-equivalent text loaders (feature/label/mask formats of
 core/ntsDataloador.hpp) — round-trip and partition-filter behavior, plus a
-check against the vendored cora.labeltable/mask when the reference is
-mounted (build container only)."""
+check against the vendored cora.labeltable/mask (data files stored as
+fixtures under tests/golden/)."""
 import os
 
 import numpy as np
-import pytest
 
 from neutronstarlite_amd import data as D
-from tests.conftest import REFERENCE
+from tests.conftest import REPO
+
+GOLDEN = os.path.join(REPO, "tests", "golden")
 
 
 def test_text_roundtrip_and_partition_filter(tmp_path):
@@ -42,13 +43,11 @@ def test_random_generate_convention():
     assert m.tolist() == [0, 1, 2, 0, 1, 2, 0, 1, 2]
 
 
-@pytest.mark.skipif(not os.path.exists(REFERENCE),
-                    reason="reference not mounted (run-time box)")
 def test_vendored_cora_label_and_mask_parse():
     labels = D.read_label_table(
-        os.path.join(REFERENCE, "data", "cora.labeltable"), 0, 2708)
+        os.path.join(GOLDEN, "cora.labeltable"), 0, 2708)
     assert labels.shape == (2708,)
     assert labels.min() >= 0 and labels.max() <= 6  # 7 Cora classes
-    mask = D.read_mask(os.path.join(REFERENCE, "data", "cora.mask"), 0, 2708)
+    mask = D.read_mask(os.path.join(GOLDEN, "cora.mask"), 0, 2708)
     assert set(np.unique(mask)).issubset({0, 1, 2, 3})
     assert (mask == 0).sum() > 0 and (mask == 2).sum() > 0

@@ -99,6 +99,38 @@ void nts_gather_by_src_from_dst(nts_stream *s,
     nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
     nts_vid edges, nts_vid batch_size, nts_vid feature_size, int with_weight);
 
+/* Column schedule of the two gather entry points.  A gather task is (work
+ * item, column window of `window_floats` floats); the schedule only changes
+ * which task runs when, so for a vertex that is not split into several work
+ * items the result is bit-identical under every schedule. */
+enum nts_gather_sched {
+  NTS_SCHED_ITEM = 0,      /* task = item*windows + window (the default) */
+  NTS_SCHED_PHASE = 1,     /* task = window*items + item: one window of all
+                              rows is live on the chip at a time */
+  NTS_SCHED_XCD = 2        /* workgroups with equal blockIdx.x % 8 (one XCD
+                              under round-robin placement) own a stripe of
+                              windows/8 windows, so each L2 caches one column
+                              stripe; the windows % 8 left over are shared out
+                              task by task; with 2 or 4 windows, 8/windows
+                              classes share one and split the items.  Needs
+                              2, 4 or >= 8 windows and >= 8 workgroups, else
+                              NTS_SCHED_ITEM runs */
+};
+
+/* Request a schedule for this stream's following gathers.  (0, 0) =
+ * automatic: chosen per call from the shape.  (0, w != 0) forces
+ * NTS_SCHED_ITEM with window w (w < 0: the native slab, i.e. exactly the
+ * pre-window launch).  window_floats = 0 with a non-zero schedule takes that
+ * schedule's default width; widths are rounded up to the vector width.
+ * Environment, for sweeps, when no request is set: NTS_GATHER_SCHED (forces,
+ * 0 included) and NTS_GATHER_WINDOW; NTS_GATHER_BLOCKS caps the grid of the
+ * column-blocked launches (default 2^20: one task per lane group up to
+ * there, which is what lets NTS_SCHED_PHASE keep one window live). */
+void nts_gather_schedule(nts_stream *s, int schedule, int window_floats);
+
+/* The schedule and window the stream's most recent gather actually ran. */
+void nts_gather_schedule_last(nts_stream *s, int *schedule, int *window_floats);
+
 /* The two gather entry points decompose (offset, batch) into bounded
  * per-wavefront work items on device, rebuilt on every call into a
  * stream-owned scratch buffer (caching by topology pointer would be unsound

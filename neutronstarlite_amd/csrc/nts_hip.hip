@@ -63,6 +63,13 @@ uint32_t nts_max_blocks() {
   static uint32_t v = env_u32("NTS_MAX_BLOCKS", 8192);
   return v;
 }
+/* grid cap of the column-blocked gather launches: they run faster the less
+ * a workgroup strides (profiles/README.md round3), so theirs is set apart
+ * from NTS_MAX_BLOCKS.  < 2^24 keeps blockIdx.x * blockDim.x in 32 bits. */
+uint32_t nts_gather_blocks() {
+  static uint32_t v = min(env_u32("NTS_GATHER_BLOCKS", 1u << 20), 1u << 23);
+  return v;
+}
 #define NTS_SPLIT nts_split()
 #define NTS_MAX_BLOCKS nts_max_blocks()
 
@@ -93,6 +100,8 @@ struct nts_stream {
                                 nts_items_reuse */
   int items_rr = 0;          /* which slot the next build replaces */
   bool items_reuse = false;  /* opt-in caching (nts_items_reuse) */
+  int sched_req = 0, window_req = 0;   /* nts_gather_schedule; 0,0 = auto */
+  int sched_last = 0, window_last = 0; /* what the last gather ran */
   float *sums_ws = nullptr;  /* per-dst reduction scratch (softmax) */
   uint64_t sums_cap = 0;
 };
@@ -167,33 +176,118 @@ __global__ void k_build_items(const uint32_t *__restrict__ offset,
 /* Forward CSC:  nbr = row_indices   (global src),  out rows = dst.    */
 /* Backward CSR: nbr = column_indices (global dst), out rows = src.    */
 /* ------------------------------------------------------------------ */
-template <int ELEM, bool WITH_W>
+/* Column scheduling (BLOCKED): a task is (work item, column window of wf */
+/* floats, tile of the lane group inside the window).  The schedules    */
+/* only permute which task a group runs when — each output element is   */
+/* still one lane's fmaf chain over the item's edges in edge order — so */
+/* results are bit-identical across schedules for unsplit vertices.     */
+/*   ITEM       t = item*windows + window      (the pre-window order)    */
+/*   PHASE      t = window*items + item: the chip sweeps one window of   */
+/*              all rows at a time (V*wf*4 B live instead of V*f*4)      */
+/*   XCD        workgroups of class blockIdx.x%8 (one XCD under         */
+/*              round-robin placement) own a stripe of windows/8         */
+/*              windows and stride over all items, so each L2 caches one */
+/*              column stripe; the windows%8 left over are shared out    */
+/*              task by task, which keeps the classes balanced.  With 2  */
+/*              or 4 windows, 8/windows classes share a window and deal  */
+/*              the items out among themselves                           */
+/* Coverage depends only on blockIdx/gridDim, never on placement.       */
+/* BLOCKED=false is the one-tile-per-window ITEM order, bound f.        */
+struct GatherPlan {
+  uint32_t sched;     /* nts_gather_sched */
+  uint32_t wf;        /* window width in floats (multiple of ELEM) */
+  uint32_t n_windows; /* ceil(f / wf); 2, 4 or >= 8 for the XCD schedule */
+  uint32_t tiles;     /* lane-group tiles per window: ceil(wf / tilef) */
+};
+
+template <int ELEM, bool WITH_W, bool BLOCKED>
 __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm(
     const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
     const uint32_t *__restrict__ nbr, const float *__restrict__ ew,
     const float *__restrict__ in, float *__restrict__ out, uint32_t nbr_start,
-    uint32_t f, uint32_t G, uint32_t n_slabs) {
+    uint32_t f, uint32_t G, GatherPlan pl) {
   constexpr int NSTR = (ELEM == 1) ? 4 : 1;  /* strided sub-elements */
   const uint32_t n_items = *n_items_p;
-  const uint64_t total = (uint64_t)n_items * n_slabs;
-  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t glane = threadIdx.x & (G - 1);
-  const uint32_t n_groups = (gridDim.x * blockDim.x) / G;
-  const uint32_t slabf = G * ELEM * NSTR;
+  const uint32_t tilef = G * ELEM * NSTR;
+  const uint32_t per_item = pl.n_windows * pl.tiles;
+  /* group index and stride: over the whole grid, or (XCD-affine) over the
+   * workgroups of this block's class blockIdx.x % 8 */
+  uint64_t t0, stride, total;
+  uint32_t cls = 0, cpw = 0;
+  const uint32_t stripe = (pl.n_windows >> 3) * pl.tiles; /* XCD: per item */
+  const uint32_t rest = (pl.n_windows & 7u) * pl.tiles;
+  uint64_t striped = 0; /* XCD: this class's tasks inside its stripe */
+  if (BLOCKED && pl.sched == NTS_SCHED_XCD) {
+    const uint32_t gpb = blockDim.x / G;
+    cls = blockIdx.x & 7u;
+    t0 = (uint64_t)(blockIdx.x >> 3) * gpb + threadIdx.x / G;
+    stride = (uint64_t)((gridDim.x - cls + 7u) >> 3) * gpb;
+    if (pl.n_windows >= 8) {
+      striped = (uint64_t)n_items * stripe;
+      const uint64_t shared = (uint64_t)n_items * rest;
+      total = striped + (shared > cls ? (shared - cls + 7u) >> 3 : 0u);
+    } else {
+      /* 2 or 4 windows: 8/windows classes share one, items dealt round */
+      cpw = 8u / pl.n_windows;
+      const uint32_t sub = cls % cpw;
+      total = n_items > sub
+                  ? (uint64_t)((n_items - sub + cpw - 1) / cpw) * pl.tiles : 0u;
+    }
+  } else {
+    t0 = (blockIdx.x * blockDim.x + threadIdx.x) / G;
+    stride = (gridDim.x * blockDim.x) / G;
+    total = (uint64_t)n_items * per_item;
+  }
 
-  for (uint64_t t = tid / G; t < total; t += n_groups) {
-    const uint32_t it = (uint32_t)(t / n_slabs);
-    const uint32_t slab = (uint32_t)(t % n_slabs);
+  for (uint64_t t = t0; t < total; t += stride) {
+    uint32_t it, fbase, fend;
+    if constexpr (!BLOCKED) {
+      it = (uint32_t)(t / per_item);
+      fbase = (uint32_t)(t % per_item) * tilef;
+      fend = f;
+    } else {
+      uint32_t win, tile;
+      if (pl.sched == NTS_SCHED_ITEM) {
+        it = (uint32_t)(t / per_item);
+        const uint32_t r = (uint32_t)(t % per_item);
+        win = r / pl.tiles;
+        tile = r % pl.tiles;
+      } else if (pl.sched == NTS_SCHED_PHASE) {
+        const uint64_t per_win = (uint64_t)n_items * pl.tiles;
+        win = (uint32_t)(t / per_win);
+        const uint64_t r = t % per_win;
+        it = (uint32_t)(r / pl.tiles);
+        tile = (uint32_t)(r % pl.tiles);
+      } else if (cpw) { /* NTS_SCHED_XCD, a window shared by cpw classes */
+        it = cls % cpw + cpw * (uint32_t)(t / pl.tiles);
+        win = cls / cpw;
+        tile = (uint32_t)(t % pl.tiles);
+      } else if (t < striped) { /* NTS_SCHED_XCD, own stripe */
+        it = (uint32_t)(t / stripe);
+        const uint32_t r = cls * stripe + (uint32_t)(t % stripe);
+        win = r / pl.tiles;
+        tile = r % pl.tiles;
+      } else { /* NTS_SCHED_XCD, every 8th task of the left-over windows */
+        const uint64_t r = cls + 8u * (t - striped);
+        it = (uint32_t)(r / rest);
+        const uint32_t j = 8u * stripe + (uint32_t)(r % rest);
+        win = j / pl.tiles;
+        tile = j % pl.tiles;
+      }
+      fbase = win * pl.wf + tile * tilef;
+      fend = min(f, (win + 1) * pl.wf);
+      if (fbase >= fend) continue; /* tile past a short last window */
+    }
     const uint4 itm = items[it];
     const uint32_t v = itm.x & 0x7fffffffu;
     const bool shared_v = (itm.x >> 31) != 0;
     const uint32_t e0 = itm.y, cnt = itm.z;
-    const uint32_t fbase = slab * slabf;
 
     float acc[ELEM * NSTR] = {};
     if constexpr (ELEM == 1) {
       /* strided dword path: element j at fbase + glane + j*G */
-      bool any = fbase + glane < f;
+      bool any = fbase + glane < fend;
       if (any) {
         /* 4-edge unroll: 4 independent row loads in flight per wave
          * (one dependent load per iteration leaves HBM latency exposed) */
@@ -211,7 +305,7 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm(
           for (int k = 0; k < 4; ++k)
 #pragma unroll
             for (int j = 0; j < NSTR; ++j)
-              if (fbase + glane + j * G < f)
+              if (fbase + glane + j * G < fend)
                 acc[j] = fmaf(wv[k], p[k][j * G], acc[j]);
         }
         for (; e < e_end; ++e) {
@@ -220,22 +314,22 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm(
           const float *p = in + src * f + fbase + glane;
 #pragma unroll
           for (int j = 0; j < NSTR; ++j)
-            if (fbase + glane + j * G < f) acc[j] = fmaf(w, p[j * G], acc[j]);
+            if (fbase + glane + j * G < fend) acc[j] = fmaf(w, p[j * G], acc[j]);
         }
         float *o = out + (uint64_t)v * f + fbase + glane;
         if (!shared_v) {
 #pragma unroll
           for (int j = 0; j < NSTR; ++j)
-            if (fbase + glane + j * G < f) o[j * G] += acc[j];
+            if (fbase + glane + j * G < fend) o[j * G] += acc[j];
         } else {
 #pragma unroll
           for (int j = 0; j < NSTR; ++j)
-            if (fbase + glane + j * G < f) atomicAdd(&o[j * G], acc[j]);
+            if (fbase + glane + j * G < fend) atomicAdd(&o[j * G], acc[j]);
         }
       }
     } else {
       const uint32_t off = fbase + glane * ELEM;
-      const int nv = (off + ELEM <= f) ? ELEM : (off < f ? (int)(f - off) : 0);
+      const int nv = (off + ELEM <= fend) ? ELEM : (off < fend ? (int)(fend - off) : 0);
       if (nv == ELEM) {
         /* 4-edge unroll: 4 independent vector row loads in flight */
         uint32_t e = e0;
@@ -1166,12 +1260,13 @@ void dbg_sync(nts_stream *s, const char *what) {
   }
 }
 
-uint32_t grid_for(uint64_t threads) {
+uint32_t grid_for(uint64_t threads, uint32_t cap) {
   uint64_t b = (threads + NTS_BLOCK - 1) / NTS_BLOCK;
   if (b < 1) b = 1;
-  if (b > NTS_MAX_BLOCKS) b = NTS_MAX_BLOCKS;
+  if (b > cap) b = cap;
   return (uint32_t)b;
 }
+uint32_t grid_for(uint64_t threads) { return grid_for(threads, NTS_MAX_BLOCKS); }
 
 /* Build the bounded work items for (offset, batch) into the stream's
  * scratch buffer.  Rebuilt on EVERY call: caching by topology pointer is
@@ -1217,10 +1312,46 @@ ItemsBuf &get_items(nts_stream *s, const uint32_t *offset, uint32_t batch,
   return ib;
 }
 
+/* When the automatic choice engages a blocked column schedule:
+ *  - the gathered matrix (rows x f x 4 B) must exceed the 256 MiB Infinity
+ *    Cache, far past the 8 x 4 MiB of L2: below that every row stays cached
+ *    in any order, and what phase-major buys is a live set (rows x window)
+ *    that fits the cache again;
+ *  - each window re-reads the item's index and weight lists, up to 16 times
+ *    at the narrowest split swept, so a gathered row must be re-read at least
+ *    2 x 16 times (edges / rows) for row reuse to outweigh that.
+ * One-window widths never engage (n_slabs == 1). */
+constexpr uint64_t NTS_BLOCK_MIN_BYTES = 256ull << 20;
+constexpr uint32_t NTS_BLOCK_MIN_REUSE = 32;
+/* Automatic schedule and window (0 = that schedule's default width): the
+ * winner of the sweep recorded in profiles/README.md (round3) — phase-major
+ * over the native slab, 55.9 ms/step against 67.1 at the headline shape. */
+constexpr int NTS_AUTO_SCHED = NTS_SCHED_PHASE;
+constexpr uint32_t NTS_AUTO_WINDOW = 0;
+
+/* Sweep overrides, read once like NTS_SPLIT: NTS_GATHER_SCHED forces a
+ * schedule (0 = the current order), NTS_GATHER_WINDOW its window width in
+ * floats (unset/0 = the schedule's default). */
+bool gather_sched_env(int *sched, int *window) {
+  static int v_s = -1, v_w = 0;
+  static bool init = false;
+  if (!init) {
+    const char *e = getenv("NTS_GATHER_SCHED");
+    if (e && *e) v_s = atoi(e);
+    const char *w = getenv("NTS_GATHER_WINDOW");
+    if (w && *w) v_w = atoi(w);
+    init = true;
+  }
+  if (v_s < 0) return false;
+  *sched = v_s;
+  *window = v_w;
+  return true;
+}
+
 void launch_gather(nts_stream *s, const float *in, float *out, const float *ew,
                    const uint32_t *nbr, const uint32_t *offset,
                    uint32_t nbr_start, uint32_t batch, uint32_t edges,
-                   uint32_t f, int with_weight, int tag) {
+                   uint32_t f, int with_weight, int tag, uint32_t rows) {
   if (!batch || !edges || !f) return;
   ItemsBuf &ib = get_items(s, offset, batch, edges);
   const uintptr_t a = (uintptr_t)in | (uintptr_t)out;
@@ -1235,13 +1366,85 @@ void launch_gather(nts_stream *s, const float *in, float *out, const float *ew,
   while (G / 2 >= need && G > 16) G /= 2;
   const uint32_t slabf = G * elem * nstr;
   const uint32_t n_slabs = (f + slabf - 1) / slabf;
-  const uint64_t bound_groups = ((uint64_t)batch + edges / NTS_SPLIT + 1) * n_slabs;
-  const uint32_t grid = grid_for(bound_groups * G);
+  const uint64_t bound_items = (uint64_t)batch + edges / NTS_SPLIT + 1;
+
+  /* ---- column schedule: request (stream, then env) or automatic ---- */
+  int sched = NTS_SCHED_ITEM;
+  uint32_t wf = slabf;
+  int env_sched = 0, env_window = 0;
+  if (s->sched_req || s->window_req) {
+    sched = s->sched_req;
+    wf = s->window_req > 0 ? (uint32_t)s->window_req : 0;
+  } else if (gather_sched_env(&env_sched, &env_window)) {
+    sched = env_sched;
+    wf = env_window > 0 ? (uint32_t)env_window : 0;
+  } else if (n_slabs > 1 && (uint64_t)rows * f * 4 > NTS_BLOCK_MIN_BYTES &&
+             edges / NTS_BLOCK_MIN_REUSE >= rows) {
+    /* rows == 0 (row count unknown to the caller) never engages */
+    sched = NTS_AUTO_SCHED;
+    wf = NTS_AUTO_WINDOW;
+  }
+  if (sched < NTS_SCHED_ITEM || sched > NTS_SCHED_XCD) sched = NTS_SCHED_ITEM;
+  const uint32_t unit = elem * nstr; /* floats per lane */
+  if (wf == 0) {
+    /* default width: the native slab; XCD: the widest full lane group
+     * (64, 32 or 16 lanes) that still gives every class a window */
+    wf = slabf;
+    if (sched == NTS_SCHED_XCD)
+      for (uint32_t g = 64; g >= 16; g /= 2) {
+        wf = g * unit;
+        if ((f + wf - 1) / wf >= 8) break;
+      }
+  }
+  wf = (wf + elem - 1) / elem * elem;
+  if (wf > f) wf = (f + elem - 1) / elem * elem;
+  const uint32_t n_windows = (f + wf - 1) / wf;
+  /* lane group of a window: the fewest lane slots (tiles x lanes), widest
+   * group on a tie — masked lanes cost as much as live ones */
+  uint32_t Gb = 64, tiles = (wf + 64 * unit - 1) / (64 * unit);
+  for (uint32_t g = 32; g >= 16; g /= 2) {
+    const uint32_t tl = (wf + g * unit - 1) / (g * unit);
+    if (tl * g < tiles * Gb) { Gb = g; tiles = tl; }
+  }
+  uint32_t grid = grid_for(bound_items * n_windows * tiles * Gb,
+                           nts_gather_blocks());
+  if (sched == NTS_SCHED_XCD) {
+    /* every class needs a workgroup and a window, its own or an even share
+     * of one; otherwise the current order runs */
+    const uint32_t cap8 = nts_gather_blocks() & ~7u;
+    if ((n_windows < 8 && n_windows != 4 && n_windows != 2) || grid < 8 ||
+        cap8 < 8) {
+      sched = NTS_SCHED_ITEM;
+      wf = slabf;
+    } else {
+      grid = min((grid + 7u) & ~7u, cap8);
+    }
+  }
+  const bool blocked =
+      n_windows > 1 && !(sched == NTS_SCHED_ITEM && wf == slabf);
+  GatherPlan pl;
+  if (blocked) {
+    G = Gb;
+    pl = GatherPlan{(uint32_t)sched, wf, n_windows, tiles};
+  } else {
+    /* exactly the pre-window launch */
+    sched = NTS_SCHED_ITEM;
+    wf = slabf;
+    grid = grid_for(bound_items * n_slabs * G);
+    pl = GatherPlan{NTS_SCHED_ITEM, slabf, n_slabs, 1u};
+  }
+  s->sched_last = sched;
+  s->window_last = (int)wf;
   Tic t(s, tag);
+#define NTS_LAUNCH_B(E, W, B)                                                 \
+  hipLaunchKernelGGL((k_gather_spmm<E, W, B>), dim3(grid), dim3(NTS_BLOCK),   \
+                     0, s->stream, ib.items, ib.counter, nbr, ew, in, out,    \
+                     nbr_start, f, G, pl)
 #define NTS_LAUNCH(E, W)                                                      \
-  hipLaunchKernelGGL((k_gather_spmm<E, W>), dim3(grid), dim3(NTS_BLOCK), 0,   \
-                     s->stream, ib.items, ib.counter, nbr, ew, in, out,       \
-                     nbr_start, f, G, n_slabs)
+  do {                                                                        \
+    if (blocked) NTS_LAUNCH_B(E, W, true);                                    \
+    else NTS_LAUNCH_B(E, W, false);                                           \
+  } while (0)
   if (with_weight) {
     if (elem == 4) NTS_LAUNCH(4, true);
     else if (elem == 2) NTS_LAUNCH(2, true);
@@ -1252,6 +1455,7 @@ void launch_gather(nts_stream *s, const float *in, float *out, const float *ew,
     else NTS_LAUNCH(1, false);
   }
 #undef NTS_LAUNCH
+#undef NTS_LAUNCH_B
   dbg_sync(s, "k_gather_spmm");
 }
 }  // namespace
@@ -1364,10 +1568,10 @@ void nts_gather_by_dst_from_src(nts_stream *s, const float *input,
                                 nts_vid dst_end, nts_vid edges,
                                 nts_vid batch_size, nts_vid feature_size,
                                 int with_weight) {
-  (void)src_end; (void)dst_start; (void)dst_end;
+  (void)dst_start; (void)dst_end;
   launch_gather(s, input, output, weight_forward, row_indices, column_offset,
                 src_start, batch_size, edges, feature_size, with_weight,
-                NTS_KTAG_FWD);
+                NTS_KTAG_FWD, src_end > src_start ? src_end - src_start : 0);
 }
 
 void nts_gather_by_src_from_dst(nts_stream *s, const float *input,
@@ -1378,10 +1582,21 @@ void nts_gather_by_src_from_dst(nts_stream *s, const float *input,
                                 nts_vid dst_start, nts_vid dst_end,
                                 nts_vid edges, nts_vid batch_size,
                                 nts_vid feature_size, int with_weight) {
-  (void)src_start; (void)src_end; (void)dst_end;
+  (void)src_start; (void)src_end;
   launch_gather(s, input, output, weight_backward, column_indices, row_offset,
                 dst_start, batch_size, edges, feature_size, with_weight,
-                NTS_KTAG_BWD);
+                NTS_KTAG_BWD, dst_end > dst_start ? dst_end - dst_start : 0);
+}
+
+void nts_gather_schedule(nts_stream *s, int schedule, int window_floats) {
+  s->sched_req = schedule;
+  s->window_req = window_floats;
+}
+
+void nts_gather_schedule_last(nts_stream *s, int *schedule,
+                              int *window_floats) {
+  if (schedule) *schedule = s->sched_last;
+  if (window_floats) *window_floats = s->window_last;
 }
 
 void nts_items_cache_clear(nts_stream *s) {
@@ -1760,7 +1975,7 @@ int nts_gather_by_src_from_dst_dot(nts_stream *s, const float *input,
      * caller must compute the dot with nts_edge_dot */
     launch_gather(s, input, output, weight_backward, column_indices,
                   row_offset, dst_start, batch_size, edges, f, 1,
-                  NTS_KTAG_BWD);
+                  NTS_KTAG_BWD, /*rows unknown*/ 0);
     return 0;
   }
   ItemsBuf &ib = get_items(s, row_offset, batch_size, edges);

@@ -73,6 +73,8 @@ def lib():
     l.nts_gather_by_dst_from_src.argtypes = [_vp] + [_vp] * 5 + [_u32] * 7 + [_i32]
     l.nts_gather_by_src_from_dst.argtypes = [_vp] + [_vp] * 5 + [_u32] * 7 + [_i32]
     l.nts_items_cache_clear.argtypes = [_vp]
+    l.nts_gather_schedule.argtypes = [_vp, _i32, _i32]
+    l.nts_gather_schedule_last.argtypes = [_vp, _vp, _vp]
     l.nts_deserialize_to_gpu.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _i32]
     l.nts_aggregate_comm_result.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _i32]
     l.nts_gather_rows.argtypes = [_vp, _vp, _vp, _vp, _u32, _u32, _u32]
@@ -290,6 +292,17 @@ class Stream:
         self._lib.nts_sample_reservoir_dbg_fallback(
             self.h, _vp(column_offset), _vp(row_indices), _vp(dst_list),
             n_dst, fanout, seed, _vp(out_src), _vp(out_cnt))
+
+    def gather_schedule(self, schedule=0, window_floats=0):
+        """Column schedule of the following gathers; (0, 0) = automatic."""
+        self._lib.nts_gather_schedule(self.h, schedule, window_floats)
+
+    def gather_schedule_last(self):
+        """(schedule, window_floats) the most recent gather ran."""
+        sched, window = _i32(0), _i32(0)
+        self._lib.nts_gather_schedule_last(self.h, _c.byref(sched),
+                                           _c.byref(window))
+        return sched.value, window.value
 
     def items_cache_clear(self):
         self._lib.nts_items_cache_clear(self.h)

@@ -125,11 +125,27 @@ enum nts_gather_sched {
  * Environment, for sweeps, when no request is set: NTS_GATHER_SCHED (forces,
  * 0 included) and NTS_GATHER_WINDOW; NTS_GATHER_BLOCKS caps the grid of the
  * column-blocked launches (default 2^20: one task per lane group up to
- * there, which is what lets NTS_SCHED_PHASE keep one window live). */
+ * there, which is what lets NTS_SCHED_PHASE keep one window live).
+ * The library reads no other environment than these three, NTS_SPLIT (max
+ * edges per work item, 256), NTS_MAX_BLOCKS (grid cap of every other launch,
+ * 8192) and NTS_DEBUG_SYNC (synchronize and check after every launch). */
 void nts_gather_schedule(nts_stream *s, int schedule, int window_floats);
 
 /* The schedule and window the stream's most recent gather actually ran. */
 void nts_gather_schedule_last(nts_stream *s, int *schedule, int *window_floats);
+
+/* The launch decision a gather of this shape would take, without touching
+ * the device: feature width, common alignment of the input and output
+ * pointers in bytes, rows of the gathered matrix (0 = unknown, as in the
+ * fused-dot fallback), offsets (batch_size) and edges, and a request as for
+ * nts_gather_schedule; the environment counts as it does for a launch.
+ * Returns the schedule and window that run, the lane group, the vector
+ * width per lane (4, 2 or 1 dwords), the grid in workgroups, and whether the
+ * column-blocked kernel instantiation runs.  Any out pointer may be NULL. */
+void nts_gather_plan(nts_vid feature_size, unsigned alignment_bytes,
+    nts_vid rows, nts_vid batch_size, nts_vid edges, int schedule_req,
+    int window_req, int *schedule, int *window_floats, int *lane_group,
+    int *vector_width, int *grid, int *blocked);
 
 /* The two gather entry points decompose (offset, batch) into bounded
  * per-wavefront work items on device, rebuilt on every call into a

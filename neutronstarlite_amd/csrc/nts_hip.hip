@@ -166,16 +166,79 @@ __global__ void k_build_items(const uint32_t *__restrict__ offset,
   }
 }
 
-/* ------------------------------------------------------------------ */
-/* THE aggregation kernel.  One lane GROUP of G<=64 lanes processes    */
-/* one (work item, feature slab): loops the item's edges, vector-loads */
-/* the neighbor row slab coalesced, fma-accumulates in registers, then */
-/* stores once (RMW for exclusive vertices, atomicAdd for split hubs). */
-/* ELEM = vector width per lane: 4 (dwordx4), 2 (dwordx2), or 1 with   */
-/* NSTR=4 strided dwords (handles any f and any 4-byte alignment).     */
-/* Forward CSC:  nbr = row_indices   (global src),  out rows = dst.    */
-/* Backward CSR: nbr = column_indices (global dst), out rows = src.    */
-/* ------------------------------------------------------------------ */
+/* ---- device helpers shared by the item-driven kernels ---- */
+struct Item {
+  uint32_t v;   /* vertex (row of the offset array) */
+  bool shared;  /* vertex split into several items: merge with atomics */
+  uint32_t e0, cnt;
+};
+__device__ __forceinline__ Item load_item(const uint4 *__restrict__ items,
+                                          uint32_t it) {
+  const uint4 x = items[it];
+  return Item{x.x & 0x7fffffffu, (x.x >> 31) != 0, x.y, x.z};
+}
+
+/* wave-per-item loops: for (it = w.wave; it < n_items; it += w.n_waves) */
+struct WaveId { uint32_t wave, lane, n_waves; };
+__device__ __forceinline__ WaveId wave_id() {
+  return WaveId{(blockIdx.x * blockDim.x + threadIdx.x) >> 6,
+                threadIdx.x & 63u, (gridDim.x * blockDim.x) >> 6};
+}
+
+/* 64-lane butterfly sum, xor 32..1 in that order (every lane gets it) */
+template <typename T>
+__device__ __forceinline__ T wave_sum(T x) {
+#pragma unroll
+  for (int w = 32; w >= 1; w >>= 1) x += __shfl_xor(x, w, 64);
+  return x;
+}
+/* same butterfly, keeping the smallest candidate and where it sits */
+__device__ __forceinline__ void wave_min(unsigned long long &best,
+                                         uint32_t &pos) {
+#pragma unroll
+  for (int w = 32; w >= 1; w >>= 1) {
+    const unsigned long long ob = __shfl_xor(best, w, 64);
+    const uint32_t op = __shfl_xor(pos, w, 64);
+    if (ob < best) { best = ob; pos = op; }
+  }
+}
+
+template <int N>
+using fvec = float __attribute__((ext_vector_type(N)));  /* dwordxN access */
+
+/* o[0..nv) += acc: plain read-modify-write for an exclusive vertex (one
+ * vector access when the lane is full), atomicAdd for a split one */
+template <int ELEM>
+__device__ __forceinline__ void store_acc(float *o, const float (&acc)[ELEM],
+                                          int nv, bool shared) {
+  if (shared) {
+    for (int j = 0; j < nv; ++j) atomicAdd(&o[j], acc[j]);
+  } else if (nv == ELEM) {
+    fvec<ELEM> y = *reinterpret_cast<fvec<ELEM> *>(o);
+#pragma unroll
+    for (int j = 0; j < ELEM; ++j) y[j] += acc[j];
+    *reinterpret_cast<fvec<ELEM> *>(o) = y;
+  } else {
+    for (int j = 0; j < nv; ++j) o[j] += acc[j];
+  }
+}
+/* strided twin: element j at o[j*G], live while col + j*G < fend */
+template <int NSTR>
+__device__ __forceinline__ void store_strided(float *o,
+                                              const float (&acc)[NSTR],
+                                              uint32_t G, uint32_t col,
+                                              uint32_t fend, bool shared) {
+  if (!shared) {
+#pragma unroll
+    for (int j = 0; j < NSTR; ++j)
+      if (col + j * G < fend) o[j * G] += acc[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < NSTR; ++j)
+      if (col + j * G < fend) atomicAdd(&o[j * G], acc[j]);
+  }
+}
+
 /* Column scheduling (BLOCKED): a task is (work item, column window of wf */
 /* floats, tile of the lane group inside the window).  The schedules    */
 /* only permute which task a group runs when — each output element is   */
@@ -200,6 +263,165 @@ struct GatherPlan {
   uint32_t tiles;     /* lane-group tiles per window: ceil(wf / tilef) */
 };
 
+/* XCD schedule: what the workgroups of class blockIdx.x % 8 own */
+struct XcdClass {
+  uint32_t cls = 0;     /* blockIdx.x % 8 */
+  uint32_t cpw = 0;     /* classes per window when there are 2 or 4, else 0 */
+  uint32_t stripe = 0;  /* tasks per item in a class's own windows/8 stripe */
+  uint32_t rest = 0;    /* tasks per item in the windows%8 left over */
+  uint64_t striped = 0; /* this class's tasks inside its stripe */
+};
+struct TaskRange { uint64_t t0, stride, total; };
+struct Task { uint32_t it, fbase, fend; };
+
+/* XCD: a group's first task, stride and task count among the workgroups of
+ * its class; fills xc for decode_task */
+__device__ __forceinline__ TaskRange xcd_range(const GatherPlan &pl,
+                                               uint32_t n_items, uint32_t G,
+                                               XcdClass &xc) {
+  const uint32_t gpb = NTS_BLOCK / G;
+  xc.cls = blockIdx.x & 7u;
+  xc.stripe = (pl.n_windows >> 3) * pl.tiles;
+  xc.rest = (pl.n_windows & 7u) * pl.tiles;
+  TaskRange r;
+  r.t0 = (uint64_t)(blockIdx.x >> 3) * gpb + threadIdx.x / G;
+  r.stride = (uint64_t)((gridDim.x - xc.cls + 7u) >> 3) * gpb;
+  if (pl.n_windows >= 8) {
+    xc.striped = (uint64_t)n_items * xc.stripe;
+    const uint64_t shared = (uint64_t)n_items * xc.rest;
+    r.total =
+        xc.striped + (shared > xc.cls ? (shared - xc.cls + 7u) >> 3 : 0u);
+  } else {
+    /* 2 or 4 windows: 8/windows classes share one, items dealt round */
+    xc.cpw = 8u / pl.n_windows;
+    const uint32_t sub = xc.cls % xc.cpw;
+    r.total = n_items > sub
+                  ? (uint64_t)((n_items - sub + xc.cpw - 1) / xc.cpw) * pl.tiles
+                  : 0u;
+  }
+  return r;
+}
+
+/* task index -> (work item, first column, column bound); fbase >= fend
+ * marks a tile past a short last window */
+template <bool BLOCKED>
+__device__ __forceinline__ Task decode_task(const GatherPlan &pl,
+                                            const XcdClass &xc, uint64_t t,
+                                            uint32_t n_items, uint32_t f,
+                                            uint32_t tilef) {
+  const uint32_t per_item = pl.n_windows * pl.tiles;
+  if constexpr (!BLOCKED) {
+    return Task{(uint32_t)(t / per_item), (uint32_t)(t % per_item) * tilef, f};
+  } else {
+    uint32_t it, win, tile;
+    if (pl.sched == NTS_SCHED_ITEM) {
+      it = (uint32_t)(t / per_item);
+      const uint32_t r = (uint32_t)(t % per_item);
+      win = r / pl.tiles;
+      tile = r % pl.tiles;
+    } else if (pl.sched == NTS_SCHED_PHASE) {
+      const uint64_t per_win = (uint64_t)n_items * pl.tiles;
+      win = (uint32_t)(t / per_win);
+      const uint64_t r = t % per_win;
+      it = (uint32_t)(r / pl.tiles);
+      tile = (uint32_t)(r % pl.tiles);
+    } else if (xc.cpw) { /* NTS_SCHED_XCD, a window shared by cpw classes */
+      it = xc.cls % xc.cpw + xc.cpw * (uint32_t)(t / pl.tiles);
+      win = xc.cls / xc.cpw;
+      tile = (uint32_t)(t % pl.tiles);
+    } else if (t < xc.striped) { /* NTS_SCHED_XCD, own stripe */
+      it = (uint32_t)(t / xc.stripe);
+      const uint32_t r = xc.cls * xc.stripe + (uint32_t)(t % xc.stripe);
+      win = r / pl.tiles;
+      tile = r % pl.tiles;
+    } else { /* NTS_SCHED_XCD, every 8th task of the left-over windows */
+      const uint64_t r = xc.cls + 8u * (t - xc.striped);
+      it = (uint32_t)(r / xc.rest);
+      const uint32_t j = 8u * xc.stripe + (uint32_t)(r % xc.rest);
+      win = j / pl.tiles;
+      tile = j % pl.tiles;
+    }
+    return Task{it, win * pl.wf + tile * tilef, min(f, (win + 1) * pl.wf)};
+  }
+}
+
+/* the gathered side of one launch */
+struct GatherSrc {
+  const uint32_t *nbr;
+  const float *ew;
+  const float *in;
+  uint32_t nbr_start, f;
+};
+
+/* acc += w[k] * row k for K full vector lanes; fmaf order edge-major,
+ * element-minor, all K loads issued before the first fmaf */
+template <int ELEM, int K>
+__device__ __forceinline__ void fma_vec(float (&acc)[ELEM],
+                                        const float *const (&p)[K],
+                                        const float (&wv)[K]) {
+  fvec<ELEM> x[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+    x[k] = *reinterpret_cast<const fvec<ELEM> *>(p[k]);
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int j = 0; j < ELEM; ++j) acc[j] = fmaf(wv[k], x[k][j], acc[j]);
+}
+/* strided dword twin: element j at p[k][j*G], live while col + j*G < fend */
+template <int NSTR, int K>
+__device__ __forceinline__ void fma_strided(float (&acc)[NSTR],
+                                            const float *const (&p)[K],
+                                            const float (&wv)[K], uint32_t G,
+                                            uint32_t col, uint32_t fend) {
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int j = 0; j < NSTR; ++j)
+      if (col + j * G < fend) acc[j] = fmaf(wv[k], p[k][j * G], acc[j]);
+}
+
+/* K consecutive edges from e on, this lane's columns from col on */
+template <int ELEM, bool WITH_W, int K, int N>
+__device__ __forceinline__ void accum_edges(float (&acc)[N],
+                                            const GatherSrc &g, uint32_t e,
+                                            uint32_t col, uint32_t G,
+                                            uint32_t fend) {
+  const float *p[K];
+  float wv[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    p[k] = g.in + (uint64_t)(g.nbr[e + k] - g.nbr_start) * g.f + col;
+    wv[k] = WITH_W ? g.ew[e + k] : 1.0f;
+  }
+  if constexpr (ELEM == 1) fma_strided<N, K>(acc, p, wv, G, col, fend);
+  else fma_vec<ELEM, K>(acc, p, wv);
+}
+
+/* one item's edges for a full lane: 4 at a time — 4 independent row loads
+ * in flight per wave (one dependent load per iteration leaves HBM latency
+ * exposed) — then the tail one by one */
+template <int ELEM, bool WITH_W, int N>
+__device__ __forceinline__ void accum_item(float (&acc)[N], const GatherSrc &g,
+                                           const Item &im, uint32_t col,
+                                           uint32_t G, uint32_t fend) {
+  uint32_t e = im.e0;
+  const uint32_t e_end = im.e0 + im.cnt;
+  for (; e + 4 <= e_end; e += 4)
+    accum_edges<ELEM, WITH_W, 4>(acc, g, e, col, G, fend);
+  for (; e < e_end; ++e) accum_edges<ELEM, WITH_W, 1>(acc, g, e, col, G, fend);
+}
+
+/* ------------------------------------------------------------------ */
+/* THE aggregation kernel. One lane GROUP of G<=64 lanes processes    */
+/* one (work item, feature slab): loops the item's edges, vector-loads */
+/* the neighbor row slab coalesced, fma-accumulates in registers, then */
+/* stores once (RMW for exclusive vertices, atomicAdd for split hubs). */
+/* ELEM = vector width per lane: 4 (dwordx4), 2 (dwordx2), or 1 with   */
+/* NSTR=4 strided dwords (handles any f and any 4-byte alignment).     */
+/* Forward CSC:  nbr = row_indices   (global src),  out rows = dst.    */
+/* Backward CSR: nbr = column_indices (global dst), out rows = src.    */
+/* ------------------------------------------------------------------ */
 template <int ELEM, bool WITH_W, bool BLOCKED>
 __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm(
     const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
@@ -210,206 +432,45 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm(
   const uint32_t n_items = *n_items_p;
   const uint32_t glane = threadIdx.x & (G - 1);
   const uint32_t tilef = G * ELEM * NSTR;
-  const uint32_t per_item = pl.n_windows * pl.tiles;
+  const GatherSrc g{nbr, ew, in, nbr_start, f};
   /* group index and stride: over the whole grid, or (XCD-affine) over the
-   * workgroups of this block's class blockIdx.x % 8 */
-  uint64_t t0, stride, total;
-  uint32_t cls = 0, cpw = 0;
-  const uint32_t stripe = (pl.n_windows >> 3) * pl.tiles; /* XCD: per item */
-  const uint32_t rest = (pl.n_windows & 7u) * pl.tiles;
-  uint64_t striped = 0; /* XCD: this class's tasks inside its stripe */
+   * workgroups of this block's class (every launch is NTS_BLOCK wide) */
+  XcdClass xc;
+  TaskRange r;
   if (BLOCKED && pl.sched == NTS_SCHED_XCD) {
-    const uint32_t gpb = blockDim.x / G;
-    cls = blockIdx.x & 7u;
-    t0 = (uint64_t)(blockIdx.x >> 3) * gpb + threadIdx.x / G;
-    stride = (uint64_t)((gridDim.x - cls + 7u) >> 3) * gpb;
-    if (pl.n_windows >= 8) {
-      striped = (uint64_t)n_items * stripe;
-      const uint64_t shared = (uint64_t)n_items * rest;
-      total = striped + (shared > cls ? (shared - cls + 7u) >> 3 : 0u);
-    } else {
-      /* 2 or 4 windows: 8/windows classes share one, items dealt round */
-      cpw = 8u / pl.n_windows;
-      const uint32_t sub = cls % cpw;
-      total = n_items > sub
-                  ? (uint64_t)((n_items - sub + cpw - 1) / cpw) * pl.tiles : 0u;
-    }
+    r = xcd_range(pl, n_items, G, xc);
   } else {
-    t0 = (blockIdx.x * blockDim.x + threadIdx.x) / G;
-    stride = (gridDim.x * blockDim.x) / G;
-    total = (uint64_t)n_items * per_item;
+    r.t0 = (blockIdx.x * NTS_BLOCK + threadIdx.x) / G;
+    r.stride = (gridDim.x * NTS_BLOCK) / G;
+    r.total = (uint64_t)n_items * (pl.n_windows * pl.tiles);
   }
 
-  for (uint64_t t = t0; t < total; t += stride) {
-    uint32_t it, fbase, fend;
-    if constexpr (!BLOCKED) {
-      it = (uint32_t)(t / per_item);
-      fbase = (uint32_t)(t % per_item) * tilef;
-      fend = f;
-    } else {
-      uint32_t win, tile;
-      if (pl.sched == NTS_SCHED_ITEM) {
-        it = (uint32_t)(t / per_item);
-        const uint32_t r = (uint32_t)(t % per_item);
-        win = r / pl.tiles;
-        tile = r % pl.tiles;
-      } else if (pl.sched == NTS_SCHED_PHASE) {
-        const uint64_t per_win = (uint64_t)n_items * pl.tiles;
-        win = (uint32_t)(t / per_win);
-        const uint64_t r = t % per_win;
-        it = (uint32_t)(r / pl.tiles);
-        tile = (uint32_t)(r % pl.tiles);
-      } else if (cpw) { /* NTS_SCHED_XCD, a window shared by cpw classes */
-        it = cls % cpw + cpw * (uint32_t)(t / pl.tiles);
-        win = cls / cpw;
-        tile = (uint32_t)(t % pl.tiles);
-      } else if (t < striped) { /* NTS_SCHED_XCD, own stripe */
-        it = (uint32_t)(t / stripe);
-        const uint32_t r = cls * stripe + (uint32_t)(t % stripe);
-        win = r / pl.tiles;
-        tile = r % pl.tiles;
-      } else { /* NTS_SCHED_XCD, every 8th task of the left-over windows */
-        const uint64_t r = cls + 8u * (t - striped);
-        it = (uint32_t)(r / rest);
-        const uint32_t j = 8u * stripe + (uint32_t)(r % rest);
-        win = j / pl.tiles;
-        tile = j % pl.tiles;
-      }
-      fbase = win * pl.wf + tile * tilef;
-      fend = min(f, (win + 1) * pl.wf);
-      if (fbase >= fend) continue; /* tile past a short last window */
-    }
-    const uint4 itm = items[it];
-    const uint32_t v = itm.x & 0x7fffffffu;
-    const bool shared_v = (itm.x >> 31) != 0;
-    const uint32_t e0 = itm.y, cnt = itm.z;
-
+  for (uint64_t t = r.t0; t < r.total; t += r.stride) {
+    const Task tk = decode_task<BLOCKED>(pl, xc, t, n_items, f, tilef);
+    if (BLOCKED && tk.fbase >= tk.fend) continue;
+    const Item im = load_item(items, tk.it);
     float acc[ELEM * NSTR] = {};
+    const uint32_t col = tk.fbase + glane * ELEM;
     if constexpr (ELEM == 1) {
-      /* strided dword path: element j at fbase + glane + j*G */
-      bool any = fbase + glane < fend;
-      if (any) {
-        /* 4-edge unroll: 4 independent row loads in flight per wave
-         * (one dependent load per iteration leaves HBM latency exposed) */
-        uint32_t e = e0;
-        const uint32_t e_end = e0 + cnt;
-        for (; e + 4 <= e_end; e += 4) {
-          const float *p[4];
-          float wv[4];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            p[k] = in + (uint64_t)(nbr[e + k] - nbr_start) * f + fbase + glane;
-            wv[k] = WITH_W ? ew[e + k] : 1.0f;
-          }
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int j = 0; j < NSTR; ++j)
-              if (fbase + glane + j * G < fend)
-                acc[j] = fmaf(wv[k], p[k][j * G], acc[j]);
-        }
-        for (; e < e_end; ++e) {
-          const uint64_t src = nbr[e] - nbr_start;
-          const float w = WITH_W ? ew[e] : 1.0f;
-          const float *p = in + src * f + fbase + glane;
-#pragma unroll
-          for (int j = 0; j < NSTR; ++j)
-            if (fbase + glane + j * G < fend) acc[j] = fmaf(w, p[j * G], acc[j]);
-        }
-        float *o = out + (uint64_t)v * f + fbase + glane;
-        if (!shared_v) {
-#pragma unroll
-          for (int j = 0; j < NSTR; ++j)
-            if (fbase + glane + j * G < fend) o[j * G] += acc[j];
-        } else {
-#pragma unroll
-          for (int j = 0; j < NSTR; ++j)
-            if (fbase + glane + j * G < fend) atomicAdd(&o[j * G], acc[j]);
-        }
+      if (col < tk.fend) {
+        accum_item<1, WITH_W>(acc, g, im, col, G, tk.fend);
+        store_strided(out + (uint64_t)im.v * f + col, acc, G, col, tk.fend,
+                      im.shared);
       }
     } else {
-      const uint32_t off = fbase + glane * ELEM;
-      const int nv = (off + ELEM <= fend) ? ELEM : (off < fend ? (int)(fend - off) : 0);
+      const int nv = (col + ELEM <= tk.fend)
+                         ? ELEM : (col < tk.fend ? (int)(tk.fend - col) : 0);
       if (nv == ELEM) {
-        /* 4-edge unroll: 4 independent vector row loads in flight */
-        uint32_t e = e0;
-        const uint32_t e_end = e0 + cnt;
-        for (; e + 4 <= e_end; e += 4) {
-          const float *p[4];
-          float wv[4];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            p[k] = in + (uint64_t)(nbr[e + k] - nbr_start) * f + off;
-            wv[k] = WITH_W ? ew[e + k] : 1.0f;
-          }
-          if constexpr (ELEM == 4) {
-            float4 x[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-              x[k] = *reinterpret_cast<const float4 *>(p[k]);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              acc[0] = fmaf(wv[k], x[k].x, acc[0]);
-              acc[1] = fmaf(wv[k], x[k].y, acc[1]);
-              acc[2] = fmaf(wv[k], x[k].z, acc[2]);
-              acc[3] = fmaf(wv[k], x[k].w, acc[3]);
-            }
-          } else {
-            float2 x[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-              x[k] = *reinterpret_cast<const float2 *>(p[k]);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-              acc[0] = fmaf(wv[k], x[k].x, acc[0]);
-              acc[1] = fmaf(wv[k], x[k].y, acc[1]);
-            }
-          }
-        }
-        for (; e < e_end; ++e) {
-          const uint64_t src = nbr[e] - nbr_start;
+        accum_item<ELEM, WITH_W>(acc, g, im, col, G, tk.fend);
+      } else if (nv > 0) { /* ragged last lane: scalar columns */
+        for (uint32_t e = im.e0; e < im.e0 + im.cnt; ++e) {
           const float w = WITH_W ? ew[e] : 1.0f;
-          const float *p = in + src * f + off;
-          if constexpr (ELEM == 4) {
-            const float4 x = *reinterpret_cast<const float4 *>(p);
-            acc[0] = fmaf(w, x.x, acc[0]);
-            acc[1] = fmaf(w, x.y, acc[1]);
-            acc[2] = fmaf(w, x.z, acc[2]);
-            acc[3] = fmaf(w, x.w, acc[3]);
-          } else {
-            const float2 x = *reinterpret_cast<const float2 *>(p);
-            acc[0] = fmaf(w, x.x, acc[0]);
-            acc[1] = fmaf(w, x.y, acc[1]);
-          }
-        }
-      } else if (nv > 0) {
-        for (uint32_t e = e0; e < e0 + cnt; ++e) {
-          const uint64_t src = nbr[e] - nbr_start;
-          const float w = WITH_W ? ew[e] : 1.0f;
-          const float *p = in + src * f + off;
+          const float *p = in + (uint64_t)(nbr[e] - nbr_start) * f + col;
           for (int j = 0; j < nv; ++j) acc[j] = fmaf(w, p[j], acc[j]);
         }
       }
-      if (nv > 0) {
-        float *o = out + (uint64_t)v * f + off;
-        if (!shared_v) {
-          if (nv == ELEM) {
-            if constexpr (ELEM == 4) {
-              float4 y = *reinterpret_cast<float4 *>(o);
-              y.x += acc[0]; y.y += acc[1]; y.z += acc[2]; y.w += acc[3];
-              *reinterpret_cast<float4 *>(o) = y;
-            } else {
-              float2 y = *reinterpret_cast<float2 *>(o);
-              y.x += acc[0]; y.y += acc[1];
-              *reinterpret_cast<float2 *>(o) = y;
-            }
-          } else {
-            for (int j = 0; j < nv; ++j) o[j] += acc[j];
-          }
-        } else {
-          for (int j = 0; j < nv; ++j) atomicAdd(&o[j], acc[j]);
-        }
-      }
+      if (nv > 0)
+        store_acc<ELEM>(out + (uint64_t)im.v * f + col, acc, nv, im.shared);
     }
   }
 }
@@ -420,18 +481,16 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm(
  * gs[e] = dot(grad_y[dst(e)], h[src]) — the attention-scalar gradient the
  * separate k_edge_dot kernel re-reads ~E*f floats to compute (9 ms of the
  * 34 ms round-1 GAT step at Reddit scale).  h[src] is loaded once per
- * (item, lane) into registers; the per-edge dot reduces across the lane
- * group with xor shuffles and lane 0 writes gs to dot_pos[e] (the CSR->CSC
- * slot map, so the softmax backward consumes it without a permute pass).
+ * (item, lane) into registers.  The per-edge dot is reduced across the lane
+ * group through LDS: lanes stash their per-edge partials for a batch of
+ * NTS_DOT_B edges into padded LDS, then NTS_DOT_B lanes each sum one edge's
+ * G partials with conflict-free stride-(G+1) reads — ~2 LDS ops per lane
+ * per edge and the reads pipeline, where a log2(G)-step shuffle chain per
+ * edge pays ds_permute latency on every edge (3.1 ms/step slower, DESIGN
+ * section 3).  The sum goes to dot_pos[e] (the CSR->CSC slot map, so the
+ * softmax backward consumes it without a permute pass).
  * Clean-case kernel: f % ELEM == 0 and f <= G*ELEM (one slab) — the
  * launcher falls back to the unfused pair otherwise. */
-/* Batched-LDS variant of the per-edge dot reduction: instead of a
- * log2(G)-step shuffle chain per edge (ds_permute latency on every edge),
- * lanes stash their per-edge partials for a batch of NTS_DOT_B edges into
- * padded LDS, then NTS_DOT_B lanes each sum one edge's G partials with
- * conflict-free stride-(G+1) reads — ~2 LDS ops per lane per edge and the
- * reads pipeline.  The gather accumulation is identical to
- * k_gather_spmm_dot (registers, RMW/atomic store). */
 constexpr uint32_t NTS_DOT_B = 16; /* edges per LDS transpose batch */
 
 template <int ELEM>
@@ -451,12 +510,10 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm_dot_lds(
   const uint32_t n_groups = (gridDim.x * blockDim.x) / G;
   float *gl = lds + (threadIdx.x / G) * NTS_DOT_B * (G + 1);
   for (uint32_t it = tid / G; it < n_items; it += n_groups) {
-    const uint4 itm = items[it];
-    const uint32_t v = itm.x & 0x7fffffffu;
-    const bool shared_v = (itm.x >> 31) != 0;
-    const uint32_t e0 = itm.y, cnt = itm.z;
+    const Item im = load_item(items, it);
+    const uint32_t v = im.v, e0 = im.e0, cnt = im.cnt;
     const uint32_t off = glane * ELEM;
-    const bool act = off + ELEM <= f;
+    const bool act = off + ELEM <= f; /* f%ELEM==0: lane is full or idle */
     float acc[ELEM] = {};
     float hreg[ELEM] = {};
     if (act) {
@@ -516,107 +573,7 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm_dot_lds(
       }
       __builtin_amdgcn_wave_barrier();
     }
-    if (act) {
-      float *o = out + (uint64_t)v * f + off;
-      if (!shared_v) {
-#pragma unroll
-        for (int j = 0; j < ELEM; ++j) o[j] += acc[j];
-      } else {
-#pragma unroll
-        for (int j = 0; j < ELEM; ++j) atomicAdd(&o[j], acc[j]);
-      }
-    }
-  }
-}
-
-template <int ELEM>
-__global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm_dot(
-    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    const uint32_t *__restrict__ nbr, const float *__restrict__ ew,
-    const float *__restrict__ in, float *__restrict__ out, uint32_t nbr_start,
-    const float *__restrict__ dot_vec, float *__restrict__ dot_out,
-    const uint32_t *__restrict__ dot_pos, uint32_t f, uint32_t G) {
-  const uint32_t n_items = *n_items_p;
-  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t glane = threadIdx.x & (G - 1);
-  const uint32_t n_groups = (gridDim.x * blockDim.x) / G;
-  for (uint32_t it = tid / G; it < n_items; it += n_groups) {
-    const uint4 itm = items[it];
-    const uint32_t v = itm.x & 0x7fffffffu;
-    const bool shared_v = (itm.x >> 31) != 0;
-    const uint32_t e0 = itm.y, cnt = itm.z;
-    const uint32_t off = glane * ELEM;
-    const bool act = off + ELEM <= f; /* f%ELEM==0: lane is full or idle */
-    float acc[ELEM] = {};
-    float hreg[ELEM] = {};
-    if (act) {
-      const float *hp = dot_vec + (uint64_t)v * f + off;
-#pragma unroll
-      for (int j = 0; j < ELEM; ++j) hreg[j] = hp[j];
-    }
-    uint32_t e = e0;
-    const uint32_t e_end = e0 + cnt;
-    for (; e + 4 <= e_end; e += 4) {
-      float dp[4] = {};
-      if (act) {
-        const float *p[4];
-        float wv[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          p[k] = in + (uint64_t)(nbr[e + k] - nbr_start) * f + off;
-          wv[k] = ew[e + k];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#pragma unroll
-          for (int j = 0; j < ELEM; ++j) {
-            const float x = p[k][j];
-            acc[j] = fmaf(wv[k], x, acc[j]);
-            dp[k] = fmaf(hreg[j], x, dp[k]);
-          }
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-#pragma unroll
-        for (int w = 32; w >= 1; w >>= 1) {
-          if ((uint32_t)w < G) dp[k] += __shfl_xor(dp[k], w, 64);
-        }
-      }
-      if (glane == 0) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          dot_out[dot_pos ? dot_pos[e + k] : e + k] = dp[k];
-      }
-    }
-    for (; e < e_end; ++e) {
-      float dp = 0.f;
-      if (act) {
-        const float w = ew[e];
-        const float *p = in + (uint64_t)(nbr[e] - nbr_start) * f + off;
-#pragma unroll
-        for (int j = 0; j < ELEM; ++j) {
-          const float x = p[j];
-          acc[j] = fmaf(w, x, acc[j]);
-          dp = fmaf(hreg[j], x, dp);
-        }
-      }
-#pragma unroll
-      for (int w = 32; w >= 1; w >>= 1) {
-        if ((uint32_t)w < G) dp += __shfl_xor(dp, w, 64);
-      }
-      if (glane == 0) dot_out[dot_pos ? dot_pos[e] : e] = dp;
-    }
-    if (act) {
-      float *o = out + (uint64_t)v * f + off;
-      if (!shared_v) {
-#pragma unroll
-        for (int j = 0; j < ELEM; ++j) o[j] += acc[j];
-      } else {
-#pragma unroll
-        for (int j = 0; j < ELEM; ++j) atomicAdd(&o[j], acc[j]);
-      }
-    }
+    if (act) store_acc<ELEM>(out + (uint64_t)v * f + off, acc, ELEM, im.shared);
   }
 }
 
@@ -638,6 +595,32 @@ __device__ __forceinline__ uint32_t k_hash_u32(unsigned long long seed,
 
 constexpr uint32_t NTS_MAX_FANOUT = 1024;
 
+/* Selection: out[pick] = src[slot] for the k smallest (key, slot) of the m
+ * candidates one wave holds in LDS, smallest first.  The slot in the low
+ * bits makes tie-breaks deterministic in the edge slot.  A taken candidate
+ * is overwritten with all-ones, so it reads as ~0ULL and a genuine max-key
+ * candidate can never be shadowed. */
+__device__ __forceinline__ void select_smallest(
+    uint32_t *s_key, uint32_t *s_slot, uint32_t m, uint32_t k, uint32_t lane,
+    uint32_t *__restrict__ out, const uint32_t *__restrict__ src) {
+  for (uint32_t pick = 0; pick < k; ++pick) {
+    unsigned long long best = ~0ULL;
+    uint32_t bp = 0;
+    for (uint32_t p = lane; p < m; p += 64) {
+      const unsigned long long cand =
+          ((unsigned long long)s_key[p] << 32) | s_slot[p];
+      if (cand < best) { best = cand; bp = p; }
+    }
+    wave_min(best, bp);
+    if (lane == 0) {
+      out[pick] = src[s_slot[bp]];
+      s_key[bp] = 0xFFFFFFFFu;
+      s_slot[bp] = 0xFFFFFFFFu;
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
 template <bool FORCE_FALLBACK /* test hook: skip the 32-bit search */>
 __global__ void k_sample_reservoir(const uint32_t *__restrict__ column_offset,
                                    const uint32_t *__restrict__ row_indices,
@@ -651,10 +634,9 @@ __global__ void k_sample_reservoir(const uint32_t *__restrict__ column_offset,
   __shared__ uint32_t s_key[4][CAP];
   __shared__ uint32_t s_slot[4][CAP];
   const uint32_t wib = threadIdx.x >> 6;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
-  for (uint32_t i = wave; i < n_dst; i += n_waves) {
+  const WaveId w = wave_id();
+  const uint32_t lane = w.lane;
+  for (uint32_t i = w.wave; i < n_dst; i += w.n_waves) {
     const uint32_t d = dst_list[i];
     const uint32_t e0 = column_offset[d];
     const uint32_t deg = column_offset[d + 1] - e0;
@@ -717,29 +699,8 @@ __global__ void k_sample_reservoir(const uint32_t *__restrict__ column_offset,
         s_slot[wib][j] = j;
       }
       __builtin_amdgcn_wave_barrier();
-      const uint32_t m = deg;
-      for (uint32_t pick = 0; pick < k; ++pick) {
-        unsigned long long best = ~0ULL;
-        uint32_t bp = 0;
-        for (uint32_t p = lane; p < m; p += 64) {
-          const unsigned long long cand =
-              ((unsigned long long)s_key[wib][p] << 32) | s_slot[wib][p];
-          if (cand < best) { best = cand; bp = p; }
-        }
-#pragma unroll
-        for (int w = 32; w >= 1; w >>= 1) {
-          const unsigned long long ob = __shfl_xor(best, w, 64);
-          const uint32_t op = __shfl_xor(bp, w, 64);
-          if (ob < best) { best = ob; bp = op; }
-        }
-        if (lane == 0) {
-          out_src[(uint64_t)i * fanout + pick] =
-              row_indices[e0 + s_slot[wib][bp]];
-          s_key[wib][bp] = 0xFFFFFFFFu;  /* removed: cand becomes ~0ULL */
-          s_slot[wib][bp] = 0xFFFFFFFFu;
-        }
-        __builtin_amdgcn_wave_barrier();
-      }
+      select_smallest(s_key[wib], s_slot[wib], deg, k, lane,
+                      out_src + (uint64_t)i * fanout, row_indices + e0);
       if (lane == 0) out_cnt[i] = k;
       continue;
     }
@@ -751,9 +712,7 @@ __global__ void k_sample_reservoir(const uint32_t *__restrict__ column_offset,
       uint32_t cnt = 0;
       for (uint32_t j = lane; j < deg; j += 64)
         cnt += (k_hash_u32(seed, 0, e0 + j) < T) ? 1u : 0u;
-#pragma unroll
-      for (int w = 32; w >= 1; w >>= 1)
-        cnt += __shfl_xor(cnt, w, 64);
+      cnt = wave_sum(cnt);
       if (cnt >= fanout && cnt <= cap) landed = true;
       else if (cnt < fanout) { lo = T; T = (T + hi + 1) / 2; }
       else { hi = T; T = (lo + T) / 2; }
@@ -782,9 +741,7 @@ __global__ void k_sample_reservoir(const uint32_t *__restrict__ column_offset,
               ((unsigned long long)k_hash_u32(seed, 0, e0 + j) << 32) | j;
           cnt += (cand < T64) ? 1u : 0u;
         }
-#pragma unroll
-        for (int w = 32; w >= 1; w >>= 1)
-          cnt += __shfl_xor(cnt, w, 64);
+        cnt = wave_sum(cnt);
         if (cnt >= fanout && cnt <= cap) break;
         if (cnt < fanout) { lo64 = T64; T64 = T64 + (hi64 - T64) / 2 + 1; }
         else { hi64 = T64; T64 = lo64 + (T64 - lo64) / 2; }
@@ -811,33 +768,8 @@ __global__ void k_sample_reservoir(const uint32_t *__restrict__ column_offset,
       base += (uint32_t)__popcll(bmask);
     }
     __builtin_amdgcn_wave_barrier();
-    const uint32_t m = base < CAP ? base : CAP;
-    /* selection: repeatedly pick the minimum (key, slot) — the slot in the
-     * low bits makes tie-breaks deterministic in the edge slot */
-    for (uint32_t pick = 0; pick < k; ++pick) {
-      unsigned long long best = ~0ULL;
-      uint32_t bp = 0;
-      for (uint32_t p = lane; p < m; p += 64) {
-        const unsigned long long cand =
-            ((unsigned long long)s_key[wib][p] << 32) | s_slot[wib][p];
-        if (cand < best) { best = cand; bp = p; }
-      }
-#pragma unroll
-      for (int w = 32; w >= 1; w >>= 1) {
-        const unsigned long long ob = __shfl_xor(best, w, 64);
-        const uint32_t op = __shfl_xor(bp, w, 64);
-        if (ob < best) { best = ob; bp = op; }
-      }
-      if (lane == 0) {
-        out_src[(uint64_t)i * fanout + pick] =
-            row_indices[e0 + s_slot[wib][bp]];
-        s_key[wib][bp] = 0xFFFFFFFFu;  /* removed: cand becomes ~0ULL so a
-                                          genuine max-key candidate can
-                                          never be shadowed */
-        s_slot[wib][bp] = 0xFFFFFFFFu;
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
+    select_smallest(s_key[wib], s_slot[wib], base < CAP ? base : CAP, k, lane,
+                    out_src + (uint64_t)i * fanout, row_indices + e0);
     if (lane == 0) out_cnt[i] = k;
   }
 }
@@ -918,15 +850,12 @@ __global__ void k_edge_items(const uint4 *__restrict__ items,
                              const uint32_t *__restrict__ mirror_index,
                              uint32_t f) {
   const uint32_t n_items = *n_items_p;
-  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
-  for (uint32_t it = wave; it < n_items; it += n_waves) {
-    const uint4 itm = items[it];
-    const uint32_t d = itm.x & 0x7fffffffu;
-    const uint32_t e0 = itm.y;
-    const uint64_t nel = (uint64_t)itm.z * f;
-    for (uint64_t i = lane; i < nel; i += 64) {
+  const WaveId w = wave_id();
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    const uint32_t d = im.v, e0 = im.e0;
+    const uint64_t nel = (uint64_t)im.cnt * f;
+    for (uint64_t i = w.lane; i < nel; i += 64) {
       const uint32_t e = e0 + (uint32_t)(i / f);
       const uint32_t r = (uint32_t)(i % f);
       uint64_t vrow;
@@ -954,26 +883,21 @@ __global__ void k_edge_softmax_sum(const uint4 *__restrict__ items,
                                    const float *__restrict__ cached,
                                    float *__restrict__ sums, uint32_t f) {
   const uint32_t n_items = *n_items_p;
-  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
-  for (uint32_t it = wave; it < n_items; it += n_waves) {
-    const uint4 itm = items[it];
-    const uint32_t d = itm.x & 0x7fffffffu;
-    const uint32_t e0 = itm.y;
+  const WaveId w = wave_id();
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
     for (uint32_t r = 0; r < f; ++r) {
       float part = 0.f;
-      for (uint32_t k = lane; k < itm.z; k += 64) {
-        const uint64_t m = (uint64_t)(e0 + k) * f + r;
+      for (uint32_t k = w.lane; k < im.cnt; k += 64) {
+        const uint64_t m = (uint64_t)(im.e0 + k) * f + r;
         float v;
         if (BACKWARD) v = in[m] * cached[m];
         else v = __expf(in[m]);
         out[m] = v;          /* stash pass-1 value; normalized in pass 2 */
         part += v;
       }
-#pragma unroll
-      for (int w = 32; w >= 1; w >>= 1) part += __shfl_xor(part, w, 64);
-      if (lane == 0) atomicAdd(&sums[(uint64_t)d * f + r], part);
+      part = wave_sum(part);
+      if (w.lane == 0) atomicAdd(&sums[(uint64_t)im.v * f + r], part);
     }
   }
 }
@@ -999,16 +923,13 @@ __global__ void k_edge_softmax_norm(const uint4 *__restrict__ items,
                                     float *__restrict__ dst_accum,
                                     uint32_t f) {
   const uint32_t n_items = *n_items_p;
-  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
-  for (uint32_t it = wave; it < n_items; it += n_waves) {
-    const uint4 itm = items[it];
-    const uint32_t d = itm.x & 0x7fffffffu;
-    const uint32_t e0 = itm.y;
-    const uint64_t nel = (uint64_t)itm.z * f;
+  const WaveId w = wave_id();
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    const uint32_t d = im.v, e0 = im.e0;
+    const uint64_t nel = (uint64_t)im.cnt * f;
     float gsum = 0.f; /* per-dst sum of the result (f==1 only) */
-    for (uint64_t i = lane; i < nel; i += 64) {
+    for (uint64_t i = w.lane; i < nel; i += 64) {
       const uint32_t e = e0 + (uint32_t)(i / f);
       const uint32_t r = (uint32_t)(i % f);
       const uint64_t m = (uint64_t)e * f + r;
@@ -1028,9 +949,8 @@ __global__ void k_edge_softmax_norm(const uint4 *__restrict__ items,
       /* the attention-scalar's per-destination reduction (gat.py g_dst),
        * emitted here instead of a separate f=1 gather pass; item-bounded,
        * so one fp32 atomic per (item, wave), hub-safe */
-#pragma unroll
-      for (int w = 32; w >= 1; w >>= 1) gsum += __shfl_xor(gsum, w, 64);
-      if (lane == 0) atomicAdd(&dst_accum[d], gsum);
+      gsum = wave_sum(gsum);
+      if (w.lane == 0) atomicAdd(&dst_accum[d], gsum);
     }
   }
 }
@@ -1052,17 +972,14 @@ __global__ void k_edge_att_sum(const uint4 *__restrict__ items,
                                const uint32_t *__restrict__ mirror_index,
                                float slope, float *__restrict__ sums) {
   const uint32_t n_items = *n_items_p;
-  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
-  for (uint32_t it = wave; it < n_items; it += n_waves) {
-    const uint4 itm = items[it];
-    const uint32_t d = itm.x & 0x7fffffffu;
-    const uint32_t e0 = itm.y;
+  const WaveId w = wave_id();
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    const uint32_t d = im.v;
     const float sd = s_dst[d];
     float part = 0.f;
-    for (uint32_t k = lane; k < itm.z; k += 64) {
-      const uint32_t e = e0 + k;
+    for (uint32_t k = w.lane; k < im.cnt; k += 64) {
+      const uint32_t e = im.e0 + k;
       const uint32_t src = row_indices[e];
       const float m = s_src[mirror_index ? mirror_index[src] : src] + sd;
       m_sum_out[e] = m;
@@ -1072,9 +989,8 @@ __global__ void k_edge_att_sum(const uint4 *__restrict__ items,
       out[e] = v;
       part += v;
     }
-#pragma unroll
-    for (int w = 32; w >= 1; w >>= 1) part += __shfl_xor(part, w, 64);
-    if (lane == 0) atomicAdd(&sums[d], part);
+    part = wave_sum(part);
+    if (w.lane == 0) atomicAdd(&sums[d], part);
   }
 }
 
@@ -1087,101 +1003,25 @@ __global__ void k_edge_att_sum(const uint4 *__restrict__ items,
 __global__ void k_weight_sum(const uint4 *__restrict__ items,
                              const uint32_t *__restrict__ n_items_p,
                              float *__restrict__ out,
-                             const float *__restrict__ w) {
+                             const float *__restrict__ weights) {
   const uint32_t n_items = *n_items_p;
-  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
-  for (uint32_t it = wave; it < n_items; it += n_waves) {
-    const uint4 itm = items[it];
-    const uint32_t v = itm.x & 0x7fffffffu;
-    const bool shared_v = (itm.x >> 31) != 0;
-    const uint32_t e0 = itm.y;
+  const WaveId w = wave_id();
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
     float part = 0.f;
-    for (uint32_t k = lane; k < itm.z; k += 64) part += w[e0 + k];
-#pragma unroll
-    for (int q = 32; q >= 1; q >>= 1) part += __shfl_xor(part, q, 64);
-    if (lane == 0) {
-      if (shared_v) atomicAdd(&out[v], part);
-      else out[v] += part;
+    for (uint32_t k = w.lane; k < im.cnt; k += 64) part += weights[im.e0 + k];
+    part = wave_sum(part);
+    if (w.lane == 0) {
+      if (im.shared) atomicAdd(&out[im.v], part);
+      else out[im.v] += part;
     }
   }
 }
 
 /* per-edge dot: out[e] = dot(dst_rows[d], src_rows[row_indices[e]-src_s]),
- * item-driven (bounded per-wave work even on power-law hubs); lanes stride
- * the feature dim per edge. */
-/* lane-per-edge variant of the edge dot: each lane owns one edge and walks
- * its source row sequentially (per-lane streaming; L1 serves the row's
- * cache lines) — 64 independent dot products in flight per wave vs one for
- * the wave-per-edge form.  Measured SLOWER (42.4 vs 34.3 ms/step on
- * config #5): kept selectable via NTS_EDGE_DOT=2 as a recorded
- * negative result. */
-__global__ void k_edge_dot_lpe(const uint4 *__restrict__ items,
-                               const uint32_t *__restrict__ n_items_p,
-                               float *__restrict__ out,
-                               const float *__restrict__ dst_rows,
-                               const float *__restrict__ src_rows,
-                               const uint32_t *__restrict__ row_indices,
-                               uint32_t src_start, uint32_t f) {
-  const uint32_t n_items = *n_items_p;
-  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
-  for (uint32_t it = wave; it < n_items; it += n_waves) {
-    const uint4 itm = items[it];
-    const uint32_t d = itm.x & 0x7fffffffu;
-    const uint32_t e0 = itm.y, cnt = itm.z;
-    const float *a = dst_rows + (uint64_t)d * f;
-    for (uint32_t ei = lane; ei < cnt; ei += 64) {
-      const uint32_t e = e0 + ei;
-      const float *b = src_rows + (uint64_t)(row_indices[e] - src_start) * f;
-      float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-      uint32_t j = 0;
-      for (; j + 4 <= f; j += 4) {
-        s0 = fmaf(a[j], b[j], s0);
-        s1 = fmaf(a[j + 1], b[j + 1], s1);
-        s2 = fmaf(a[j + 2], b[j + 2], s2);
-        s3 = fmaf(a[j + 3], b[j + 3], s3);
-      }
-      for (; j < f; ++j) s0 = fmaf(a[j], b[j], s0);
-      out[e] = ((s0 + s1) + (s2 + s3));
-    }
-  }
-}
-
-template <int GS>  /* lanes per edge; 64/GS edges concurrent per wave */
-__global__ void k_edge_dot_sg(const uint4 *__restrict__ items,
-                              const uint32_t *__restrict__ n_items_p,
-                              float *__restrict__ out,
-                              const float *__restrict__ dst_rows,
-                              const float *__restrict__ src_rows,
-                              const uint32_t *__restrict__ row_indices,
-                              uint32_t src_start, uint32_t f) {
-  const uint32_t n_items = *n_items_p;
-  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
-  const uint32_t sub = lane / GS;           /* which edge of the pair/quad */
-  const uint32_t sl = lane % GS;
-  constexpr uint32_t NSUB = 64 / GS;
-  for (uint32_t it = wave; it < n_items; it += n_waves) {
-    const uint4 itm = items[it];
-    const uint32_t d = itm.x & 0x7fffffffu;
-    const uint32_t e0 = itm.y, cnt = itm.z;
-    const float *a = dst_rows + (uint64_t)d * f;
-    for (uint32_t k = sub; k < cnt; k += NSUB) {
-      const uint32_t e = e0 + k;
-      const float *b = src_rows + (uint64_t)(row_indices[e] - src_start) * f;
-      float sum = 0.f;
-      for (uint32_t j = sl; j < f; j += GS) sum += a[j] * b[j];
-#pragma unroll
-      for (int w = GS / 2; w >= 1; w >>= 1) sum += __shfl_xor(sum, w, GS);
-      if (sl == 0) out[e] = sum;
-    }
-  }
-}
-
+ * item-driven (bounded per-wave work even on power-law hubs); one wave per
+ * edge, lanes stride the feature dim.  Measured against a lane-per-edge and
+ * a sub-group (16/32 lanes per edge) form, both slower. */
 __global__ void k_edge_dot(const uint4 *__restrict__ items,
                            const uint32_t *__restrict__ n_items_p,
                            float *__restrict__ out,
@@ -1190,14 +1030,12 @@ __global__ void k_edge_dot(const uint4 *__restrict__ items,
                            const uint32_t *__restrict__ row_indices,
                            uint32_t src_start, uint32_t f) {
   const uint32_t n_items = *n_items_p;
-  const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t n_waves = (gridDim.x * blockDim.x) >> 6;
-  for (uint32_t it = wave; it < n_items; it += n_waves) {
-    const uint4 itm = items[it];
-    const uint32_t d = itm.x & 0x7fffffffu;
-    const uint32_t e0 = itm.y, cnt = itm.z;
-    const float *a = dst_rows + (uint64_t)d * f;
+  const WaveId w = wave_id();
+  const uint32_t lane = w.lane;
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    const uint32_t e0 = im.e0, cnt = im.cnt;
+    const float *a = dst_rows + (uint64_t)im.v * f;
     /* 4-edge unroll: four independent source-row loads in flight */
     uint32_t k = 0;
     for (; k + 4 <= cnt; k += 4) {
@@ -1214,9 +1052,7 @@ __global__ void k_edge_dot(const uint4 *__restrict__ items,
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-#pragma unroll
-        for (int w = 32; w >= 1; w >>= 1)
-          sum[q] += __shfl_xor(sum[q], w, 64);
+        sum[q] = wave_sum(sum[q]);
         if (lane == 0) out[e0 + k + q] = sum[q];
       }
     }
@@ -1225,8 +1061,7 @@ __global__ void k_edge_dot(const uint4 *__restrict__ items,
       const float *b = src_rows + (uint64_t)(row_indices[e] - src_start) * f;
       float sum = 0.f;
       for (uint32_t j = lane; j < f; j += 64) sum += a[j] * b[j];
-#pragma unroll
-      for (int w = 32; w >= 1; w >>= 1) sum += __shfl_xor(sum, w, 64);
+      sum = wave_sum(sum);
       if (lane == 0) out[e] = sum;
     }
   }
@@ -1312,6 +1147,11 @@ ItemsBuf &get_items(nts_stream *s, const uint32_t *offset, uint32_t batch,
   return ib;
 }
 
+/* grid of the wave-per-item kernels: one wave per (bounded) work item */
+uint32_t items_grid(uint32_t batch, uint32_t edges) {
+  return grid_for(((uint64_t)batch + edges / NTS_SPLIT) * 64);
+}
+
 /* When the automatic choice engages a blocked column schedule:
  *  - the gathered matrix (rows x f x 4 B) must exceed the 256 MiB Infinity
  *    Cache, far past the 8 x 4 MiB of L2: below that every row stays cached
@@ -1329,63 +1169,86 @@ constexpr uint32_t NTS_BLOCK_MIN_REUSE = 32;
 constexpr int NTS_AUTO_SCHED = NTS_SCHED_PHASE;
 constexpr uint32_t NTS_AUTO_WINDOW = 0;
 
-/* Sweep overrides, read once like NTS_SPLIT: NTS_GATHER_SCHED forces a
- * schedule (0 = the current order), NTS_GATHER_WINDOW its window width in
- * floats (unset/0 = the schedule's default). */
-bool gather_sched_env(int *sched, int *window) {
-  static int v_s = -1, v_w = 0;
-  static bool init = false;
-  if (!init) {
+/* What the environment adds to a gather launch decision, read once like
+ * NTS_SPLIT.  Sweep overrides: NTS_GATHER_SCHED forces a schedule (0 = the
+ * current order), NTS_GATHER_WINDOW its window width in floats (unset/0 =
+ * the schedule's default). */
+struct GatherEnv {
+  bool forced = false;
+  int sched = 0, window = 0;
+  uint32_t split, max_blocks, gather_blocks;
+};
+const GatherEnv &gather_env() {
+  static const GatherEnv env = [] {
+    GatherEnv v;
     const char *e = getenv("NTS_GATHER_SCHED");
-    if (e && *e) v_s = atoi(e);
-    const char *w = getenv("NTS_GATHER_WINDOW");
-    if (w && *w) v_w = atoi(w);
-    init = true;
-  }
-  if (v_s < 0) return false;
-  *sched = v_s;
-  *window = v_w;
-  return true;
+    if (e && *e && atoi(e) >= 0) {
+      v.forced = true;
+      v.sched = atoi(e);
+      const char *w = getenv("NTS_GATHER_WINDOW");
+      if (w && *w) v.window = atoi(w);
+    }
+    v.split = NTS_SPLIT;
+    v.max_blocks = NTS_MAX_BLOCKS;
+    v.gather_blocks = nts_gather_blocks();
+    return v;
+  }();
+  return env;
 }
 
-void launch_gather(nts_stream *s, const float *in, float *out, const float *ew,
-                   const uint32_t *nbr, const uint32_t *offset,
-                   uint32_t nbr_start, uint32_t batch, uint32_t edges,
-                   uint32_t f, int with_weight, int tag, uint32_t rows) {
-  if (!batch || !edges || !f) return;
-  ItemsBuf &ib = get_items(s, offset, batch, edges);
-  const uintptr_t a = (uintptr_t)in | (uintptr_t)out;
+/* Vector width per lane (dwordx4 / dwordx2 / 4 strided dwords) from the
+ * width and the pointers' common alignment, and the lane group: the
+ * smallest power of two in [16,64] covering the slab work */
+struct GatherGeom { int elem, nstr; uint32_t G; };
+GatherGeom gather_geometry(uint32_t f, uintptr_t alignment) {
+  GatherGeom g;
+  if (f % 4 == 0 && alignment % 16 == 0) g.elem = 4;
+  else if (f % 2 == 0 && alignment % 8 == 0) g.elem = 2;
+  else g.elem = 1;
+  g.nstr = (g.elem == 1) ? 4 : 1;
+  const uint32_t unit = g.elem * g.nstr; /* floats per lane */
+  const uint32_t need = (f + unit - 1) / unit;
+  g.G = 64;
+  while (g.G / 2 >= need && g.G > 16) g.G /= 2;
+  return g;
+}
+
+/* The whole launch decision of one gather; pl.sched and pl.wf are the
+ * schedule and window that run. */
+struct GatherLaunch {
   int elem;
-  if (f % 4 == 0 && a % 16 == 0) elem = 4;
-  else if (f % 2 == 0 && a % 8 == 0) elem = 2;
-  else elem = 1;
-  const int nstr = (elem == 1) ? 4 : 1;
-  /* lane group: smallest power of two in [16,64] covering the slab work */
-  const uint32_t need = (f + elem * nstr - 1) / (elem * nstr);
-  uint32_t G = 64;
-  while (G / 2 >= need && G > 16) G /= 2;
-  const uint32_t slabf = G * elem * nstr;
+  uint32_t G, grid;
+  bool blocked;
+  GatherPlan pl;
+};
+
+/* Pure: no HIP call, no stream.  rows == 0 (row count unknown to the caller)
+ * never engages the automatic choice. */
+GatherLaunch plan_gather(uint32_t f, uintptr_t alignment, uint32_t rows,
+                         uint32_t batch, uint32_t edges, int sched_req,
+                         int window_req, const GatherEnv &env) {
+  const GatherGeom geo = gather_geometry(f, alignment);
+  const uint32_t elem = geo.elem;
+  const uint32_t unit = elem * geo.nstr; /* floats per lane */
+  const uint32_t slabf = geo.G * unit;
   const uint32_t n_slabs = (f + slabf - 1) / slabf;
-  const uint64_t bound_items = (uint64_t)batch + edges / NTS_SPLIT + 1;
+  const uint64_t bound_items = (uint64_t)batch + edges / env.split + 1;
 
   /* ---- column schedule: request (stream, then env) or automatic ---- */
   int sched = NTS_SCHED_ITEM;
   uint32_t wf = slabf;
-  int env_sched = 0, env_window = 0;
-  if (s->sched_req || s->window_req) {
-    sched = s->sched_req;
-    wf = s->window_req > 0 ? (uint32_t)s->window_req : 0;
-  } else if (gather_sched_env(&env_sched, &env_window)) {
-    sched = env_sched;
-    wf = env_window > 0 ? (uint32_t)env_window : 0;
+  if (sched_req || window_req) {
+    sched = sched_req;
+    wf = window_req > 0 ? (uint32_t)window_req : 0;
+  } else if (env.forced) {
+    sched = env.sched;
+    wf = env.window > 0 ? (uint32_t)env.window : 0;
   } else if (n_slabs > 1 && (uint64_t)rows * f * 4 > NTS_BLOCK_MIN_BYTES &&
              edges / NTS_BLOCK_MIN_REUSE >= rows) {
-    /* rows == 0 (row count unknown to the caller) never engages */
     sched = NTS_AUTO_SCHED;
     wf = NTS_AUTO_WINDOW;
   }
   if (sched < NTS_SCHED_ITEM || sched > NTS_SCHED_XCD) sched = NTS_SCHED_ITEM;
-  const uint32_t unit = elem * nstr; /* floats per lane */
   if (wf == 0) {
     /* default width: the native slab; XCD: the widest full lane group
      * (64, 32 or 16 lanes) that still gives every class a window */
@@ -1406,12 +1269,12 @@ void launch_gather(nts_stream *s, const float *in, float *out, const float *ew,
     const uint32_t tl = (wf + g * unit - 1) / (g * unit);
     if (tl * g < tiles * Gb) { Gb = g; tiles = tl; }
   }
-  uint32_t grid = grid_for(bound_items * n_windows * tiles * Gb,
-                           nts_gather_blocks());
+  uint32_t grid =
+      grid_for(bound_items * n_windows * tiles * Gb, env.gather_blocks);
   if (sched == NTS_SCHED_XCD) {
     /* every class needs a workgroup and a window, its own or an even share
      * of one; otherwise the current order runs */
-    const uint32_t cap8 = nts_gather_blocks() & ~7u;
+    const uint32_t cap8 = env.gather_blocks & ~7u;
     if ((n_windows < 8 && n_windows != 4 && n_windows != 2) || grid < 8 ||
         cap8 < 8) {
       sched = NTS_SCHED_ITEM;
@@ -1420,42 +1283,37 @@ void launch_gather(nts_stream *s, const float *in, float *out, const float *ew,
       grid = min((grid + 7u) & ~7u, cap8);
     }
   }
-  const bool blocked =
-      n_windows > 1 && !(sched == NTS_SCHED_ITEM && wf == slabf);
-  GatherPlan pl;
-  if (blocked) {
-    G = Gb;
-    pl = GatherPlan{(uint32_t)sched, wf, n_windows, tiles};
-  } else {
-    /* exactly the pre-window launch */
-    sched = NTS_SCHED_ITEM;
-    wf = slabf;
-    grid = grid_for(bound_items * n_slabs * G);
-    pl = GatherPlan{NTS_SCHED_ITEM, slabf, n_slabs, 1u};
-  }
-  s->sched_last = sched;
-  s->window_last = (int)wf;
+  if (n_windows > 1 && !(sched == NTS_SCHED_ITEM && wf == slabf))
+    return GatherLaunch{geo.elem, Gb, grid, true,
+                        GatherPlan{(uint32_t)sched, wf, n_windows, tiles}};
+  /* exactly the pre-window launch */
+  return GatherLaunch{
+      geo.elem, geo.G,
+      grid_for(bound_items * n_slabs * geo.G, env.max_blocks), false,
+      GatherPlan{NTS_SCHED_ITEM, slabf, n_slabs, 1u}};
+}
+
+void launch_gather(nts_stream *s, const float *in, float *out, const float *ew,
+                   const uint32_t *nbr, const uint32_t *offset,
+                   uint32_t nbr_start, uint32_t batch, uint32_t edges,
+                   uint32_t f, int with_weight, int tag, uint32_t rows) {
+  if (!batch || !edges || !f) return;
+  ItemsBuf &ib = get_items(s, offset, batch, edges);
+  const GatherLaunch L =
+      plan_gather(f, (uintptr_t)in | (uintptr_t)out, rows, batch, edges,
+                  s->sched_req, s->window_req, gather_env());
+  using Kernel = decltype(&k_gather_spmm<1, false, false>);
+#define NTS_K(E)                                                              \
+  {{k_gather_spmm<E, false, false>, k_gather_spmm<E, false, true>},           \
+   {k_gather_spmm<E, true, false>, k_gather_spmm<E, true, true>}}
+  static const Kernel kernels[3][2][2] = {NTS_K(1), NTS_K(2), NTS_K(4)};
+#undef NTS_K
+  s->sched_last = (int)L.pl.sched;
+  s->window_last = (int)L.pl.wf;
   Tic t(s, tag);
-#define NTS_LAUNCH_B(E, W, B)                                                 \
-  hipLaunchKernelGGL((k_gather_spmm<E, W, B>), dim3(grid), dim3(NTS_BLOCK),   \
-                     0, s->stream, ib.items, ib.counter, nbr, ew, in, out,    \
-                     nbr_start, f, G, pl)
-#define NTS_LAUNCH(E, W)                                                      \
-  do {                                                                        \
-    if (blocked) NTS_LAUNCH_B(E, W, true);                                    \
-    else NTS_LAUNCH_B(E, W, false);                                           \
-  } while (0)
-  if (with_weight) {
-    if (elem == 4) NTS_LAUNCH(4, true);
-    else if (elem == 2) NTS_LAUNCH(2, true);
-    else NTS_LAUNCH(1, true);
-  } else {
-    if (elem == 4) NTS_LAUNCH(4, false);
-    else if (elem == 2) NTS_LAUNCH(2, false);
-    else NTS_LAUNCH(1, false);
-  }
-#undef NTS_LAUNCH
-#undef NTS_LAUNCH_B
+  hipLaunchKernelGGL(kernels[L.elem >> 1][with_weight != 0][L.blocked],
+                     dim3(L.grid), dim3(NTS_BLOCK), 0, s->stream, ib.items,
+                     ib.counter, nbr, ew, in, out, nbr_start, f, L.G, L.pl);
   dbg_sync(s, "k_gather_spmm");
 }
 }  // namespace
@@ -1599,6 +1457,23 @@ void nts_gather_schedule_last(nts_stream *s, int *schedule,
   if (window_floats) *window_floats = s->window_last;
 }
 
+void nts_gather_plan(nts_vid feature_size, unsigned alignment_bytes,
+                     nts_vid rows, nts_vid batch_size, nts_vid edges,
+                     int schedule_req, int window_req, int *schedule,
+                     int *window_floats, int *lane_group, int *vector_width,
+                     int *grid, int *blocked) {
+  GatherLaunch L{};
+  if (batch_size && edges && feature_size) /* else nothing is launched */
+    L = plan_gather(feature_size, alignment_bytes, rows, batch_size, edges,
+                    schedule_req, window_req, gather_env());
+  if (schedule) *schedule = (int)L.pl.sched;
+  if (window_floats) *window_floats = (int)L.pl.wf;
+  if (lane_group) *lane_group = (int)L.G;
+  if (vector_width) *vector_width = L.elem;
+  if (grid) *grid = (int)L.grid;
+  if (blocked) *blocked = L.blocked ? 1 : 0;
+}
+
 void nts_items_cache_clear(nts_stream *s) {
   NTS_CHECK(hipStreamSynchronize(s->stream));
   for (auto &slot : s->items_scratch) slot.valid = false;
@@ -1680,6 +1555,23 @@ static uint32_t read_edge_count(nts_stream *s, const nts_vid *column_offset,
   return last;
 }
 
+/* Prologue of the item-driven edge entry points: the edge count (one host
+ * sync), the work items and the grid.  ib == nullptr: nothing to do. */
+struct EdgeItems {
+  ItemsBuf *ib = nullptr;
+  uint32_t edges = 0, grid = 0;
+};
+static EdgeItems edge_items(nts_stream *s, const nts_vid *offset,
+                            nts_vid batch) {
+  EdgeItems p;
+  if (!batch) return p;
+  p.edges = read_edge_count(s, offset, batch);
+  if (!p.edges) return p;
+  p.ib = &get_items(s, offset, batch, p.edges);
+  p.grid = items_grid(batch, p.edges);
+  return p;
+}
+
 static float *get_sums(nts_stream *s, uint64_t n) {
   if (s->sums_cap < n) {
     NTS_CHECK(hipStreamSynchronize(s->stream));
@@ -1696,61 +1588,47 @@ static void launch_edge_op(nts_stream *s, EdgeOp op, float *message,
                            const nts_vid *column_offset,
                            const nts_vid *mirror_index, nts_vid batch,
                            nts_vid f) {
-  if (!batch || !f) return;
-  const uint32_t edges = read_edge_count(s, column_offset, batch);
-  if (!edges) return;
-  ItemsBuf &ib = get_items(s, column_offset, batch, edges);
+  if (!f) return;
+  const EdgeItems p = edge_items(s, column_offset, batch);
+  if (!p.ib) return;
   Tic t(s, NTS_KTAG_EDGE);
-  const uint32_t grid = grid_for(((uint64_t)batch + edges / NTS_SPLIT) * 64);
-#define NTS_ELAUNCH(OP)                                                       \
-  hipLaunchKernelGGL((k_edge_items<OP>), dim3(grid), dim3(NTS_BLOCK), 0,      \
-                     s->stream, ib.items, ib.counter, message, vfeat,         \
-                     row_indices, mirror_index, f)
-  switch (op) {
-    case E_SCATTER_SRC: NTS_ELAUNCH(E_SCATTER_SRC); break;
-    case E_GATHER_SRC: NTS_ELAUNCH(E_GATHER_SRC); break;
-    case E_SCATTER_DST: NTS_ELAUNCH(E_SCATTER_DST); break;
-    case E_GATHER_DST: NTS_ELAUNCH(E_GATHER_DST); break;
-    case E_SCATTER_GRAD: NTS_ELAUNCH(E_SCATTER_GRAD); break;
-  }
-#undef NTS_ELAUNCH
+  static constexpr decltype(&k_edge_items<E_SCATTER_SRC>) kernels[] = {
+      k_edge_items<E_SCATTER_SRC>, k_edge_items<E_GATHER_SRC>,
+      k_edge_items<E_SCATTER_DST>, k_edge_items<E_GATHER_DST>,
+      k_edge_items<E_SCATTER_GRAD>}; /* in EdgeOp order */
+  hipLaunchKernelGGL(kernels[op], dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream,
+                     p.ib->items, p.ib->counter, message, vfeat, row_indices,
+                     mirror_index, f);
   dbg_sync(s, "k_edge_items");
 }
 
-static void launch_edge_softmax(nts_stream *s, bool backward, float *out,
-                                const float *in, const float *cached,
-                                const nts_vid *column_offset, nts_vid batch,
-                                nts_vid f, float *out2 = nullptr,
-                                const nts_vid *pos2 = nullptr,
-                                const float *lrelu_in = nullptr,
-                                float slope = 0.f,
-                                float *dst_accum = nullptr) {
+/* returns the edge count it read (0: nothing ran) */
+static uint32_t launch_edge_softmax(nts_stream *s, bool backward, float *out,
+                                    const float *in, const float *cached,
+                                    const nts_vid *column_offset,
+                                    nts_vid batch, nts_vid f,
+                                    float *out2 = nullptr,
+                                    const nts_vid *pos2 = nullptr,
+                                    const float *lrelu_in = nullptr,
+                                    float slope = 0.f,
+                                    float *dst_accum = nullptr) {
   if (dst_accum && f != 1) abort(); /* per-dst sum emission is f==1 only */
-  if (!batch || !f) return;
-  const uint32_t edges = read_edge_count(s, column_offset, batch);
-  if (!edges) return;
-  ItemsBuf &ib = get_items(s, column_offset, batch, edges);
+  if (!f) return 0;
+  const EdgeItems p = edge_items(s, column_offset, batch);
+  if (!p.ib) return 0;
   float *sums = get_sums(s, (uint64_t)batch * f);
-  const uint32_t grid = grid_for(((uint64_t)batch + edges / NTS_SPLIT) * 64);
   Tic t(s, NTS_KTAG_EDGE);
-  if (backward) {
-    hipLaunchKernelGGL((k_edge_softmax_sum<true>), dim3(grid), dim3(NTS_BLOCK),
-                       0, s->stream, ib.items, ib.counter, out, in, cached,
-                       sums, f);
-    hipLaunchKernelGGL((k_edge_softmax_norm<true>), dim3(grid),
-                       dim3(NTS_BLOCK), 0, s->stream, ib.items, ib.counter,
-                       out, cached, sums, out2, pos2, lrelu_in, slope,
-                       dst_accum, f);
-  } else {
-    hipLaunchKernelGGL((k_edge_softmax_sum<false>), dim3(grid),
-                       dim3(NTS_BLOCK), 0, s->stream, ib.items, ib.counter,
-                       out, in, cached, sums, f);
-    hipLaunchKernelGGL((k_edge_softmax_norm<false>), dim3(grid),
-                       dim3(NTS_BLOCK), 0, s->stream, ib.items, ib.counter,
-                       out, cached, sums, out2, pos2, nullptr, 0.f,
-                       dst_accum, f);
-  }
+  hipLaunchKernelGGL(
+      backward ? k_edge_softmax_sum<true> : k_edge_softmax_sum<false>,
+      dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+      p.ib->counter, out, in, cached, sums, f);
+  hipLaunchKernelGGL(
+      backward ? k_edge_softmax_norm<true> : k_edge_softmax_norm<false>,
+      dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+      p.ib->counter, out, cached, sums, out2, pos2, lrelu_in, slope,
+      dst_accum, f);
   dbg_sync(s, "k_edge_softmax");
+  return p.edges;
 }
 
 void nts_scatter_src_mirror_to_msg(nts_stream *s, float *message,
@@ -1796,40 +1674,13 @@ void nts_edge_dot(nts_stream *s, float *out, const float *dst_rows,
                   const float *src_rows, const nts_vid *row_indices,
                   const nts_vid *column_offset, nts_vid src_start,
                   nts_vid batch_size, nts_vid feature_size) {
-  if (!batch_size || !feature_size) return;
-  const uint32_t edges = read_edge_count(s, column_offset, batch_size);
-  if (!edges) return;
-  ItemsBuf &ib = get_items(s, column_offset, batch_size, edges);
+  if (!feature_size) return;
+  const EdgeItems p = edge_items(s, column_offset, batch_size);
+  if (!p.ib) return;
   Tic t(s, NTS_KTAG_EDGE);
-  const uint32_t grid =
-      grid_for(((uint64_t)batch_size + edges / NTS_SPLIT) * 64);
-  /* measured on config #5 (f=128): wave-per-edge 34.3 ms/step beats
-   * lane-per-edge 42.4 (scattered rows thrash L1); the sub-group form
-   * (GS lanes per edge) also measured worse at f=128 (~+6 ms/step).
-   * NTS_EDGE_DOT: 1 = wave-per-edge (default), 2 = lane-per-edge,
-   * 3 = sub-group — both alternatives kept as recorded negative results. */
-  static const uint32_t variant = env_u32("NTS_EDGE_DOT", 1);
-  if (variant == 1) {
-    hipLaunchKernelGGL(k_edge_dot, dim3(grid), dim3(NTS_BLOCK), 0, s->stream,
-                       ib.items, ib.counter, out, dst_rows, src_rows,
-                       row_indices, src_start, feature_size);
-  } else if (variant == 2) {
-    hipLaunchKernelGGL(k_edge_dot_lpe, dim3(grid), dim3(NTS_BLOCK), 0,
-                       s->stream, ib.items, ib.counter, out, dst_rows,
-                       src_rows, row_indices, src_start, feature_size);
-  } else if (feature_size <= 32) {
-    hipLaunchKernelGGL(k_edge_dot_sg<16>, dim3(grid), dim3(NTS_BLOCK), 0,
-                       s->stream, ib.items, ib.counter, out, dst_rows,
-                       src_rows, row_indices, src_start, feature_size);
-  } else if (feature_size <= 256) {
-    hipLaunchKernelGGL(k_edge_dot_sg<32>, dim3(grid), dim3(NTS_BLOCK), 0,
-                       s->stream, ib.items, ib.counter, out, dst_rows,
-                       src_rows, row_indices, src_start, feature_size);
-  } else {
-    hipLaunchKernelGGL(k_edge_dot, dim3(grid), dim3(NTS_BLOCK), 0, s->stream,
-                       ib.items, ib.counter, out, dst_rows, src_rows,
-                       row_indices, src_start, feature_size);
-  }
+  hipLaunchKernelGGL(k_edge_dot, dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream,
+                     p.ib->items, p.ib->counter, out, dst_rows, src_rows,
+                     row_indices, src_start, feature_size);
   dbg_sync(s, "k_edge_dot");
 }
 
@@ -1850,17 +1701,9 @@ void nts_edge_softmax_forward(nts_stream *s, float *msg_output,
                               const nts_vid *column_offset, nts_vid batch_size,
                               nts_vid feature_size) {
   (void)row_indices;
-  launch_edge_softmax(s, false, msg_output, msg_input, nullptr, column_offset,
-                      batch_size, feature_size);
-  /* cache = output for backward (reference caches at
-   * ntsCUDADistKernel.cuh:210) */
-  if (msg_cached && msg_cached != msg_output && batch_size && feature_size) {
-    const uint32_t edges = read_edge_count(s, column_offset, batch_size);
-    const uint64_t n = (uint64_t)edges * feature_size;
-    if (n)
-      hipLaunchKernelGGL(k_copy, dim3(grid_for(n)), dim3(NTS_BLOCK), 0,
-                         s->stream, msg_cached, msg_output, n);
-  }
+  nts_edge_softmax_forward_dual(s, msg_output, nullptr, nullptr, msg_input,
+                                msg_cached, column_offset, batch_size,
+                                feature_size);
 }
 
 void nts_edge_softmax_backward(nts_stream *s, float *msg_input_grad,
@@ -1882,15 +1725,16 @@ void nts_edge_softmax_forward_dual(nts_stream *s, float *msg_output,
                                    const float *msg_input, float *msg_cached,
                                    const nts_vid *column_offset,
                                    nts_vid batch_size, nts_vid feature_size) {
-  launch_edge_softmax(s, false, msg_output, msg_input, nullptr, column_offset,
-                      batch_size, feature_size, msg_output_perm, perm_pos);
-  if (msg_cached && msg_cached != msg_output && batch_size && feature_size) {
-    const uint32_t edges = read_edge_count(s, column_offset, batch_size);
-    const uint64_t n = (uint64_t)edges * feature_size;
-    if (n)
-      hipLaunchKernelGGL(k_copy, dim3(grid_for(n)), dim3(NTS_BLOCK), 0,
-                         s->stream, msg_cached, msg_output, n);
-  }
+  const uint32_t edges =
+      launch_edge_softmax(s, false, msg_output, msg_input, nullptr,
+                          column_offset, batch_size, feature_size,
+                          msg_output_perm, perm_pos);
+  /* cache = output for backward (reference caches at
+   * ntsCUDADistKernel.cuh:210) */
+  const uint64_t n = (uint64_t)edges * feature_size;
+  if (n && msg_cached && msg_cached != msg_output)
+    hipLaunchKernelGGL(k_copy, dim3(grid_for(n)), dim3(NTS_BLOCK), 0,
+                       s->stream, msg_cached, msg_output, n);
 }
 
 void nts_edge_softmax_backward_fused(nts_stream *s, float *msg_input_grad,
@@ -1910,15 +1754,11 @@ void nts_edge_softmax_backward_fused(nts_stream *s, float *msg_input_grad,
 
 void nts_weight_sum(nts_stream *s, float *out, const float *weights,
                     const nts_vid *offset, nts_vid batch_size) {
-  if (!batch_size) return;
-  const uint32_t edges = read_edge_count(s, offset, batch_size);
-  if (!edges) return;
-  ItemsBuf &ib = get_items(s, offset, batch_size, edges);
-  const uint32_t grid =
-      grid_for(((uint64_t)batch_size + edges / NTS_SPLIT) * 64);
+  const EdgeItems p = edge_items(s, offset, batch_size);
+  if (!p.ib) return;
   Tic t(s, NTS_KTAG_EDGE);
-  hipLaunchKernelGGL(k_weight_sum, dim3(grid), dim3(NTS_BLOCK), 0, s->stream,
-                     ib.items, ib.counter, out, weights);
+  hipLaunchKernelGGL(k_weight_sum, dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream,
+                     p.ib->items, p.ib->counter, out, weights);
   dbg_sync(s, "k_weight_sum");
 }
 
@@ -1930,13 +1770,11 @@ void nts_edge_attention_forward(nts_stream *s, float *softmax_out,
                                 const nts_vid *mirror_index, float slope,
                                 const nts_vid *column_offset,
                                 nts_vid batch_size) {
-  if (!batch_size) return;
-  const uint32_t edges = read_edge_count(s, column_offset, batch_size);
-  if (!edges) return;
-  ItemsBuf &ib = get_items(s, column_offset, batch_size, edges);
+  const EdgeItems p = edge_items(s, column_offset, batch_size);
+  if (!p.ib) return;
+  const ItemsBuf &ib = *p.ib;
+  const uint32_t grid = p.grid;
   float *sums = get_sums(s, batch_size);
-  const uint32_t grid =
-      grid_for(((uint64_t)batch_size + edges / NTS_SPLIT) * 64);
   Tic t(s, NTS_KTAG_EDGE);
   hipLaunchKernelGGL(k_edge_att_sum, dim3(grid), dim3(NTS_BLOCK), 0,
                      s->stream, ib.items, ib.counter, softmax_out, m_sum_out,
@@ -1959,17 +1797,10 @@ int nts_gather_by_src_from_dst_dot(nts_stream *s, const float *input,
                                    const nts_vid *dot_pos) {
   const uint32_t f = feature_size;
   if (!batch_size || !edges || !f) return 1;
-  const uintptr_t a =
-      (uintptr_t)input | (uintptr_t)output | (uintptr_t)dot_vec;
-  int elem;
-  if (f % 4 == 0 && a % 16 == 0) elem = 4;
-  else if (f % 2 == 0 && a % 8 == 0) elem = 2;
-  else elem = 1;
-  uint32_t G = 64;
-  if (elem > 1) {
-    const uint32_t need = (f + elem - 1) / elem;
-    while (G / 2 >= need && G > 16) G /= 2;
-  }
+  const GatherGeom geo = gather_geometry(
+      f, (uintptr_t)input | (uintptr_t)output | (uintptr_t)dot_vec);
+  const int elem = geo.elem;
+  const uint32_t G = geo.G;
   if (elem == 1 || f > G * (uint32_t)elem) {
     /* ragged or multi-slab width: unfused fallback — plain CSR gather; the
      * caller must compute the dot with nts_edge_dot */
@@ -1981,32 +1812,23 @@ int nts_gather_by_src_from_dst_dot(nts_stream *s, const float *input,
   ItemsBuf &ib = get_items(s, row_offset, batch_size, edges);
   const uint64_t bound_groups = (uint64_t)batch_size + edges / NTS_SPLIT + 1;
   const uint32_t grid = grid_for(bound_groups * G);
-  /* NTS_GATHER_DOT: 1 = batched LDS-transpose reduction (default),
-   * 2 = per-edge shuffle chains (kept selectable for A/B). */
-  static const uint32_t variant = env_u32("NTS_GATHER_DOT", 1);
   Tic t(s, NTS_KTAG_BWD);
-#define NTS_DOT_LAUNCH(K, E)                                                  \
-  hipLaunchKernelGGL((K<E>), dim3(grid), dim3(NTS_BLOCK), 0, s->stream,       \
-                     ib.items, ib.counter, column_indices, weight_backward,   \
-                     input, output, dst_start, dot_vec, dot_out, dot_pos, f,  \
-                     G)
-  if (variant == 2) {
-    if (elem == 4) NTS_DOT_LAUNCH(k_gather_spmm_dot, 4);
-    else NTS_DOT_LAUNCH(k_gather_spmm_dot, 2);
-  } else {
-    if (elem == 4) NTS_DOT_LAUNCH(k_gather_spmm_dot_lds, 4);
-    else NTS_DOT_LAUNCH(k_gather_spmm_dot_lds, 2);
-  }
-#undef NTS_DOT_LAUNCH
-  dbg_sync(s, "k_gather_spmm_dot");
+  hipLaunchKernelGGL(
+      elem == 4 ? k_gather_spmm_dot_lds<4> : k_gather_spmm_dot_lds<2>,
+      dim3(grid), dim3(NTS_BLOCK), 0, s->stream, ib.items, ib.counter,
+      column_indices, weight_backward, input, output, dst_start, dot_vec,
+      dot_out, dot_pos, f, G);
+  dbg_sync(s, "k_gather_spmm_dot_lds");
   return 1;
 }
 
-void nts_sample_reservoir(nts_stream *s, const nts_vid *column_offset,
-                          const nts_vid *row_indices, const nts_vid *dst_list,
-                          nts_vid n_dst, nts_vid fanout,
-                          unsigned long long seed, nts_vid *out_src,
-                          nts_vid *out_cnt) {
+static void launch_sampler(nts_stream *s,
+                           decltype(&k_sample_reservoir<false>) kernel,
+                           const nts_vid *column_offset,
+                           const nts_vid *row_indices, const nts_vid *dst_list,
+                           nts_vid n_dst, nts_vid fanout,
+                           unsigned long long seed, nts_vid *out_src,
+                           nts_vid *out_cnt) {
   if (!n_dst || !fanout) return;
   if (fanout > NTS_MAX_FANOUT) {
     fprintf(stderr, "nts_sample_reservoir: fanout %u > %u\n", fanout,
@@ -2014,11 +1836,19 @@ void nts_sample_reservoir(nts_stream *s, const nts_vid *column_offset,
     abort();
   }
   Tic t(s, NTS_KTAG_ITEMS);
-  hipLaunchKernelGGL(k_sample_reservoir<false>,
-                     dim3(grid_for((uint64_t)n_dst * 64)), dim3(NTS_BLOCK), 0,
-                     s->stream, column_offset, row_indices, dst_list, n_dst,
-                     fanout, seed, out_src, out_cnt);
+  hipLaunchKernelGGL(kernel, dim3(grid_for((uint64_t)n_dst * 64)),
+                     dim3(NTS_BLOCK), 0, s->stream, column_offset, row_indices,
+                     dst_list, n_dst, fanout, seed, out_src, out_cnt);
   dbg_sync(s, "k_sample_reservoir");
+}
+
+void nts_sample_reservoir(nts_stream *s, const nts_vid *column_offset,
+                          const nts_vid *row_indices, const nts_vid *dst_list,
+                          nts_vid n_dst, nts_vid fanout,
+                          unsigned long long seed, nts_vid *out_src,
+                          nts_vid *out_cnt) {
+  launch_sampler(s, k_sample_reservoir<false>, column_offset, row_indices,
+                 dst_list, n_dst, fanout, seed, out_src, out_cnt);
 }
 
 /* TEST-ONLY: same sampler with the 32-bit threshold search skipped, so the
@@ -2029,13 +1859,8 @@ void nts_sample_reservoir_dbg_fallback(
     nts_stream *s, const nts_vid *column_offset, const nts_vid *row_indices,
     const nts_vid *dst_list, nts_vid n_dst, nts_vid fanout,
     unsigned long long seed, nts_vid *out_src, nts_vid *out_cnt) {
-  if (!n_dst || !fanout) return;
-  if (fanout > NTS_MAX_FANOUT) abort();
-  hipLaunchKernelGGL(k_sample_reservoir<true>,
-                     dim3(grid_for((uint64_t)n_dst * 64)), dim3(NTS_BLOCK), 0,
-                     s->stream, column_offset, row_indices, dst_list, n_dst,
-                     fanout, seed, out_src, out_cnt);
-  dbg_sync(s, "k_sample_reservoir_dbg_fallback");
+  launch_sampler(s, k_sample_reservoir<true>, column_offset, row_indices,
+                 dst_list, n_dst, fanout, seed, out_src, out_cnt);
 }
 
 void nts_permute_f32(nts_stream *s, float *out, const float *in,

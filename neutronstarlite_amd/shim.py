@@ -75,6 +75,7 @@ def lib():
     l.nts_items_cache_clear.argtypes = [_vp]
     l.nts_gather_schedule.argtypes = [_vp, _i32, _i32]
     l.nts_gather_schedule_last.argtypes = [_vp, _vp, _vp]
+    l.nts_gather_plan.argtypes = [_u32] * 5 + [_i32] * 2 + [_vp] * 6
     l.nts_deserialize_to_gpu.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _i32]
     l.nts_aggregate_comm_result.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _i32]
     l.nts_gather_rows.argtypes = [_vp, _vp, _vp, _vp, _u32, _u32, _u32]
@@ -108,6 +109,20 @@ def lib():
     l.nts_build_arch.restype = _c.c_char_p
     _lib = l
     return l
+
+
+def gather_plan(f, alignment, rows, batch, edges, schedule=0, window=0):
+    """The launch decision a gather of this shape would take (no device
+    access): dict of schedule, window, lane_group, vector_width, grid,
+    blocked.  (schedule, window) is a request as for Stream.gather_schedule."""
+    names = ("schedule", "window", "lane_group", "vector_width", "grid",
+             "blocked")
+    out = [_i32(0) for _ in names]
+    lib().nts_gather_plan(f, alignment, rows, batch, edges, schedule, window,
+                          *[_c.byref(o) for o in out])
+    plan = {n: o.value for n, o in zip(names, out)}
+    plan["blocked"] = bool(plan["blocked"])
+    return plan
 
 
 _live_streams = weakref.WeakSet()

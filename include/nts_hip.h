@@ -82,8 +82,12 @@ void nts_memcpy_d2h(nts_stream *s, void *h, const void *d, long bytes, int sync)
  * There is no <=512-feature special case: one kernel handles any
  * feature_size by slab decomposition, and power-law columns are split into
  * bounded work items on device (see nts_hip.hip).  with_weight=0 replaces the
- * _without_weight twins; tensor (per-edge-tensor) weights are out of scope
- * for this path, as in the exercised configs. */
+ * _without_weight twins.
+ * LIMITATION (tensor_weight): an edge weight is ONE fp32 scalar per edge.  The
+ * reference's tensor_weight form, a weight row of feature_size values per
+ * edge multiplied element by element, has no entry point here: none of the
+ * exercised configs uses it, and a caller that needs it must materialize the
+ * per-edge messages with the edge-wise kernels below instead. */
 void nts_gather_by_dst_from_src(nts_stream *s,
     const float *input, float *output, const float *weight_forward,
     const nts_vid *row_indices, const nts_vid *column_offset,
@@ -99,7 +103,35 @@ void nts_gather_by_src_from_dst(nts_stream *s,
     nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
     nts_vid edges, nts_vid batch_size, nts_vid feature_size, int with_weight);
 
-/* Column schedule of the two gather entry points.  A gather task is (work
+/* ---- bfloat16 feature rows (additive, not in the reference ABI) ----
+ * The same two gathers over an input matrix stored as bfloat16: row-major
+ * [rows, feature_size] raw uint16_t, row pitch 2*feature_size bytes, 2-byte
+ * aligned at least.  Weights, accumulation and output stay fp32, and the
+ * output keeps the += contract.  A bf16 value is widened exactly (its bits
+ * are the high half of the fp32), and each output element is the same fp32
+ * fmaf chain over the item's edges in edge order, so for a vertex that is
+ * not split into several work items the result is bit-identical to the fp32
+ * entry run on the widened values.  What halves is the dominant term of the
+ * traffic, the gathered row: about edges*(2f+8) + rows*8f bytes against
+ * edges*(4f+8) + rows*8f.  Lane widths: 8 elements (one 16-byte load;
+ * feature_size % 8 == 0, input and output 16-byte aligned), 4 (8-byte;
+ * % 4, 8-byte aligned), 2 (4-byte; % 2, 4-byte aligned), else 4 strided
+ * 2-byte loads per lane.  Schedules, windows (in columns), NTS_SPLIT, the
+ * grid caps, the item cache and the NTS_KTAG_FWD / NTS_KTAG_BWD timing tags
+ * are shared with the fp32 entries.  bf16 weights or output, the ring, the
+ * row pack entries and the fused gather-dot are fp32 only. */
+void nts_gather_by_dst_from_src_bf16(nts_stream *s,
+    const uint16_t *input, float *output, const float *weight_forward,
+    const nts_vid *row_indices, const nts_vid *column_offset,
+    nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
+    nts_vid edges, nts_vid batch_size, nts_vid feature_size, int with_weight);
+void nts_gather_by_src_from_dst_bf16(nts_stream *s,
+    const uint16_t *input, float *output, const float *weight_backward,
+    const nts_vid *row_offset, const nts_vid *column_indices,
+    nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
+    nts_vid edges, nts_vid batch_size, nts_vid feature_size, int with_weight);
+
+/* Column schedule of the gather entry points, fp32 and bf16.  A gather task is (work
  * item, column window of `window_floats` floats); the schedule only changes
  * which task runs when, so for a vertex that is not split into several work
  * items the result is bit-identical under every schedule. */
@@ -143,6 +175,14 @@ void nts_gather_schedule_last(nts_stream *s, int *schedule, int *window_floats);
  * width per lane (4, 2 or 1 dwords), the grid in workgroups, and whether the
  * column-blocked kernel instantiation runs.  Any out pointer may be NULL. */
 void nts_gather_plan(nts_vid feature_size, unsigned alignment_bytes,
+    nts_vid rows, nts_vid batch_size, nts_vid edges, int schedule_req,
+    int window_req, int *schedule, int *window_floats, int *lane_group,
+    int *vector_width, int *grid, int *blocked);
+
+/* The same for the bf16 entry points (additive): vector_width is in
+ * elements per lane (8, 4, 2 or 1), windows are in columns, and "larger than
+ * the Infinity Cache" counts the matrix at 2 bytes per element. */
+void nts_gather_plan_bf16(nts_vid feature_size, unsigned alignment_bytes,
     nts_vid rows, nts_vid batch_size, nts_vid edges, int schedule_req,
     int window_req, int *schedule, int *window_floats, int *lane_group,
     int *vector_width, int *grid, int *blocked);

@@ -11,7 +11,10 @@
  *    64-lane wavefront group reads a source row slab per edge as wide
  *    vector loads (dwordx4 / dwordx2 / 4x strided dword chosen from the
  *    feature width and pointer alignment) and accumulates in REGISTERS —
- *    no LDS staging, no per-element shared-memory atomics.
+ *    no LDS staging, no per-element shared-memory atomics.  The gathered
+ *    rows may be stored as bfloat16 (half the bytes per edge): the same
+ *    kernel, loading 16 / 8 / 4 bytes per lane and widening in registers;
+ *    weights, accumulators and output stay fp32.
  *  - Power-law load balance: columns are decomposed on device into bounded
  *    work items of <= NTS_SPLIT consecutive edges of one vertex (rebuilt
  *    per call into a stream scratch buffer — two launches, ~0.05% of a
@@ -206,18 +209,25 @@ __device__ __forceinline__ void wave_min(unsigned long long &best,
 template <int N>
 using fvec = float __attribute__((ext_vector_type(N)));  /* dwordxN access */
 
-/* o[0..nv) += acc: plain read-modify-write for an exclusive vertex (one
- * vector access when the lane is full), atomicAdd for a split one */
-template <int ELEM>
+/* o[0..nv) += acc: plain read-modify-write for an exclusive vertex (vector
+ * accesses of OV floats when the lane is full: one, or ELEM/OV where o is
+ * only known to be aligned to OV floats), atomicAdd for a split one */
+template <int ELEM, int OV = ELEM>
 __device__ __forceinline__ void store_acc(float *o, const float (&acc)[ELEM],
                                           int nv, bool shared) {
+  static_assert(ELEM % OV == 0, "whole vector accesses");
   if (shared) {
     for (int j = 0; j < nv; ++j) atomicAdd(&o[j], acc[j]);
   } else if (nv == ELEM) {
-    fvec<ELEM> y = *reinterpret_cast<fvec<ELEM> *>(o);
+    fvec<OV> y[ELEM / OV];
 #pragma unroll
-    for (int j = 0; j < ELEM; ++j) y[j] += acc[j];
-    *reinterpret_cast<fvec<ELEM> *>(o) = y;
+    for (int c = 0; c < ELEM / OV; ++c)
+      y[c] = reinterpret_cast<fvec<OV> *>(o)[c];
+#pragma unroll
+    for (int j = 0; j < ELEM; ++j) y[j / OV][j % OV] += acc[j];
+#pragma unroll
+    for (int c = 0; c < ELEM / OV; ++c)
+      reinterpret_cast<fvec<OV> *>(o)[c] = y[c];
   } else {
     for (int j = 0; j < nv; ++j) o[j] += acc[j];
   }
@@ -345,49 +355,89 @@ __device__ __forceinline__ Task decode_task(const GatherPlan &pl,
   }
 }
 
+/* Row element types of the gathered matrix: fp32, or bfloat16 held as raw
+ * uint16_t.  bits << 16 is the exact fp32 of a bf16 (normals, subnormals,
+ * zeros, infinities, NaNs), so a bf16 gather runs the very fmaf chain of the
+ * fp32 gather on the upcast values. */
+__device__ __forceinline__ float to_f32(float x) { return x; }
+__device__ __forceinline__ float to_f32(uint16_t bits) {
+  return __uint_as_float((uint32_t)bits << 16);
+}
+
+/* one lane's ELEM consecutive row elements as fp32, in one access: dwordxELEM
+ * for fp32 rows; ELEM/2 dwords (16, 8 or 4 bytes) for bf16 rows, unpacked in
+ * registers — element 2i is the low half of dword i, 2i+1 the high half */
+template <int ELEM>
+__device__ __forceinline__ void load_lane(const float *p, float (&x)[ELEM]) {
+  const fvec<ELEM> v = *reinterpret_cast<const fvec<ELEM> *>(p);
+#pragma unroll
+  for (int j = 0; j < ELEM; ++j) x[j] = v[j];
+}
+template <int ELEM>
+__device__ __forceinline__ void load_lane(const uint16_t *p,
+                                          float (&x)[ELEM]) {
+  static_assert(ELEM % 2 == 0, "bf16 lanes load whole dwords");
+  uint32_t d[ELEM / 2];
+  if constexpr (ELEM == 2) {
+    d[0] = *reinterpret_cast<const uint32_t *>(p);
+  } else {
+    using uvec = uint32_t __attribute__((ext_vector_type(ELEM / 2)));
+    const uvec v = *reinterpret_cast<const uvec *>(p);
+#pragma unroll
+    for (int j = 0; j < ELEM / 2; ++j) d[j] = v[j];
+  }
+#pragma unroll
+  for (int j = 0; j < ELEM / 2; ++j) {
+    x[2 * j] = __uint_as_float(d[j] << 16);
+    x[2 * j + 1] = __uint_as_float(d[j] & 0xffff0000u);
+  }
+}
+
 /* the gathered side of one launch */
+template <typename T>
 struct GatherSrc {
   const uint32_t *nbr;
   const float *ew;
-  const float *in;
+  const T *in;
   uint32_t nbr_start, f;
 };
 
 /* acc += w[k] * row k for K full vector lanes; fmaf order edge-major,
  * element-minor, all K loads issued before the first fmaf */
-template <int ELEM, int K>
+template <int ELEM, int K, typename T>
 __device__ __forceinline__ void fma_vec(float (&acc)[ELEM],
-                                        const float *const (&p)[K],
+                                        const T *const (&p)[K],
                                         const float (&wv)[K]) {
-  fvec<ELEM> x[K];
+  float x[K][ELEM];
 #pragma unroll
-  for (int k = 0; k < K; ++k)
-    x[k] = *reinterpret_cast<const fvec<ELEM> *>(p[k]);
+  for (int k = 0; k < K; ++k) load_lane<ELEM>(p[k], x[k]);
 #pragma unroll
   for (int k = 0; k < K; ++k)
 #pragma unroll
     for (int j = 0; j < ELEM; ++j) acc[j] = fmaf(wv[k], x[k][j], acc[j]);
 }
-/* strided dword twin: element j at p[k][j*G], live while col + j*G < fend */
-template <int NSTR, int K>
+/* strided twin (one dword, or one 2-byte bf16, per access): element j at
+ * p[k][j*G], live while col + j*G < fend */
+template <int NSTR, int K, typename T>
 __device__ __forceinline__ void fma_strided(float (&acc)[NSTR],
-                                            const float *const (&p)[K],
+                                            const T *const (&p)[K],
                                             const float (&wv)[K], uint32_t G,
                                             uint32_t col, uint32_t fend) {
 #pragma unroll
   for (int k = 0; k < K; ++k)
 #pragma unroll
     for (int j = 0; j < NSTR; ++j)
-      if (col + j * G < fend) acc[j] = fmaf(wv[k], p[k][j * G], acc[j]);
+      if (col + j * G < fend)
+        acc[j] = fmaf(wv[k], to_f32(p[k][j * G]), acc[j]);
 }
 
 /* K consecutive edges from e on, this lane's columns from col on */
-template <int ELEM, bool WITH_W, int K, int N>
+template <int ELEM, bool WITH_W, int K, int N, typename T>
 __device__ __forceinline__ void accum_edges(float (&acc)[N],
-                                            const GatherSrc &g, uint32_t e,
+                                            const GatherSrc<T> &g, uint32_t e,
                                             uint32_t col, uint32_t G,
                                             uint32_t fend) {
-  const float *p[K];
+  const T *p[K];
   float wv[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
@@ -401,8 +451,9 @@ __device__ __forceinline__ void accum_edges(float (&acc)[N],
 /* one item's edges for a full lane: 4 at a time — 4 independent row loads
  * in flight per wave (one dependent load per iteration leaves HBM latency
  * exposed) — then the tail one by one */
-template <int ELEM, bool WITH_W, int N>
-__device__ __forceinline__ void accum_item(float (&acc)[N], const GatherSrc &g,
+template <int ELEM, bool WITH_W, int N, typename T>
+__device__ __forceinline__ void accum_item(float (&acc)[N],
+                                           const GatherSrc<T> &g,
                                            const Item &im, uint32_t col,
                                            uint32_t G, uint32_t fend) {
   uint32_t e = im.e0;
@@ -417,22 +468,26 @@ __device__ __forceinline__ void accum_item(float (&acc)[N], const GatherSrc &g,
 /* one (work item, feature slab): loops the item's edges, vector-loads */
 /* the neighbor row slab coalesced, fma-accumulates in registers, then */
 /* stores once (RMW for exclusive vertices, atomicAdd for split hubs). */
-/* ELEM = vector width per lane: 4 (dwordx4), 2 (dwordx2), or 1 with   */
-/* NSTR=4 strided dwords (handles any f and any 4-byte alignment).     */
+/* T = row element type of `in`: float, or uint16_t for bfloat16 rows  */
+/* (weights, accumulators and `out` are fp32 either way).              */
+/* ELEM = elements per lane.  fp32: 4 (dwordx4), 2 (dwordx2), or 1     */
+/* with NSTR=4 strided dwords (any f, any 4-byte alignment).  bf16: 8  */
+/* (16-byte load), 4 (8-byte), 2 (4-byte), or 1 with NSTR=4 strided    */
+/* 2-byte loads (any f, any 2-byte alignment).                         */
 /* Forward CSC:  nbr = row_indices   (global src),  out rows = dst.    */
 /* Backward CSR: nbr = column_indices (global dst), out rows = src.    */
 /* ------------------------------------------------------------------ */
-template <int ELEM, bool WITH_W, bool BLOCKED>
+template <typename T, int ELEM, bool WITH_W, bool BLOCKED>
 __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm(
     const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
     const uint32_t *__restrict__ nbr, const float *__restrict__ ew,
-    const float *__restrict__ in, float *__restrict__ out, uint32_t nbr_start,
+    const T *__restrict__ in, float *__restrict__ out, uint32_t nbr_start,
     uint32_t f, uint32_t G, GatherPlan pl) {
   constexpr int NSTR = (ELEM == 1) ? 4 : 1;  /* strided sub-elements */
   const uint32_t n_items = *n_items_p;
   const uint32_t glane = threadIdx.x & (G - 1);
   const uint32_t tilef = G * ELEM * NSTR;
-  const GatherSrc g{nbr, ew, in, nbr_start, f};
+  const GatherSrc<T> g{nbr, ew, in, nbr_start, f};
   /* group index and stride: over the whole grid, or (XCD-affine) over the
    * workgroups of this block's class (every launch is NTS_BLOCK wide) */
   XcdClass xc;
@@ -465,12 +520,16 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm(
       } else if (nv > 0) { /* ragged last lane: scalar columns */
         for (uint32_t e = im.e0; e < im.e0 + im.cnt; ++e) {
           const float w = WITH_W ? ew[e] : 1.0f;
-          const float *p = in + (uint64_t)(nbr[e] - nbr_start) * f + col;
-          for (int j = 0; j < nv; ++j) acc[j] = fmaf(w, p[j], acc[j]);
+          const T *p = in + (uint64_t)(nbr[e] - nbr_start) * f + col;
+          for (int j = 0; j < nv; ++j) acc[j] = fmaf(w, to_f32(p[j]), acc[j]);
         }
       }
+      /* the pointers' common alignment is ELEM elements of T: that many
+       * bytes of `out` per vector access (bf16 ELEM=8: two dwordx4) */
+      constexpr int OV = ELEM * (int)sizeof(T) / (int)sizeof(float);
       if (nv > 0)
-        store_acc<ELEM>(out + (uint64_t)im.v * f + col, acc, nv, im.shared);
+        store_acc<ELEM, OV>(out + (uint64_t)im.v * f + col, acc, nv,
+                            im.shared);
     }
   }
 }
@@ -1153,7 +1212,7 @@ uint32_t items_grid(uint32_t batch, uint32_t edges) {
 }
 
 /* When the automatic choice engages a blocked column schedule:
- *  - the gathered matrix (rows x f x 4 B) must exceed the 256 MiB Infinity
+ *  - the gathered matrix (rows x f x element bytes) must exceed the 256 MiB Infinity
  *    Cache, far past the 8 x 4 MiB of L2: below that every row stays cached
  *    in any order, and what phase-major buys is a live set (rows x window)
  *    that fits the cache again;
@@ -1168,6 +1227,13 @@ constexpr uint32_t NTS_BLOCK_MIN_REUSE = 32;
  * over the native slab, 55.9 ms/step against 67.1 at the headline shape. */
 constexpr int NTS_AUTO_SCHED = NTS_SCHED_PHASE;
 constexpr uint32_t NTS_AUTO_WINDOW = 0;
+/* The same for bfloat16 rows, from the sweep in profiles/bench_lines.md
+ * (bf16 feature rows): XCD-affine over two windows of the headline width,
+ * 35.1 ms/step against 37.4 for the native launch and 37.8 phase-major over
+ * the native slab.  A width that 302-column windows do not cut into 2, 4 or
+ * >= 8 runs the native launch, as for any XCD request. */
+constexpr int NTS_AUTO_SCHED_BF16 = NTS_SCHED_XCD;
+constexpr uint32_t NTS_AUTO_WINDOW_BF16 = 302;
 
 /* What the environment adds to a gather launch decision, read once like
  * NTS_SPLIT.  Sweep overrides: NTS_GATHER_SCHED forces a schedule (0 = the
@@ -1196,17 +1262,25 @@ const GatherEnv &gather_env() {
   return env;
 }
 
-/* Vector width per lane (dwordx4 / dwordx2 / 4 strided dwords) from the
- * width and the pointers' common alignment, and the lane group: the
- * smallest power of two in [16,64] covering the slab work */
+/* Elements per lane from the width, the row element size and the pointers'
+ * common alignment — the widest of 16, 8 or 4 bytes of a row in one load
+ * (fp32: dwordx4 / dwordx2; bf16: 8 / 4 / 2 elements), else 4 strided
+ * single elements — and the lane group: the smallest power of two in
+ * [16,64] covering the slab work */
 struct GatherGeom { int elem, nstr; uint32_t G; };
-GatherGeom gather_geometry(uint32_t f, uintptr_t alignment) {
+GatherGeom gather_geometry(uint32_t f, uintptr_t alignment,
+                           uint32_t elem_bytes) {
   GatherGeom g;
-  if (f % 4 == 0 && alignment % 16 == 0) g.elem = 4;
-  else if (f % 2 == 0 && alignment % 8 == 0) g.elem = 2;
-  else g.elem = 1;
+  g.elem = 1;
+  for (uint32_t bytes = 16; bytes > elem_bytes; bytes /= 2) {
+    const uint32_t n = bytes / elem_bytes;
+    if (f % n == 0 && alignment % bytes == 0) {
+      g.elem = (int)n;
+      break;
+    }
+  }
   g.nstr = (g.elem == 1) ? 4 : 1;
-  const uint32_t unit = g.elem * g.nstr; /* floats per lane */
+  const uint32_t unit = g.elem * g.nstr; /* elements per lane */
   const uint32_t need = (f + unit - 1) / unit;
   g.G = 64;
   while (g.G / 2 >= need && g.G > 16) g.G /= 2;
@@ -1224,12 +1298,12 @@ struct GatherLaunch {
 
 /* Pure: no HIP call, no stream.  rows == 0 (row count unknown to the caller)
  * never engages the automatic choice. */
-GatherLaunch plan_gather(uint32_t f, uintptr_t alignment, uint32_t rows,
-                         uint32_t batch, uint32_t edges, int sched_req,
-                         int window_req, const GatherEnv &env) {
-  const GatherGeom geo = gather_geometry(f, alignment);
+GatherLaunch plan_gather(uint32_t f, uintptr_t alignment, uint32_t elem_bytes,
+                         uint32_t rows, uint32_t batch, uint32_t edges,
+                         int sched_req, int window_req, const GatherEnv &env) {
+  const GatherGeom geo = gather_geometry(f, alignment, elem_bytes);
   const uint32_t elem = geo.elem;
-  const uint32_t unit = elem * geo.nstr; /* floats per lane */
+  const uint32_t unit = elem * geo.nstr; /* elements per lane */
   const uint32_t slabf = geo.G * unit;
   const uint32_t n_slabs = (f + slabf - 1) / slabf;
   const uint64_t bound_items = (uint64_t)batch + edges / env.split + 1;
@@ -1243,10 +1317,11 @@ GatherLaunch plan_gather(uint32_t f, uintptr_t alignment, uint32_t rows,
   } else if (env.forced) {
     sched = env.sched;
     wf = env.window > 0 ? (uint32_t)env.window : 0;
-  } else if (n_slabs > 1 && (uint64_t)rows * f * 4 > NTS_BLOCK_MIN_BYTES &&
+  } else if (n_slabs > 1 &&
+             (uint64_t)rows * f * elem_bytes > NTS_BLOCK_MIN_BYTES &&
              edges / NTS_BLOCK_MIN_REUSE >= rows) {
-    sched = NTS_AUTO_SCHED;
-    wf = NTS_AUTO_WINDOW;
+    sched = elem_bytes == 2 ? NTS_AUTO_SCHED_BF16 : NTS_AUTO_SCHED;
+    wf = elem_bytes == 2 ? NTS_AUTO_WINDOW_BF16 : NTS_AUTO_WINDOW;
   }
   if (sched < NTS_SCHED_ITEM || sched > NTS_SCHED_XCD) sched = NTS_SCHED_ITEM;
   if (wf == 0) {
@@ -1293,25 +1368,32 @@ GatherLaunch plan_gather(uint32_t f, uintptr_t alignment, uint32_t rows,
       GatherPlan{NTS_SCHED_ITEM, slabf, n_slabs, 1u}};
 }
 
-void launch_gather(nts_stream *s, const float *in, float *out, const float *ew,
+/* T = row element type of `in` (float, or uint16_t for bfloat16) */
+template <typename T>
+void launch_gather(nts_stream *s, const T *in, float *out, const float *ew,
                    const uint32_t *nbr, const uint32_t *offset,
                    uint32_t nbr_start, uint32_t batch, uint32_t edges,
                    uint32_t f, int with_weight, int tag, uint32_t rows) {
   if (!batch || !edges || !f) return;
   ItemsBuf &ib = get_items(s, offset, batch, edges);
   const GatherLaunch L =
-      plan_gather(f, (uintptr_t)in | (uintptr_t)out, rows, batch, edges,
-                  s->sched_req, s->window_req, gather_env());
-  using Kernel = decltype(&k_gather_spmm<1, false, false>);
+      plan_gather(f, (uintptr_t)in | (uintptr_t)out, sizeof(T), rows, batch,
+                  edges, s->sched_req, s->window_req, gather_env());
+  using Kernel = decltype(&k_gather_spmm<T, 1, false, false>);
 #define NTS_K(E)                                                              \
-  {{k_gather_spmm<E, false, false>, k_gather_spmm<E, false, true>},           \
-   {k_gather_spmm<E, true, false>, k_gather_spmm<E, true, true>}}
-  static const Kernel kernels[3][2][2] = {NTS_K(1), NTS_K(2), NTS_K(4)};
+  {{k_gather_spmm<T, E, false, false>, k_gather_spmm<T, E, false, true>},     \
+   {k_gather_spmm<T, E, true, false>, k_gather_spmm<T, E, true, true>}}
+  /* indexed by log2(elements per lane); the last entry is the widest lane:
+   * 4 dwords, or 8 bf16 */
+  constexpr int WIDEST = 16 / (int)sizeof(T);
+  static const Kernel kernels[4][2][2] = {NTS_K(1), NTS_K(2), NTS_K(4),
+                                          NTS_K(WIDEST)};
 #undef NTS_K
   s->sched_last = (int)L.pl.sched;
   s->window_last = (int)L.pl.wf;
   Tic t(s, tag);
-  hipLaunchKernelGGL(kernels[L.elem >> 1][with_weight != 0][L.blocked],
+  hipLaunchKernelGGL(kernels[__builtin_ctz((unsigned)L.elem)]
+                            [with_weight != 0][L.blocked],
                      dim3(L.grid), dim3(NTS_BLOCK), 0, s->stream, ib.items,
                      ib.counter, nbr, ew, in, out, nbr_start, f, L.G, L.pl);
   dbg_sync(s, "k_gather_spmm");
@@ -1446,6 +1528,30 @@ void nts_gather_by_src_from_dst(nts_stream *s, const float *input,
                 NTS_KTAG_BWD, dst_end > dst_start ? dst_end - dst_start : 0);
 }
 
+void nts_gather_by_dst_from_src_bf16(
+    nts_stream *s, const uint16_t *input, float *output,
+    const float *weight_forward, const nts_vid *row_indices,
+    const nts_vid *column_offset, nts_vid src_start, nts_vid src_end,
+    nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid batch_size,
+    nts_vid feature_size, int with_weight) {
+  (void)dst_start; (void)dst_end;
+  launch_gather(s, input, output, weight_forward, row_indices, column_offset,
+                src_start, batch_size, edges, feature_size, with_weight,
+                NTS_KTAG_FWD, src_end > src_start ? src_end - src_start : 0);
+}
+
+void nts_gather_by_src_from_dst_bf16(
+    nts_stream *s, const uint16_t *input, float *output,
+    const float *weight_backward, const nts_vid *row_offset,
+    const nts_vid *column_indices, nts_vid src_start, nts_vid src_end,
+    nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid batch_size,
+    nts_vid feature_size, int with_weight) {
+  (void)src_start; (void)src_end;
+  launch_gather(s, input, output, weight_backward, column_indices, row_offset,
+                dst_start, batch_size, edges, feature_size, with_weight,
+                NTS_KTAG_BWD, dst_end > dst_start ? dst_end - dst_start : 0);
+}
+
 void nts_gather_schedule(nts_stream *s, int schedule, int window_floats) {
   s->sched_req = schedule;
   s->window_req = window_floats;
@@ -1457,21 +1563,42 @@ void nts_gather_schedule_last(nts_stream *s, int *schedule,
   if (window_floats) *window_floats = s->window_last;
 }
 
-void nts_gather_plan(nts_vid feature_size, unsigned alignment_bytes,
-                     nts_vid rows, nts_vid batch_size, nts_vid edges,
-                     int schedule_req, int window_req, int *schedule,
-                     int *window_floats, int *lane_group, int *vector_width,
-                     int *grid, int *blocked) {
+static void report_plan(uint32_t elem_bytes, nts_vid feature_size,
+                        unsigned alignment_bytes, nts_vid rows,
+                        nts_vid batch_size, nts_vid edges, int schedule_req,
+                        int window_req, int *schedule, int *window_floats,
+                        int *lane_group, int *vector_width, int *grid,
+                        int *blocked) {
   GatherLaunch L{};
   if (batch_size && edges && feature_size) /* else nothing is launched */
-    L = plan_gather(feature_size, alignment_bytes, rows, batch_size, edges,
-                    schedule_req, window_req, gather_env());
+    L = plan_gather(feature_size, alignment_bytes, elem_bytes, rows,
+                    batch_size, edges, schedule_req, window_req, gather_env());
   if (schedule) *schedule = (int)L.pl.sched;
   if (window_floats) *window_floats = (int)L.pl.wf;
   if (lane_group) *lane_group = (int)L.G;
   if (vector_width) *vector_width = L.elem;
   if (grid) *grid = (int)L.grid;
   if (blocked) *blocked = L.blocked ? 1 : 0;
+}
+
+void nts_gather_plan(nts_vid feature_size, unsigned alignment_bytes,
+                     nts_vid rows, nts_vid batch_size, nts_vid edges,
+                     int schedule_req, int window_req, int *schedule,
+                     int *window_floats, int *lane_group, int *vector_width,
+                     int *grid, int *blocked) {
+  report_plan(sizeof(float), feature_size, alignment_bytes, rows, batch_size,
+              edges, schedule_req, window_req, schedule, window_floats,
+              lane_group, vector_width, grid, blocked);
+}
+
+void nts_gather_plan_bf16(nts_vid feature_size, unsigned alignment_bytes,
+                          nts_vid rows, nts_vid batch_size, nts_vid edges,
+                          int schedule_req, int window_req, int *schedule,
+                          int *window_floats, int *lane_group,
+                          int *vector_width, int *grid, int *blocked) {
+  report_plan(sizeof(uint16_t), feature_size, alignment_bytes, rows,
+              batch_size, edges, schedule_req, window_req, schedule,
+              window_floats, lane_group, vector_width, grid, blocked);
 }
 
 void nts_items_cache_clear(nts_stream *s) {
@@ -1798,7 +1925,8 @@ int nts_gather_by_src_from_dst_dot(nts_stream *s, const float *input,
   const uint32_t f = feature_size;
   if (!batch_size || !edges || !f) return 1;
   const GatherGeom geo = gather_geometry(
-      f, (uintptr_t)input | (uintptr_t)output | (uintptr_t)dot_vec);
+      f, (uintptr_t)input | (uintptr_t)output | (uintptr_t)dot_vec,
+      sizeof(float));
   const int elem = geo.elem;
   const uint32_t G = geo.G;
   if (elem == 1 || f > G * (uint32_t)elem) {

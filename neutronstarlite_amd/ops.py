@@ -56,6 +56,26 @@ class DeviceChunk:
         return self.src_e - self.src_s
 
 
+def gather_entry(stream: "shim.Stream", forward: bool, inp: torch.Tensor,
+                 out: torch.Tensor):
+    """The stream's gather entry for the dtype of the gathered rows: float32,
+    or bfloat16 (widened exactly in the kernel).  Weights, accumulation and
+    `out` are float32 either way.  Raises before anything is launched: the
+    kernels take raw pointers and would misread any other element type."""
+    if not (inp.is_cuda and out.is_cuda):
+        raise TypeError("gather needs device tensors")
+    if out.dtype != torch.float32:
+        raise TypeError(f"gather output must be float32, got {out.dtype}")
+    if inp.dtype == torch.float32:
+        return (stream.gather_by_dst_from_src if forward
+                else stream.gather_by_src_from_dst)
+    if inp.dtype == torch.bfloat16:
+        return (stream.gather_by_dst_from_src_bf16 if forward
+                else stream.gather_by_src_from_dst_bf16)
+    raise TypeError(
+        f"gather input must be float32 or bfloat16, got {inp.dtype}")
+
+
 class HipEngine:
     """The product aggregation engine: HIP kernels via the C-ABI on the
     current torch stream."""
@@ -65,12 +85,14 @@ class HipEngine:
 
     def csc_forward(self, ch: DeviceChunk, x_block: torch.Tensor,
                     y: torch.Tensor, with_weight=True):
-        """y[0:dst_n] += CSC-aggregate of x_block (dense over ch's src range)."""
+        """y[0:dst_n] += CSC-aggregate of x_block (dense over ch's src range;
+        float32 or bfloat16 rows, y float32)."""
         f = y.shape[1]
-        assert x_block.is_cuda and y.is_cuda and x_block.dtype == torch.float32
+        gather = gather_entry(self.stream, True, x_block, y)
         assert x_block.is_contiguous() and y.is_contiguous()
         assert x_block.shape[0] == ch.src_n and y.shape[0] == ch.dst_n
-        self.stream.gather_by_dst_from_src(
+        assert x_block.shape[1] == f
+        gather(
             x_block.data_ptr(), y.data_ptr(), ch.w_fwd.data_ptr(),
             ch.row_indices.data_ptr(), ch.column_offset.data_ptr(),
             ch.src_s, ch.src_e, ch.dst_s, ch.dst_e,
@@ -78,11 +100,14 @@ class HipEngine:
 
     def csr_backward(self, ch: DeviceChunk, grad_block: torch.Tensor,
                      out: torch.Tensor, with_weight=True):
-        """out[0:src_n] += CSR-aggregate of grad_block (dense over dst range)."""
+        """out[0:src_n] += CSR-aggregate of grad_block (dense over dst range;
+        float32 or bfloat16 rows, out float32)."""
         f = out.shape[1]
+        gather = gather_entry(self.stream, False, grad_block, out)
         assert grad_block.is_contiguous() and out.is_contiguous()
         assert grad_block.shape[0] == ch.dst_n and out.shape[0] == ch.src_n
-        self.stream.gather_by_src_from_dst(
+        assert grad_block.shape[1] == f
+        gather(
             grad_block.data_ptr(), out.data_ptr(), ch.w_bwd.data_ptr(),
             ch.row_offset.data_ptr(), ch.column_indices.data_ptr(),
             ch.src_s, ch.src_e, ch.dst_s, ch.dst_e,
@@ -99,6 +124,7 @@ class _AggregateFn(torch.autograd.Function):
     def forward(ctx, x, dchunk, engine):
         ctx.dchunk = dchunk
         ctx.engine = engine
+        ctx.x_dtype = x.dtype
         y = torch.zeros(dchunk.dst_n, x.shape[1], dtype=torch.float32,
                         device=x.device)
         engine.csc_forward(dchunk, x.contiguous(), y)
@@ -109,7 +135,7 @@ class _AggregateFn(torch.autograd.Function):
         gx = torch.zeros(ctx.dchunk.src_n, grad_y.shape[1],
                          dtype=torch.float32, device=grad_y.device)
         ctx.engine.csr_backward(ctx.dchunk, grad_y.contiguous(), gx)
-        return gx, None, None
+        return gx.to(ctx.x_dtype), None, None
 
 
 def aggregate(x: torch.Tensor, dchunk: "DeviceChunk",
@@ -127,11 +153,12 @@ class _MiniBatchAggFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, op):
         ctx.op = op
+        ctx.x_dtype = x.dtype
         return op.forward(x.contiguous())
 
     @staticmethod
     def backward(ctx, grad_y):
-        return ctx.op.backward(grad_y.contiguous()), None
+        return ctx.op.backward(grad_y.contiguous()).to(ctx.x_dtype), None
 
 
 def minibatch_aggregate(x: torch.Tensor, op: "MiniBatchFuseOp") -> torch.Tensor:
@@ -170,7 +197,7 @@ class MiniBatchFuseOp:
         f = x_compact.shape[1]
         y = torch.zeros(ly.n_dst, f, dtype=torch.float32,
                         device=x_compact.device)
-        self.engine.stream.gather_by_dst_from_src(
+        gather_entry(self.engine.stream, True, x_compact, y)(
             x_compact.data_ptr(), y.data_ptr(), self.w_fwd.data_ptr(),
             self.row_indices.data_ptr(), self.column_offset.data_ptr(),
             0, ly.n_src, 0, ly.n_dst, ly.e_size, ly.n_dst, f, True)
@@ -182,7 +209,7 @@ class MiniBatchFuseOp:
         f = grad_y.shape[1]
         gx = torch.zeros(ly.n_src, f, dtype=torch.float32,
                          device=grad_y.device)
-        self.engine.stream.gather_by_src_from_dst(
+        gather_entry(self.engine.stream, False, grad_y, gx)(
             grad_y.data_ptr(), gx.data_ptr(), self.w_bwd.data_ptr(),
             self.row_offset.data_ptr(), self.column_indices.data_ptr(),
             0, ly.n_src, 0, ly.n_dst, ly.e_size, ly.n_src, f, True)

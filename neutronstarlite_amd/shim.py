@@ -72,10 +72,15 @@ def lib():
     # hot kernels
     l.nts_gather_by_dst_from_src.argtypes = [_vp] + [_vp] * 5 + [_u32] * 7 + [_i32]
     l.nts_gather_by_src_from_dst.argtypes = [_vp] + [_vp] * 5 + [_u32] * 7 + [_i32]
+    l.nts_gather_by_dst_from_src_bf16.argtypes = (
+        l.nts_gather_by_dst_from_src.argtypes)
+    l.nts_gather_by_src_from_dst_bf16.argtypes = (
+        l.nts_gather_by_src_from_dst.argtypes)
     l.nts_items_cache_clear.argtypes = [_vp]
     l.nts_gather_schedule.argtypes = [_vp, _i32, _i32]
     l.nts_gather_schedule_last.argtypes = [_vp, _vp, _vp]
     l.nts_gather_plan.argtypes = [_u32] * 5 + [_i32] * 2 + [_vp] * 6
+    l.nts_gather_plan_bf16.argtypes = l.nts_gather_plan.argtypes
     l.nts_deserialize_to_gpu.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _i32]
     l.nts_aggregate_comm_result.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _i32]
     l.nts_gather_rows.argtypes = [_vp, _vp, _vp, _vp, _u32, _u32, _u32]
@@ -111,18 +116,30 @@ def lib():
     return l
 
 
+def _plan(entry, f, alignment, rows, batch, edges, schedule, window):
+    names = ("schedule", "window", "lane_group", "vector_width", "grid",
+             "blocked")
+    out = [_i32(0) for _ in names]
+    entry(f, alignment, rows, batch, edges, schedule, window,
+          *[_c.byref(o) for o in out])
+    plan = {n: o.value for n, o in zip(names, out)}
+    plan["blocked"] = bool(plan["blocked"])
+    return plan
+
+
 def gather_plan(f, alignment, rows, batch, edges, schedule=0, window=0):
     """The launch decision a gather of this shape would take (no device
     access): dict of schedule, window, lane_group, vector_width, grid,
     blocked.  (schedule, window) is a request as for Stream.gather_schedule."""
-    names = ("schedule", "window", "lane_group", "vector_width", "grid",
-             "blocked")
-    out = [_i32(0) for _ in names]
-    lib().nts_gather_plan(f, alignment, rows, batch, edges, schedule, window,
-                          *[_c.byref(o) for o in out])
-    plan = {n: o.value for n, o in zip(names, out)}
-    plan["blocked"] = bool(plan["blocked"])
-    return plan
+    return _plan(lib().nts_gather_plan, f, alignment, rows, batch, edges,
+                 schedule, window)
+
+
+def gather_plan_bf16(f, alignment, rows, batch, edges, schedule=0, window=0):
+    """gather_plan for bfloat16 feature rows: vector_width is in elements per
+    lane (8, 4, 2 or 1), window in columns."""
+    return _plan(lib().nts_gather_plan_bf16, f, alignment, rows, batch, edges,
+                 schedule, window)
 
 
 _live_streams = weakref.WeakSet()
@@ -191,6 +208,25 @@ class Stream:
                                column_indices_ptr, src_s, src_e, dst_s, dst_e,
                                edges, batch, f, with_weight=True):
         self._lib.nts_gather_by_src_from_dst(
+            self.h, _vp(g_ptr), _vp(y_ptr), _vp(w_ptr), _vp(row_offset_ptr),
+            _vp(column_indices_ptr), src_s, src_e, dst_s, dst_e, edges, batch,
+            f, 1 if with_weight else 0)
+
+    def gather_by_dst_from_src_bf16(self, x_ptr, y_ptr, w_ptr,
+                                    row_indices_ptr, column_offset_ptr, src_s,
+                                    src_e, dst_s, dst_e, edges, batch, f,
+                                    with_weight=True):
+        """gather_by_dst_from_src over bfloat16 input rows (fp32 output)."""
+        self._lib.nts_gather_by_dst_from_src_bf16(
+            self.h, _vp(x_ptr), _vp(y_ptr), _vp(w_ptr), _vp(row_indices_ptr),
+            _vp(column_offset_ptr), src_s, src_e, dst_s, dst_e, edges, batch,
+            f, 1 if with_weight else 0)
+
+    def gather_by_src_from_dst_bf16(self, g_ptr, y_ptr, w_ptr, row_offset_ptr,
+                                    column_indices_ptr, src_s, src_e, dst_s,
+                                    dst_e, edges, batch, f, with_weight=True):
+        """gather_by_src_from_dst over bfloat16 input rows (fp32 output)."""
+        self._lib.nts_gather_by_src_from_dst_bf16(
             self.h, _vp(g_ptr), _vp(y_ptr), _vp(w_ptr), _vp(row_offset_ptr),
             _vp(column_indices_ptr), src_s, src_e, dst_s, dst_e, edges, batch,
             f, 1 if with_weight else 0)

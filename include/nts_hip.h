@@ -83,11 +83,15 @@ void nts_memcpy_d2h(nts_stream *s, void *h, const void *d, long bytes, int sync)
  * feature_size by slab decomposition, and power-law columns are split into
  * bounded work items on device (see nts_hip.hip).  with_weight=0 replaces the
  * _without_weight twins.
- * LIMITATION (tensor_weight): an edge weight is ONE fp32 scalar per edge.  The
- * reference's tensor_weight form, a weight row of feature_size values per
- * edge multiplied element by element, has no entry point here: none of the
- * exercised configs uses it, and a caller that needs it must materialize the
- * per-edge messages with the edge-wise kernels below instead. */
+ * tensor_weight: in these two entries an edge weight is ONE fp32 scalar per
+ * edge.  The reference's tensor_weight form, a weight row of feature_size
+ * values per edge multiplied element by element (the _tensor_weight kernels
+ * of ntsCUDAFuseKernel.cuh, Gather_By_Dst_From_Src(..., tensor_weight=true)),
+ * is the heads gather below called with heads == feature_size.  Its cost:
+ * the column schedules do not apply (the native launch always runs), and
+ * with one column per head the lanes run the 4-strided-dword path with one
+ * weight load per element, so an edge reads as many weight bytes as row
+ * bytes.  Not measured: no exercised config uses it. */
 void nts_gather_by_dst_from_src(nts_stream *s,
     const float *input, float *output, const float *weight_forward,
     const nts_vid *row_indices, const nts_vid *column_offset,
@@ -130,6 +134,42 @@ void nts_gather_by_src_from_dst_bf16(nts_stream *s,
     const nts_vid *row_offset, const nts_vid *column_indices,
     nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
     nts_vid edges, nts_vid batch_size, nts_vid feature_size, int with_weight);
+
+/* ---- per-head edge weights (additive, not in the reference ABI) ----
+ * The same two gathers with a ROW of `heads` fp32 weights per edge (multi-
+ * head GAT): K = heads, C = feature_size / heads columns per head, columns
+ * head-major (column c belongs to head c / C), weights [edges, K] row-major,
+ * in CSC edge order for the forward gather and CSR order for the backward:
+ *   output[d,c] += sum_{e in column d} w[e*K + c/C] * input[row_indices[e]-src_start, c]
+ *   output[v,c] += sum_{e in row v}    w[e*K + c/C] * input[column_indices[e]-dst_start, c]
+ * The += contract, the work items, NTS_SPLIT, the item cache and the
+ * NTS_KTAG_FWD / NTS_KTAG_BWD tags are those of the scalar gathers.  Lane
+ * width: the widest of 4 / 2 dwords that divides C as well as feature_size
+ * and that the pointers' alignment permits (a lane then loads one weight per
+ * edge), else 4 strided dwords per lane with the head of each element.
+ * Only the native launch runs (nts_gather_schedule requests are ignored,
+ * nts_gather_schedule_last reports NTS_SCHED_ITEM): GAT widths sit far below
+ * the sizes at which the column schedules engage.  heads == 1 IS the scalar
+ * entry with with_weight = 1 (same launch); heads == feature_size is the
+ * reference's tensor_weight form.  heads == 0, heads > feature_size or
+ * feature_size % heads != 0 aborts.  fp32 rows only. */
+void nts_gather_by_dst_from_src_heads(nts_stream *s,
+    const float *input, float *output, const float *weight_forward,
+    const nts_vid *row_indices, const nts_vid *column_offset,
+    nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
+    nts_vid edges, nts_vid batch_size, nts_vid feature_size, nts_vid heads);
+void nts_gather_by_src_from_dst_heads(nts_stream *s,
+    const float *input, float *output, const float *weight_backward,
+    const nts_vid *row_offset, const nts_vid *column_indices,
+    nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
+    nts_vid edges, nts_vid batch_size, nts_vid feature_size, nts_vid heads);
+
+/* The launch decision of a heads gather, without touching the device (like
+ * nts_gather_plan): lane group, dwords per lane (4, 2 or 1) and grid.  With
+ * heads == 1 these are nts_gather_plan's for the request (0, -1). */
+void nts_gather_plan_heads(nts_vid feature_size, nts_vid heads,
+    unsigned alignment_bytes, nts_vid batch_size, nts_vid edges,
+    int *lane_group, int *vector_width, int *grid);
 
 /* Column schedule of the gather entry points, fp32 and bf16.  A gather task is (work
  * item, column window of `window_floats` floats); the schedule only changes
@@ -302,6 +342,48 @@ void nts_edge_attention_forward(nts_stream *s, float *softmax_out,
  * source gradient).  out is caller-zeroed. */
 void nts_weight_sum(nts_stream *s, float *out, const float *weights,
     const nts_vid *offset, nts_vid batch_size);
+
+/* ---- multi-head GAT edge entries (additive) ----
+ * K = heads.  Per-edge values (softmax, m_sum, gradients) are fp32
+ * [edges, K] row-major, per-vertex attention scalars fp32 [rows, K]
+ * row-major; this is what nts_edge_softmax_forward_dual and
+ * nts_edge_softmax_backward_fused read and write with feature_size = K.
+ * These three take the host-known edge count, as the gathers do, so they
+ * add no device-to-host copy and no stream synchronize.  heads == 1 runs the
+ * single-head kernel of the entry named in each comment.  Invalid heads
+ * abort as for the heads gathers. */
+
+/* nts_edge_attention_forward for K heads: per edge and head
+ * m = s_src_mirror[mirror_index[src]*K + k] + s_dst[dst*K + k] (mirror_index
+ * NULL = identity), stored to m_sum_out; leaky-relu(slope), exp without max
+ * subtraction, per-(destination, head) sums; the shared normalize pass then
+ * dual-emits the softmax at softmax_out[e*K + k] and, with perm_pos, at
+ * softmax_out_perm[perm_pos[e]*K + k]. */
+void nts_edge_attention_forward_heads(nts_stream *s, float *softmax_out,
+    float *softmax_out_perm, const nts_vid *perm_pos, float *m_sum_out,
+    const float *s_src_mirror, const float *s_dst,
+    const nts_vid *row_indices, const nts_vid *mirror_index, float slope,
+    const nts_vid *column_offset, nts_vid batch_size, nts_vid edges,
+    nts_vid heads);
+
+/* nts_edge_dot per head: out[e*K + k] = sum_{j<C} dst_rows[d, k*C + j] *
+ * src_rows[row_indices[e]-src_start, k*C + j], C = feature_size / heads. */
+void nts_edge_dot_heads(nts_stream *s, float *out, const float *dst_rows,
+    const float *src_rows, const nts_vid *row_indices,
+    const nts_vid *column_offset, nts_vid src_start, nts_vid batch_size,
+    nts_vid edges, nts_vid feature_size, nts_vid heads);
+
+/* nts_weight_sum over K columns: out[v*K + k] += sum of weights[e*K + k]
+ * over v's edges (CSC or CSR offsets). */
+void nts_weight_sum_heads(nts_stream *s, float *out, const float *weights,
+    const nts_vid *offset, nts_vid batch_size, nts_vid edges, nts_vid heads);
+
+/* TEST/MEASUREMENT hook: with enable=1 the three heads edge entries above
+ * run their general kernel forms (any K, any C) on this stream even where a
+ * faster form exists for the shape (attention forward and weight sum: K a
+ * power of two <= 64; edge dot: C a power of two <= 256), so both can be
+ * tested and timed on the same input. */
+void nts_heads_dbg_general(nts_stream *s, int enable);
 
 /* Opt-in work-item reuse: with enable=1 the stream caches its two most
  * recent item decompositions keyed on (offset pointer, batch, edges) and

@@ -107,6 +107,7 @@ struct nts_stream {
   int sched_last = 0, window_last = 0; /* what the last gather ran */
   float *sums_ws = nullptr;  /* per-dst reduction scratch (softmax) */
   uint64_t sums_cap = 0;
+  bool heads_general = false; /* nts_heads_dbg_general: no heads fast paths */
 };
 
 namespace {
@@ -530,6 +531,95 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm(
       if (nv > 0)
         store_acc<ELEM, OV>(out + (uint64_t)im.v * f + col, acc, nv,
                             im.shared);
+    }
+  }
+}
+
+/* ---- multi-head gather: a row of K weights per edge ---- */
+/* Sibling of k_gather_spmm<float, ELEM, true, false> on the same helpers
+ * (decode_task, fma_vec, store_acc, store_strided): a lane group per (work
+ * item, slab), four row loads in flight, register accumulation, one store.
+ * Columns are head-major, C per head, and edge e scales column c by
+ * ew[e*K + c/C].  ELEM = 4 or 2 is chosen to divide C as well as f, so a
+ * lane's vector never straddles two heads and the lane loads ONE weight per
+ * edge (f % ELEM == 0: every live lane is full, there is no ragged lane);
+ * ELEM = 1 runs 4 strided dwords per lane with the head of each element. */
+template <int ELEM, int NE>
+__device__ __forceinline__ void heads_edges_vec(float (&acc)[ELEM],
+                                                const GatherSrc<float> &g,
+                                                uint32_t e, uint32_t col,
+                                                uint32_t K, uint32_t head) {
+  const float *p[NE];
+  float wv[NE];
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    p[k] = g.in + (uint64_t)(g.nbr[e + k] - g.nbr_start) * g.f + col;
+    wv[k] = g.ew[(uint64_t)(e + k) * K + head];
+  }
+  fma_vec<ELEM, NE>(acc, p, wv);
+}
+/* strided twin: element j at column col + j*G, head hd[j], live while
+ * col + j*G < f */
+template <int NSTR, int NE>
+__device__ __forceinline__ void heads_edges_strided(
+    float (&acc)[NSTR], const GatherSrc<float> &g, uint32_t e, uint32_t col,
+    uint32_t G, uint32_t K, const uint32_t (&hd)[NSTR]) {
+  const float *p[NE];
+  const float *wrow[NE];
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    p[k] = g.in + (uint64_t)(g.nbr[e + k] - g.nbr_start) * g.f + col;
+    wrow[k] = g.ew + (uint64_t)(e + k) * K;
+  }
+#pragma unroll
+  for (int k = 0; k < NE; ++k)
+#pragma unroll
+    for (int j = 0; j < NSTR; ++j)
+      if (col + j * G < g.f)
+        acc[j] = fmaf(wrow[k][hd[j]], p[k][j * G], acc[j]);
+}
+
+template <int ELEM>
+__global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm_heads(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ nbr, const float *__restrict__ ew,
+    const float *__restrict__ in, float *__restrict__ out, uint32_t nbr_start,
+    uint32_t f, uint32_t G, uint32_t n_slabs, uint32_t K, uint32_t C) {
+  constexpr int NSTR = (ELEM == 1) ? 4 : 1;
+  const uint32_t n_items = *n_items_p;
+  const uint32_t glane = threadIdx.x & (G - 1);
+  const uint32_t tilef = G * ELEM * NSTR;
+  const GatherSrc<float> g{nbr, ew, in, nbr_start, f};
+  const GatherPlan pl{NTS_SCHED_ITEM, tilef, n_slabs, 1u};
+  const XcdClass xc;
+  const uint64_t total = (uint64_t)n_items * n_slabs;
+  const uint64_t stride = (gridDim.x * NTS_BLOCK) / G;
+  for (uint64_t t = (blockIdx.x * NTS_BLOCK + threadIdx.x) / G; t < total;
+       t += stride) {
+    const Task tk = decode_task<false>(pl, xc, t, n_items, f, tilef);
+    const uint32_t col = tk.fbase + glane * ELEM;
+    if (col >= f) continue;
+    const Item im = load_item(items, tk.it);
+    const uint32_t e_end = im.e0 + im.cnt;
+    uint32_t e = im.e0;
+    float acc[ELEM * NSTR] = {};
+    float *o = out + (uint64_t)im.v * f + col;
+    if constexpr (ELEM == 1) {
+      uint32_t hd[NSTR];
+#pragma unroll
+      for (int j = 0; j < NSTR; ++j)
+        hd[j] = (col + j * G < f) ? (col + j * G) / C : 0u;
+      for (; e + 4 <= e_end; e += 4)
+        heads_edges_strided<NSTR, 4>(acc, g, e, col, G, K, hd);
+      for (; e < e_end; ++e)
+        heads_edges_strided<NSTR, 1>(acc, g, e, col, G, K, hd);
+      store_strided(o, acc, G, col, f, im.shared);
+    } else {
+      const uint32_t head = col / C;
+      for (; e + 4 <= e_end; e += 4)
+        heads_edges_vec<ELEM, 4>(acc, g, e, col, K, head);
+      for (; e < e_end; ++e) heads_edges_vec<ELEM, 1>(acc, g, e, col, K, head);
+      store_acc<ELEM>(o, acc, ELEM, im.shared);
     }
   }
 }
@@ -1126,6 +1216,214 @@ __global__ void k_edge_dot(const uint4 *__restrict__ items,
   }
 }
 
+/* ---------------- multi-head edge kernels ---------------- */
+/* Per-edge values are [E, K] row-major, per-vertex scalars [rows, K].  Each
+ * kernel comes in two forms.  The general one, for any K, is the loop order
+ * of k_edge_softmax_sum: for each head, lanes stride the item's edges,
+ * wave_sum, one atomic per (item, head).  FLAT, for K a power of two <= 64:
+ * lanes stride the item's cnt*K values in memory order (coalesced); 64 % K
+ * == 0, so a lane stays on head lane % K, and the butterfly steps xor 32..K
+ * leave head k's sum on lanes == k mod K. */
+__device__ __forceinline__ float heads_lane_sum(float x, uint32_t K) {
+  for (uint32_t w = 32; w >= K; w >>= 1) x += __shfl_xor(x, w, 64);
+  return x;
+}
+
+/* attention forward, pass 1, K heads (k_edge_att_sum's twin) */
+template <bool FLAT>
+__global__ void k_edge_att_sum_heads(const uint4 *__restrict__ items,
+                                     const uint32_t *__restrict__ n_items_p,
+                                     float *__restrict__ out /* exp stash */,
+                                     float *__restrict__ m_sum_out,
+                                     const float *__restrict__ s_src,
+                                     const float *__restrict__ s_dst,
+                                     const uint32_t *__restrict__ row_indices,
+                                     const uint32_t *__restrict__ mirror_index,
+                                     float slope, float *__restrict__ sums,
+                                     uint32_t K) {
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    const uint32_t d = im.v;
+    if constexpr (FLAT) {
+      const uint32_t k = w.lane & (K - 1);
+      const uint32_t lgk = 31u - (uint32_t)__clz(K);
+      const float sd = s_dst[(uint64_t)d * K + k];
+      const uint64_t m0 = (uint64_t)im.e0 * K;
+      const uint64_t nel = (uint64_t)im.cnt * K;
+      float part = 0.f;
+      for (uint64_t i = w.lane; i < nel; i += 64) {
+        const uint32_t src = row_indices[im.e0 + (uint32_t)(i >> lgk)];
+        const uint64_t row = mirror_index ? mirror_index[src] : src;
+        const float m = s_src[row * K + k] + sd;
+        m_sum_out[m0 + i] = m;
+        const float a = (m > 0.f) ? m : slope * m;
+        const float v = __expf(a); /* no max subtraction, as k_edge_att_sum */
+        out[m0 + i] = v;
+        part += v;
+      }
+      part = heads_lane_sum(part, K);
+      if (w.lane < K) atomicAdd(&sums[(uint64_t)d * K + w.lane], part);
+    } else {
+      for (uint32_t k = 0; k < K; ++k) {
+        const float sd = s_dst[(uint64_t)d * K + k];
+        float part = 0.f;
+        for (uint32_t j = w.lane; j < im.cnt; j += 64) {
+          const uint32_t e = im.e0 + j;
+          const uint32_t src = row_indices[e];
+          const uint64_t row = mirror_index ? mirror_index[src] : src;
+          const float m = s_src[row * K + k] + sd;
+          m_sum_out[(uint64_t)e * K + k] = m;
+          const float a = (m > 0.f) ? m : slope * m;
+          const float v = __expf(a);
+          out[(uint64_t)e * K + k] = v;
+          part += v;
+        }
+        part = wave_sum(part);
+        if (w.lane == 0) atomicAdd(&sums[(uint64_t)d * K + k], part);
+      }
+    }
+  }
+}
+
+/* out[v*K + k] += sum over v's edges of weights[e*K + k] (k_weight_sum's
+ * twin; split vertices merge by atomics) */
+template <bool FLAT>
+__global__ void k_weight_sum_heads(const uint4 *__restrict__ items,
+                                   const uint32_t *__restrict__ n_items_p,
+                                   float *__restrict__ out,
+                                   const float *__restrict__ weights,
+                                   uint32_t K) {
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    const float *wp = weights + (uint64_t)im.e0 * K;
+    float *o = out + (uint64_t)im.v * K;
+    if constexpr (FLAT) {
+      const uint64_t nel = (uint64_t)im.cnt * K;
+      float part = 0.f;
+      for (uint64_t i = w.lane; i < nel; i += 64) part += wp[i];
+      part = heads_lane_sum(part, K);
+      if (w.lane < K) {
+        if (im.shared) atomicAdd(&o[w.lane], part);
+        else o[w.lane] += part;
+      }
+    } else {
+      for (uint32_t k = 0; k < K; ++k) {
+        float part = 0.f;
+        for (uint32_t j = w.lane; j < im.cnt; j += 64)
+          part += wp[(uint64_t)j * K + k];
+        part = wave_sum(part);
+        if (w.lane == 0) {
+          if (im.shared) atomicAdd(&o[k], part);
+          else o[k] += part;
+        }
+      }
+    }
+  }
+}
+
+/* per-head edge dot: out[e*K + k] = dot over head k's C columns.
+ * The general form runs a wave per (edge, head): lanes stride the head's C
+ * columns, wave_sum (64 - C lanes idle when C < 64).
+ * k_edge_dot_heads_seg, for C a power of two <= 64*R: a lane holds R
+ * consecutive columns (one dwordxR load: 4, 2 or 1 by C and the pointers'
+ * alignment), so a head is an aligned segment of L = C/R lanes and a row is
+ * G = f/R lanes (at most 64 per step); 64/G edges share a wave.  The lane
+ * multiplies its R columns, a log2(L)-step butterfly sums each segment, and
+ * the segment's first lane writes.  Lanes past the row's end and edge slots
+ * past the item's end load a clamped (valid) address and are never written:
+ * segments lie inside one head and one lane group, so what such lanes hold
+ * never meets a live sum. */
+__device__ __forceinline__ float seg_sum(float x, uint32_t L) {
+  for (uint32_t w = L >> 1; w >= 1; w >>= 1) x += __shfl_xor(x, w, 64);
+  return x;
+}
+
+template <int R>
+__global__ void k_edge_dot_heads_seg(const uint4 *__restrict__ items,
+                                     const uint32_t *__restrict__ n_items_p,
+                                     float *__restrict__ out,
+                                     const float *__restrict__ dst_rows,
+                                     const float *__restrict__ src_rows,
+                                     const uint32_t *__restrict__ row_indices,
+                                     uint32_t src_start, uint32_t f,
+                                     uint32_t K, uint32_t C, uint32_t G) {
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  const uint32_t L = C / R;          /* lanes per head */
+  const uint32_t gl = w.lane & (G - 1);
+  const uint32_t gi = w.lane / G;    /* which of the wave's edge slots */
+  const uint32_t ng = 64 / G;
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    const uint32_t e0 = im.e0, cnt = im.cnt;
+    for (uint32_t base = 0; base < f; base += G * R) {
+      const uint32_t col = base + gl * R;
+      const bool live = col < f;     /* f % R == 0: a live lane is full */
+      const uint32_t cc = live ? col : 0u;
+      const bool writer = live && (gl & (L - 1)) == 0;
+      const uint32_t head = cc / C;
+      float av[R];
+      if constexpr (R == 1) av[0] = dst_rows[(uint64_t)im.v * f + cc];
+      else load_lane<R>(dst_rows + (uint64_t)im.v * f + cc, av);
+      /* 4 edge slots per lane group in flight */
+      for (uint32_t k0 = 0; k0 < cnt; k0 += 4 * ng) {
+        float pr[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const uint32_t k = min(k0 + q * ng + gi, cnt - 1);
+          const float *b = src_rows +
+              (uint64_t)(row_indices[e0 + k] - src_start) * f + cc;
+          float bv[R];
+          if constexpr (R == 1) bv[0] = b[0];
+          else load_lane<R>(b, bv);
+          pr[q] = 0.f;
+#pragma unroll
+          for (int j = 0; j < R; ++j) pr[q] = fmaf(av[j], bv[j], pr[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const uint32_t k = k0 + q * ng + gi;
+          const float sum = seg_sum(pr[q], L);
+          if (writer && k < cnt) out[(uint64_t)(e0 + k) * K + head] = sum;
+        }
+      }
+    }
+  }
+}
+
+__global__ void k_edge_dot_heads(const uint4 *__restrict__ items,
+                                 const uint32_t *__restrict__ n_items_p,
+                                 float *__restrict__ out,
+                                 const float *__restrict__ dst_rows,
+                                 const float *__restrict__ src_rows,
+                                 const uint32_t *__restrict__ row_indices,
+                                 uint32_t src_start, uint32_t f, uint32_t K,
+                                 uint32_t C) {
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  const uint32_t lane = w.lane;
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    const uint32_t e0 = im.e0, cnt = im.cnt;
+    const float *a = dst_rows + (uint64_t)im.v * f;
+    for (uint32_t k = 0; k < cnt; ++k) {
+      const uint32_t e = e0 + k;
+      const float *b = src_rows + (uint64_t)(row_indices[e] - src_start) * f;
+      for (uint32_t h = 0; h < K; ++h) {
+        float sum = 0.f;
+        for (uint32_t j = h * C + lane; j < (h + 1) * C; j += 64)
+          sum = fmaf(a[j], b[j], sum);
+        sum = wave_sum(sum);
+        if (lane == 0) out[(uint64_t)e * K + h] = sum;
+      }
+    }
+  }
+}
+
 /* forward softmax also fills msg_cached */
 __global__ void k_copy(float *__restrict__ dst, const float *__restrict__ src,
                        uint64_t n) {
@@ -1268,13 +1566,17 @@ const GatherEnv &gather_env() {
  * single elements — and the lane group: the smallest power of two in
  * [16,64] covering the slab work */
 struct GatherGeom { int elem, nstr; uint32_t G; };
+/* also_divides (0 = absent): a second width the lane's element count must
+ * divide — the columns per head of a heads gather, so that no lane's vector
+ * straddles two heads */
 GatherGeom gather_geometry(uint32_t f, uintptr_t alignment,
-                           uint32_t elem_bytes) {
+                           uint32_t elem_bytes, uint32_t also_divides = 0) {
   GatherGeom g;
   g.elem = 1;
   for (uint32_t bytes = 16; bytes > elem_bytes; bytes /= 2) {
     const uint32_t n = bytes / elem_bytes;
-    if (f % n == 0 && alignment % bytes == 0) {
+    if (f % n == 0 && alignment % bytes == 0 &&
+        (!also_divides || also_divides % n == 0)) {
       g.elem = (int)n;
       break;
     }
@@ -1397,6 +1699,59 @@ void launch_gather(nts_stream *s, const T *in, float *out, const float *ew,
                      dim3(L.grid), dim3(NTS_BLOCK), 0, s->stream, ib.items,
                      ib.counter, nbr, ew, in, out, nbr_start, f, L.G, L.pl);
   dbg_sync(s, "k_gather_spmm");
+}
+
+/* heads: 1 <= K <= f and K | f, else abort (error culture of the header) */
+void check_heads(const char *entry, uint32_t f, uint32_t heads) {
+  if (heads == 0 || heads > f || f % heads != 0) {
+    fprintf(stderr, "%s: heads %u does not divide feature_size %u\n", entry,
+            heads, f);
+    abort();
+  }
+}
+
+/* Launch decision of a heads gather: always the native launch (one tile per
+ * slab, item-major), lanes narrowed until they divide the columns per head.
+ * Pure, like plan_gather; at K = 1 it is plan_gather's native launch. */
+GatherLaunch plan_gather_heads(uint32_t f, uint32_t heads, uintptr_t alignment,
+                               uint32_t batch, uint32_t edges,
+                               const GatherEnv &env) {
+  const GatherGeom geo =
+      gather_geometry(f, alignment, sizeof(float), f / heads);
+  const uint32_t slabf = geo.G * geo.elem * geo.nstr;
+  const uint32_t n_slabs = (f + slabf - 1) / slabf;
+  const uint64_t bound_items = (uint64_t)batch + edges / env.split + 1;
+  return GatherLaunch{
+      geo.elem, geo.G,
+      grid_for(bound_items * n_slabs * geo.G, env.max_blocks), false,
+      GatherPlan{NTS_SCHED_ITEM, slabf, n_slabs, 1u}};
+}
+
+void launch_gather_heads(nts_stream *s, const char *entry, const float *in,
+                         float *out, const float *ew, const uint32_t *nbr,
+                         const uint32_t *offset, uint32_t nbr_start,
+                         uint32_t batch, uint32_t edges, uint32_t f,
+                         uint32_t heads, int tag, uint32_t rows) {
+  check_heads(entry, f, heads);
+  if (heads == 1) { /* the scalar gather itself */
+    launch_gather(s, in, out, ew, nbr, offset, nbr_start, batch, edges, f, 1,
+                  tag, rows);
+    return;
+  }
+  if (!batch || !edges) return;
+  ItemsBuf &ib = get_items(s, offset, batch, edges);
+  const GatherLaunch L = plan_gather_heads(
+      f, heads, (uintptr_t)in | (uintptr_t)out, batch, edges, gather_env());
+  s->sched_last = (int)L.pl.sched;
+  s->window_last = (int)L.pl.wf;
+  Tic t(s, tag);
+  hipLaunchKernelGGL(L.elem == 4   ? k_gather_spmm_heads<4>
+                     : L.elem == 2 ? k_gather_spmm_heads<2>
+                                   : k_gather_spmm_heads<1>,
+                     dim3(L.grid), dim3(NTS_BLOCK), 0, s->stream, ib.items,
+                     ib.counter, nbr, ew, in, out, nbr_start, f, L.G,
+                     L.pl.n_windows, heads, f / heads);
+  dbg_sync(s, "k_gather_spmm_heads");
 }
 }  // namespace
 
@@ -1550,6 +1905,46 @@ void nts_gather_by_src_from_dst_bf16(
   launch_gather(s, input, output, weight_backward, column_indices, row_offset,
                 dst_start, batch_size, edges, feature_size, with_weight,
                 NTS_KTAG_BWD, dst_end > dst_start ? dst_end - dst_start : 0);
+}
+
+void nts_gather_by_dst_from_src_heads(
+    nts_stream *s, const float *input, float *output,
+    const float *weight_forward, const nts_vid *row_indices,
+    const nts_vid *column_offset, nts_vid src_start, nts_vid src_end,
+    nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid batch_size,
+    nts_vid feature_size, nts_vid heads) {
+  (void)dst_start; (void)dst_end;
+  launch_gather_heads(s, "nts_gather_by_dst_from_src_heads", input, output,
+                      weight_forward, row_indices, column_offset, src_start,
+                      batch_size, edges, feature_size, heads, NTS_KTAG_FWD,
+                      src_end > src_start ? src_end - src_start : 0);
+}
+
+void nts_gather_by_src_from_dst_heads(
+    nts_stream *s, const float *input, float *output,
+    const float *weight_backward, const nts_vid *row_offset,
+    const nts_vid *column_indices, nts_vid src_start, nts_vid src_end,
+    nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid batch_size,
+    nts_vid feature_size, nts_vid heads) {
+  (void)src_start; (void)src_end;
+  launch_gather_heads(s, "nts_gather_by_src_from_dst_heads", input, output,
+                      weight_backward, column_indices, row_offset, dst_start,
+                      batch_size, edges, feature_size, heads, NTS_KTAG_BWD,
+                      dst_end > dst_start ? dst_end - dst_start : 0);
+}
+
+void nts_gather_plan_heads(nts_vid feature_size, nts_vid heads,
+                           unsigned alignment_bytes, nts_vid batch_size,
+                           nts_vid edges, int *lane_group, int *vector_width,
+                           int *grid) {
+  check_heads("nts_gather_plan_heads", feature_size, heads);
+  GatherLaunch L{};
+  if (batch_size && edges) /* else nothing is launched */
+    L = plan_gather_heads(feature_size, heads, alignment_bytes, batch_size,
+                          edges, gather_env());
+  if (lane_group) *lane_group = (int)L.G;
+  if (vector_width) *vector_width = L.elem;
+  if (grid) *grid = (int)L.grid;
 }
 
 void nts_gather_schedule(nts_stream *s, int schedule, int window_floats) {
@@ -1912,6 +2307,117 @@ void nts_edge_attention_forward(nts_stream *s, float *softmax_out,
                      softmax_out, nullptr, sums, softmax_out_perm, perm_pos,
                      nullptr, 0.f, nullptr, 1u);
   dbg_sync(s, "k_edge_att");
+}
+
+/* ---- multi-head entries (additive; see include/nts_hip.h) ---- */
+
+/* Prologue of the heads edge entries: as edge_items, with the edge count
+ * from the caller — no device-to-host copy, no stream synchronize. */
+static EdgeItems edge_items_known(nts_stream *s, const nts_vid *offset,
+                                  nts_vid batch, nts_vid edges) {
+  EdgeItems p;
+  if (!batch || !edges) return p;
+  p.edges = edges;
+  p.ib = &get_items(s, offset, batch, edges);
+  p.grid = items_grid(batch, edges);
+  return p;
+}
+
+/* the FLAT kernel forms take K a power of two <= 64 */
+static bool heads_flat(const nts_stream *s, uint32_t K) {
+  return !s->heads_general && K <= 64 && (K & (K - 1)) == 0;
+}
+
+void nts_heads_dbg_general(nts_stream *s, int enable) {
+  s->heads_general = enable != 0;
+}
+
+void nts_edge_attention_forward_heads(
+    nts_stream *s, float *softmax_out, float *softmax_out_perm,
+    const nts_vid *perm_pos, float *m_sum_out, const float *s_src_mirror,
+    const float *s_dst, const nts_vid *row_indices,
+    const nts_vid *mirror_index, float slope, const nts_vid *column_offset,
+    nts_vid batch_size, nts_vid edges, nts_vid heads) {
+  check_heads("nts_edge_attention_forward_heads", heads, heads);
+  const EdgeItems p = edge_items_known(s, column_offset, batch_size, edges);
+  if (!p.ib) return;
+  const ItemsBuf &ib = *p.ib;
+  float *sums = get_sums(s, (uint64_t)batch_size * heads);
+  Tic t(s, NTS_KTAG_EDGE);
+  if (heads == 1)
+    hipLaunchKernelGGL(k_edge_att_sum, dim3(p.grid), dim3(NTS_BLOCK), 0,
+                       s->stream, ib.items, ib.counter, softmax_out, m_sum_out,
+                       s_src_mirror, s_dst, row_indices, mirror_index, slope,
+                       sums);
+  else
+    hipLaunchKernelGGL(heads_flat(s, heads) ? k_edge_att_sum_heads<true>
+                                            : k_edge_att_sum_heads<false>,
+                       dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream, ib.items,
+                       ib.counter, softmax_out, m_sum_out, s_src_mirror, s_dst,
+                       row_indices, mirror_index, slope, sums, heads);
+  hipLaunchKernelGGL((k_edge_softmax_norm<false>), dim3(p.grid),
+                     dim3(NTS_BLOCK), 0, s->stream, ib.items, ib.counter,
+                     softmax_out, nullptr, sums, softmax_out_perm, perm_pos,
+                     nullptr, 0.f, nullptr, heads);
+  dbg_sync(s, "k_edge_att_heads");
+}
+
+void nts_edge_dot_heads(nts_stream *s, float *out, const float *dst_rows,
+                        const float *src_rows, const nts_vid *row_indices,
+                        const nts_vid *column_offset, nts_vid src_start,
+                        nts_vid batch_size, nts_vid edges,
+                        nts_vid feature_size, nts_vid heads) {
+  check_heads("nts_edge_dot_heads", feature_size, heads);
+  const EdgeItems p = edge_items_known(s, column_offset, batch_size, edges);
+  if (!p.ib) return;
+  const uint32_t C = feature_size / heads;
+  Tic t(s, NTS_KTAG_EDGE);
+  if (heads == 1)
+    hipLaunchKernelGGL(k_edge_dot, dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream,
+                       p.ib->items, p.ib->counter, out, dst_rows, src_rows,
+                       row_indices, src_start, feature_size);
+  else {
+    /* columns per lane: the widest of 4 / 2 / 1 dwords that divides C and
+     * that both row pointers' alignment permits; lanes per head C / R */
+    const GatherGeom geo = gather_geometry(
+        C, (uintptr_t)dst_rows | (uintptr_t)src_rows, sizeof(float));
+    const uint32_t R = (uint32_t)geo.elem, L = C / R;
+    if (!s->heads_general && (L & (L - 1)) == 0 && L <= 64) {
+      /* lane group of one row: f / R lanes, a power of two up to 64 */
+      uint32_t G = 64;
+      while (G / 2 >= feature_size / R) G /= 2;
+      hipLaunchKernelGGL(R == 4   ? k_edge_dot_heads_seg<4>
+                         : R == 2 ? k_edge_dot_heads_seg<2>
+                                  : k_edge_dot_heads_seg<1>,
+                         dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream,
+                         p.ib->items, p.ib->counter, out, dst_rows, src_rows,
+                         row_indices, src_start, feature_size, heads, C, G);
+    } else {
+      hipLaunchKernelGGL(k_edge_dot_heads, dim3(p.grid), dim3(NTS_BLOCK), 0,
+                         s->stream, p.ib->items, p.ib->counter, out, dst_rows,
+                         src_rows, row_indices, src_start, feature_size, heads,
+                         C);
+    }
+  }
+  dbg_sync(s, "k_edge_dot_heads");
+}
+
+void nts_weight_sum_heads(nts_stream *s, float *out, const float *weights,
+                          const nts_vid *offset, nts_vid batch_size,
+                          nts_vid edges, nts_vid heads) {
+  check_heads("nts_weight_sum_heads", heads, heads);
+  const EdgeItems p = edge_items_known(s, offset, batch_size, edges);
+  if (!p.ib) return;
+  Tic t(s, NTS_KTAG_EDGE);
+  if (heads == 1)
+    hipLaunchKernelGGL(k_weight_sum, dim3(p.grid), dim3(NTS_BLOCK), 0,
+                       s->stream, p.ib->items, p.ib->counter, out, weights);
+  else
+    hipLaunchKernelGGL(heads_flat(s, heads) ? k_weight_sum_heads<true>
+                                            : k_weight_sum_heads<false>,
+                       dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream,
+                       p.ib->items, p.ib->counter, out, weights, heads);
+  dbg_sync(s, "k_weight_sum_heads");
 }
 
 int nts_gather_by_src_from_dst_dot(nts_stream *s, const float *input,

@@ -19,6 +19,16 @@ single-GPU case: every vertex is its own master, mirror_index = identity):
 
 The per-edge attention value is a SCALAR (f=1), matching the exercised
 reference config: E×f edge tensors never materialize.
+
+Multi-head attention (GATLayer(..., heads=K), K > 1): the f = K*C columns are
+head-major (column c belongs to head c // C), attention scalars are [V, K],
+and every per-edge value (softmax, leaky-relu input, gradients) is [E, K]
+row-major.  Each head has its own softmax over a destination's in-edges and
+its weight scales only that head's C columns; the index lists are read once
+per pass and E×f messages still never materialize.  The chain is the one
+above through the *_heads entries of include/nts_hip.h, except that the CSR
+gather and the per-head edge dot run as two kernels (the fused gather-dot is
+single-head).  `attend` wraps forward/backward as a torch.autograd.Function.
 """
 import numpy as np
 import torch
@@ -31,7 +41,17 @@ from .ops import DeviceChunk, _u32_cuda
 class GATLayer:
     """Attention-weighted aggregation on one chunk (whole graph on 1 GPU)."""
 
-    def __init__(self, ch: Chunk, v: int, device):
+    def __init__(self, ch: Chunk, v: int, device, heads: int = 1,
+                 _heads_path: bool = False):
+        """heads = K attention heads over head-major column blocks.  With
+        heads == 1 the layer makes exactly the single-head calls.
+        _heads_path (private, for tools/bench_gat_heads.py) runs the heads
+        call chain at heads == 1 too: unfused CSR gather + edge dot."""
+        if not isinstance(heads, int) or heads < 1:
+            raise ValueError(f"heads must be a positive int, got {heads!r}")
+        self.heads = heads
+        self._heads_path = heads > 1 or _heads_path
+        self.v = v
         self.np_ch = ch
         self.ch = DeviceChunk(ch, device)
         self.stream = shim.Stream.wrap_torch_current()
@@ -74,7 +94,10 @@ class GATLayer:
 
     def forward(self, h: torch.Tensor, s_src: torch.Tensor,
                 s_dst: torch.Tensor, negative_slope: float = 0.2):
-        """h: [V,f] projected features; s_src/s_dst: [V] attention scalars."""
+        """h: [V,f] projected features; s_src/s_dst: [V] attention scalars
+        ([V, heads] for a multi-head layer)."""
+        if self._heads_path:
+            return self._forward_heads(h, s_src, s_dst, negative_slope)
         ch, st, E = self.ch, self.stream, self.E
         dev = h.device
         h = h.contiguous()
@@ -109,7 +132,10 @@ class GATLayer:
 
     def backward(self, grad_y: torch.Tensor, saved,
                  negative_slope: float = 0.2):
-        """Returns (grad_h from the aggregation, grad_s_src[V], grad_s_dst[V])."""
+        """Returns (grad_h from the aggregation, grad_s_src[V], grad_s_dst[V]);
+        the two scalar gradients are [V, heads] for a multi-head layer."""
+        if self._heads_path:
+            return self._backward_heads(grad_y, saved, negative_slope)
         ch, st, E = self.ch, self.stream, self.E
         dev = grad_y.device
         f = grad_y.shape[1]
@@ -163,3 +189,126 @@ class GATLayer:
         sst.weight_sum(g_src.data_ptr(), ge_csr.data_ptr(),
                        ch.row_offset.data_ptr(), ch.src_n)
         return grad_h, g_src[:, 0], g_dst[:, 0]
+
+    # ---- multi-head path (heads = K > 1) ----
+    @staticmethod
+    def _check_rows(name, t, rows, cols):
+        """The kernels take raw pointers: anything but a contiguous float32
+        device matrix of the expected shape raises before a launch."""
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+        if not t.is_cuda:
+            raise TypeError(f"{name} must be a device tensor")
+        if tuple(t.shape) != (rows, cols):
+            raise ValueError(
+                f"{name} must have shape ({rows}, {cols}), got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+
+    def _width(self, name, t):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"{name} must be a 2-d tensor")
+        f = int(t.shape[1])
+        if f < self.heads or f % self.heads != 0:
+            raise ValueError(
+                f"{name} has {f} columns, not a multiple of heads={self.heads}")
+        return f
+
+    def _forward_heads(self, h, s_src, s_dst, negative_slope):
+        """h: [V, K*C]; s_src/s_dst: [V, K].  Returns (y[V, K*C], saved)."""
+        ch, st, E, K = self.ch, self.stream, self.E, self.heads
+        f = self._width("h", h)
+        self._check_rows("h", h, ch.src_n, f)
+        self._check_rows("s_src", s_src, self.v, K)
+        self._check_rows("s_dst", s_dst, ch.dst_n, K)
+        dev = h.device
+        st.items_reuse(1)
+        s = torch.empty(E, K, device=dev)
+        s_csr = torch.empty(E, K, device=dev)
+        m_sum = torch.empty(E, K, device=dev)
+        st.edge_attention_forward_heads(
+            s.data_ptr(), s_csr.data_ptr(), self._inv_perm_u32.data_ptr(),
+            m_sum.data_ptr(), s_src.data_ptr(), s_dst.data_ptr(),
+            ch.row_indices.data_ptr(), self.mirror_index.data_ptr(),
+            negative_slope, ch.column_offset.data_ptr(), ch.dst_n, E, K)
+        y = torch.zeros(ch.dst_n, f, device=dev)
+        st.gather_by_dst_from_src_heads(
+            h.data_ptr(), y.data_ptr(), s.data_ptr(),
+            ch.row_indices.data_ptr(), ch.column_offset.data_ptr(),
+            ch.src_s, ch.src_e, ch.dst_s, ch.dst_e, E, ch.dst_n, f, K)
+        saved = {"h": h, "s": s, "s_csr": s_csr, "cached": s, "m_sum": m_sum}
+        return y, saved
+
+    def _backward_heads(self, grad_y, saved, negative_slope):
+        """Returns (grad_h[V, K*C], g_src[V, K], g_dst[V, K])."""
+        ch, st, E, K = self.ch, self.stream, self.E, self.heads
+        f = self._width("grad_y", grad_y)
+        self._check_rows("grad_y", grad_y, ch.dst_n, f)
+        if tuple(saved["h"].shape) != (ch.src_n, f):
+            raise ValueError("grad_y does not match the saved forward input")
+        dev = grad_y.device
+        st.items_reuse(1)
+        self.scalar_stream.items_reuse(1)
+        # the fused gather-dot is single-head: the CSR gather (weights in CSR
+        # order from the forward's dual emission) and the per-head dot
+        # gs[e, k] = grad_y[dst(e), head k] . h[src(e), head k] run apart
+        grad_h = torch.zeros(ch.src_n, f, device=dev)
+        st.gather_by_src_from_dst_heads(
+            grad_y.data_ptr(), grad_h.data_ptr(), saved["s_csr"].data_ptr(),
+            ch.row_offset.data_ptr(), ch.column_indices.data_ptr(),
+            ch.src_s, ch.src_e, ch.dst_s, ch.dst_e, E, ch.src_n, f, K)
+        gs = torch.empty(E, K, device=dev)
+        st.edge_dot_heads(gs.data_ptr(), grad_y.data_ptr(),
+                          saved["h"].data_ptr(), ch.row_indices.data_ptr(),
+                          ch.column_offset.data_ptr(), ch.src_s, ch.dst_n, E,
+                          f, K)
+        ge = torch.empty(E, K, device=dev)
+        ge_csr = torch.empty(E, K, device=dev)
+        st.edge_softmax_backward_fused(
+            ge.data_ptr(), ge_csr.data_ptr(), self._inv_perm_u32.data_ptr(),
+            gs.data_ptr(), saved["cached"].data_ptr(),
+            saved["m_sum"].data_ptr(), negative_slope,
+            ch.column_offset.data_ptr(), ch.dst_n, K, dst_sum=None)
+        # per-(vertex, head) sums of the edge gradient: by source over the
+        # CSR order, by destination over the CSC order (the softmax
+        # backward's own dst_sum emission is single-column)
+        sst = self.scalar_stream
+        g_src = torch.zeros(ch.src_n, K, device=dev)
+        sst.weight_sum_heads(g_src.data_ptr(), ge_csr.data_ptr(),
+                             ch.row_offset.data_ptr(), ch.src_n, E, K)
+        g_dst = torch.zeros(ch.dst_n, K, device=dev)
+        sst.weight_sum_heads(g_dst.data_ptr(), ge.data_ptr(),
+                             ch.column_offset.data_ptr(), ch.dst_n, E, K)
+        return grad_h, g_src, g_dst
+
+
+class _AttendFn(torch.autograd.Function):
+    """torch.autograd bridge over GATLayer.forward/backward (the GAT twin of
+    ops._AggregateFn): gradients flow to h, s_src and s_dst."""
+
+    @staticmethod
+    def forward(ctx, h, s_src, s_dst, layer, negative_slope):
+        y, saved = layer.forward(h.detach().contiguous(),
+                                 s_src.detach().contiguous(),
+                                 s_dst.detach().contiguous(), negative_slope)
+        ctx.layer, ctx.saved, ctx.slope = layer, saved, negative_slope
+        ctx.scalar_shapes = (s_src.shape, s_dst.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        grad_h, g_src, g_dst = ctx.layer.backward(grad_y.contiguous(),
+                                                  ctx.saved, ctx.slope)
+        return (grad_h, g_src.reshape(ctx.scalar_shapes[0]),
+                g_dst.reshape(ctx.scalar_shapes[1]), None, None)
+
+
+def attend(h: torch.Tensor, s_src: torch.Tensor, s_dst: torch.Tensor,
+           layer: GATLayer, negative_slope: float = 0.2) -> torch.Tensor:
+    """Autograd-aware attention-weighted aggregation on `layer`'s graph:
+    y = layer.forward(h, s_src, s_dst), differentiable in all three.  The
+    projections stay in torch, e.g. for K heads of C columns
+    s_src = (h.view(V, K, C) * a_src).sum(-1) with a_src of shape [K, C]."""
+    return _AttendFn.apply(h, s_src, s_dst, layer, negative_slope)

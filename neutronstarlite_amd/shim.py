@@ -103,6 +103,17 @@ def lib():
     l.nts_gather_by_src_from_dst_dot.restype = _i32
     l.nts_edge_attention_forward.argtypes = (
         [_vp] + [_vp] * 8 + [_c.c_float] + [_vp] + [_u32])
+    # per-head edge weights (multi-head GAT)
+    l.nts_gather_by_dst_from_src_heads.argtypes = (
+        [_vp] + [_vp] * 5 + [_u32] * 8)
+    l.nts_gather_by_src_from_dst_heads.argtypes = (
+        l.nts_gather_by_dst_from_src_heads.argtypes)
+    l.nts_gather_plan_heads.argtypes = [_u32] * 5 + [_vp] * 3
+    l.nts_edge_attention_forward_heads.argtypes = (
+        [_vp] + [_vp] * 8 + [_c.c_float] + [_vp] + [_u32] * 3)
+    l.nts_edge_dot_heads.argtypes = [_vp] + [_vp] * 5 + [_u32] * 5
+    l.nts_weight_sum_heads.argtypes = [_vp] + [_vp] * 3 + [_u32] * 3
+    l.nts_heads_dbg_general.argtypes = [_vp, _i32]
     l.nts_items_reuse.argtypes = [_vp, _i32]
     l.nts_weight_sum.argtypes = [_vp, _vp, _vp, _vp, _u32]
     l.nts_permute_f32.argtypes = [_vp, _vp, _vp, _vp, _i64]
@@ -140,6 +151,26 @@ def gather_plan_bf16(f, alignment, rows, batch, edges, schedule=0, window=0):
     lane (8, 4, 2 or 1), window in columns."""
     return _plan(lib().nts_gather_plan_bf16, f, alignment, rows, batch, edges,
                  schedule, window)
+
+
+def check_heads(f, heads):
+    """1 <= heads <= f and heads | f, else ValueError — the library itself
+    aborts on these, so every heads binding checks before it calls."""
+    if not (isinstance(heads, int) and isinstance(f, int)
+            and 1 <= heads <= f and f % heads == 0):
+        raise ValueError(
+            f"heads={heads!r} must be a positive divisor of the width {f!r}")
+
+
+def gather_plan_heads(f, heads, alignment, batch, edges):
+    """The launch decision of a heads gather (no device access): dict of
+    lane_group, vector_width (4, 2 or 1 dwords per lane) and grid."""
+    check_heads(f, heads)
+    names = ("lane_group", "vector_width", "grid")
+    out = [_i32(0) for _ in names]
+    lib().nts_gather_plan_heads(f, heads, alignment, batch, edges,
+                                *[_c.byref(o) for o in out])
+    return {n: o.value for n, o in zip(names, out)}
 
 
 _live_streams = weakref.WeakSet()
@@ -373,6 +404,57 @@ class Stream:
             self.h, _vp(softmax_out), _vp(softmax_out_perm), _vp(perm_pos),
             _vp(m_sum_out), _vp(s_src_mirror), _vp(s_dst), _vp(row_indices),
             _vp(mirror_index), slope, _vp(column_offset), batch)
+
+    # ---- per-head edge weights (multi-head GAT); heads is checked here,
+    # the library aborts on an invalid value ----
+    def gather_by_dst_from_src_heads(self, x_ptr, y_ptr, w_ptr,
+                                     row_indices_ptr, column_offset_ptr,
+                                     src_s, src_e, dst_s, dst_e, edges, batch,
+                                     f, heads):
+        """CSC gather with weights [edges, heads] in CSC edge order."""
+        check_heads(f, heads)
+        self._lib.nts_gather_by_dst_from_src_heads(
+            self.h, _vp(x_ptr), _vp(y_ptr), _vp(w_ptr), _vp(row_indices_ptr),
+            _vp(column_offset_ptr), src_s, src_e, dst_s, dst_e, edges, batch,
+            f, heads)
+
+    def gather_by_src_from_dst_heads(self, g_ptr, y_ptr, w_ptr,
+                                     row_offset_ptr, column_indices_ptr,
+                                     src_s, src_e, dst_s, dst_e, edges, batch,
+                                     f, heads):
+        """CSR gather with weights [edges, heads] in CSR edge order."""
+        check_heads(f, heads)
+        self._lib.nts_gather_by_src_from_dst_heads(
+            self.h, _vp(g_ptr), _vp(y_ptr), _vp(w_ptr), _vp(row_offset_ptr),
+            _vp(column_indices_ptr), src_s, src_e, dst_s, dst_e, edges, batch,
+            f, heads)
+
+    def edge_attention_forward_heads(self, softmax_out, softmax_out_perm,
+                                     perm_pos, m_sum_out, s_src_mirror, s_dst,
+                                     row_indices, mirror_index, slope,
+                                     column_offset, batch, edges, heads):
+        check_heads(heads, heads)
+        self._lib.nts_edge_attention_forward_heads(
+            self.h, _vp(softmax_out), _vp(softmax_out_perm), _vp(perm_pos),
+            _vp(m_sum_out), _vp(s_src_mirror), _vp(s_dst), _vp(row_indices),
+            _vp(mirror_index), slope, _vp(column_offset), batch, edges, heads)
+
+    def edge_dot_heads(self, out, dst_rows, src_rows, row_indices,
+                       column_offset, src_start, batch, edges, f, heads):
+        check_heads(f, heads)
+        self._lib.nts_edge_dot_heads(
+            self.h, _vp(out), _vp(dst_rows), _vp(src_rows), _vp(row_indices),
+            _vp(column_offset), src_start, batch, edges, f, heads)
+
+    def weight_sum_heads(self, out, weights, offset, batch, edges, heads):
+        check_heads(heads, heads)
+        self._lib.nts_weight_sum_heads(self.h, _vp(out), _vp(weights),
+                                       _vp(offset), batch, edges, heads)
+
+    def heads_dbg_general(self, enable):
+        """TEST/MEASUREMENT hook: the general forms of the heads edge
+        kernels even where a faster one exists for the shape."""
+        self._lib.nts_heads_dbg_general(self.h, 1 if enable else 0)
 
     def destroy(self):
         if self.h:

@@ -171,6 +171,71 @@ void nts_gather_plan_heads(nts_vid feature_size, nts_vid heads,
     unsigned alignment_bytes, nts_vid batch_size, nts_vid edges,
     int *lane_group, int *vector_width, int *grid);
 
+/* ---- max / min neighbour aggregation (additive, not in the reference ABI) ----
+ * The reference has these on the CPU only, over a materialised [E, f] edge
+ * tensor: SingleCPUDstAggregateOpMax/Min (core/ntsSingleCPUGraphOp.hpp:206-340)
+ * and DistAggregateDstMax/Min (core/ntsDistCPUGraphOp.hpp:306-440), built on
+ * nts_max / nts_min / nts_assign (core/ntsBaseOp.hpp:135-165) and write_max /
+ * write_min (dep/gemini/atomic.hpp:36-52).  Here it is a fused gather: the
+ * source rows are read through the CSC index once, the running best and its
+ * edge position stay in registers, and a value row and an arg row are written
+ * per destination; no [E, f] message tensor is built.
+ *   output[d,c] = max (min) over e in column_offset[d]..[d+1] of
+ *                 input[row_indices[e]-src_start, c]
+ *   arg[d,c]    = the chunk-local CSC edge position e that attains it
+ * Tie rule: the LOWEST e wins (the reference's serial write_max, strict <).
+ * The comparison is IEEE > / <, so -0 and +0 tie (a vertex split into several
+ * work items reports a zero extremum as +0); +-inf are ordinary values, and a
+ * vertex with at least one edge always gets a valid arg (the running best is
+ * seeded from the first edge).  NaN inputs are unspecified.  A destination
+ * with no in-edges gets output = 0 and arg = NTS_NO_EDGE.  The entry
+ * OVERWRITES all batch_size rows of both outputs (no += contract; the caller
+ * need not zero them).  NOT replicated: the reference zero-initialises its
+ * output and compares against it, so there a max over all-negative inputs
+ * yields 0 with no record (and its record array, `new VertexId(N)`, holds one
+ * element).
+ * row_indices == NULL is the reference's message form: input is [edges, f]
+ * and edge e reads row e.  fp32 rows only; arg is u32 [batch_size, f].
+ * Work items, NTS_SPLIT, the lane widths (4 / 2 dwords, else 4 strided; the
+ * alignment is that of input, output and arg together) and the grid are those
+ * of the scalar gather's native launch.  Only that launch runs:
+ * nts_gather_schedule requests are ignored and nts_gather_schedule_last
+ * reports NTS_SCHED_ITEM, as for the heads gathers.  A vertex split into
+ * several work items merges through a 64-bit atomic max on a key (ordered
+ * value, ~e) in a stream-owned u64 [batch_size, f] scratch, so the tie rule
+ * holds at every NTS_SPLIT and no row is read twice; the scratch is
+ * 8 * batch_size * feature_size bytes (about 1.1 GB at V = 232 965, f = 602),
+ * grows on demand like the stream's other scratch buffers, and is not
+ * allocated when edges <= NTS_SPLIT.  No device-to-host copy, no stream
+ * synchronize (but for scratch growth).  Timing tag NTS_KTAG_FWD. */
+enum nts_reduce_op { NTS_REDUCE_MAX = 0, NTS_REDUCE_MIN = 1 };
+#define NTS_NO_EDGE 0xffffffffu
+void nts_reduce_by_dst_from_src(nts_stream *s, int op, const float *input,
+    float *output, nts_vid *arg, const nts_vid *row_indices,
+    const nts_vid *column_offset, nts_vid src_start, nts_vid src_end,
+    nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid batch_size,
+    nts_vid feature_size);
+
+/* Its backward, a scatter with one lane per (d, c) element:
+ *   grad_input[row_indices[arg[d,c]]-src_start, c] += grad_output[d,c]
+ * wherever arg[d,c] != NTS_NO_EDGE; with row_indices == NULL the target row
+ * is arg[d,c] itself (the nts_assign message-grad form, no collisions).
+ * grad_input is caller-zeroed, as for every other += entry.  The adds are
+ * fp32 atomics, so the order of additions into one source element is not
+ * fixed.  About 12 * V * f bytes plus V * f atomics, against the 8 * E * f a
+ * CSR gather testing arg per edge would stream.  Timing tag NTS_KTAG_BWD. */
+void nts_reduce_backward(nts_stream *s, const float *grad_output,
+    const nts_vid *arg, const nts_vid *row_indices, nts_vid src_start,
+    float *grad_input, nts_vid batch_size, nts_vid feature_size);
+
+/* The forward launch decision without touching the device: lane group,
+ * vector width and grid are nts_gather_plan's for the request (0, -1) at
+ * rows = batch_size; scratch_bytes is the merge scratch the call needs (0
+ * when edges <= NTS_SPLIT: no vertex can then be split). */
+void nts_reduce_plan(nts_vid feature_size, unsigned alignment_bytes,
+    nts_vid batch_size, nts_vid edges, int *lane_group, int *vector_width,
+    int *grid, unsigned long long *scratch_bytes);
+
 /* Column schedule of the gather entry points, fp32 and bf16.  A gather task is (work
  * item, column window of `window_floats` floats); the schedule only changes
  * which task runs when, so for a vertex that is not split into several work

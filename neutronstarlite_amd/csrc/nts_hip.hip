@@ -20,6 +20,9 @@
  *    per call into a stream scratch buffer — two launches, ~0.05% of a
  *    gather); single-item vertices do plain read-modify-write stores,
  *    split (hub) vertices merge with device-scope fp32 atomics.
+ *  - Max / min aggregation is the same gather with compare-and-select in
+ *    place of fmaf and an edge position carried beside each running best;
+ *    split vertices merge through 64-bit atomic-max keys (k_gather_reduce).
  *  - Launches are grid-stride with ~2048 blocks of 256 threads (4 waves),
  *    plenty to fill 256 CUs across 8 XCDs; occupancy (8 waves/SIMD at this
  *    register budget) hides HBM latency.
@@ -107,6 +110,8 @@ struct nts_stream {
   int sched_last = 0, window_last = 0; /* what the last gather ran */
   float *sums_ws = nullptr;  /* per-dst reduction scratch (softmax) */
   uint64_t sums_cap = 0;
+  unsigned long long *keys_ws = nullptr; /* hub merge keys (max/min gather) */
+  uint64_t keys_cap = 0;
   bool heads_general = false; /* nts_heads_dbg_general: no heads fast paths */
 };
 
@@ -621,6 +626,228 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm_heads(
       for (; e < e_end; ++e) heads_edges_vec<ELEM, 1>(acc, g, e, col, K, head);
       store_acc<ELEM>(o, acc, ELEM, im.shared);
     }
+  }
+}
+
+/* ---- max / min gather with an arg record ---- */
+/* Sibling of k_gather_spmm<float, ELEM, false, false> on the same helpers
+ * (decode_task, load_item, load_lane): a lane group per (work item, slab),
+ * four row loads in flight.  fmaf becomes compare-and-select: each lane keeps
+ * best[] and the edge position bestE[] that attained it, seeded from the
+ * item's first edge and updated with a strict compare in edge order, so the
+ * lowest position wins a tie and -0 ties +0.  MSG: edge e reads row e (the
+ * message form, nbr == NULL).  An exclusive vertex stores its value and arg rows; a
+ * split one merges with a 64-bit atomic max on reduce_key (below). */
+template <bool IS_MIN>
+__device__ __forceinline__ bool reduce_beats(float x, float best) {
+  return IS_MIN ? x < best : x > best;
+}
+
+/* (ordered value << 32) | ~e: the monotone float -> uint map (flip all bits
+ * of a negative, set the sign bit of the rest; complemented for min) above
+ * the complemented edge position, so a 64-bit max picks the better value and,
+ * among equal ones, the lowest e.  -0 is folded onto +0 first, so the two tie
+ * as they do under the register path's IEEE compare.  Every key of a real
+ * edge is > 0: the high word of a non-NaN is, and so is ~e for e < 2^32 - 1. */
+template <bool IS_MIN>
+__device__ __forceinline__ unsigned long long reduce_key(float x, uint32_t e) {
+  uint32_t u = __float_as_uint(x);
+  if (u == 0x80000000u) u = 0u;
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  if (IS_MIN) u = ~u;
+  return ((unsigned long long)u << 32) | (0xffffffffu - e);
+}
+template <bool IS_MIN>
+__device__ __forceinline__ void reduce_unkey(unsigned long long key, float &x,
+                                             uint32_t &e) {
+  uint32_t u = (uint32_t)(key >> 32);
+  if (IS_MIN) u = ~u;
+  u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+  x = __uint_as_float(u);
+  e = 0xffffffffu - (uint32_t)key;
+}
+
+/* MSG (the message form) is a template parameter, not a test of g.nbr: a
+ * conditional index load inside the edge loop compiles to a branch and a full
+ * wait per edge, which serializes the four index loads of a batch */
+template <bool MSG>
+__device__ __forceinline__ const float *reduce_row(const GatherSrc<float> &g,
+                                                   uint32_t e, uint32_t col) {
+  const uint32_t row = MSG ? e : g.nbr[e] - g.nbr_start;
+  return g.in + (uint64_t)row * g.f + col;
+}
+
+/* K consecutive edges from e on, this lane's columns from col on: all K row
+ * loads issued before the first compare; SEED assigns instead (the item's
+ * first edge).  ELEM == 1: element j at p[j*G], live while col + j*G < fend
+ * (a dead element compares zeros and is never stored). */
+template <int ELEM, int K, bool IS_MIN, bool MSG, bool SEED, int N>
+__device__ __forceinline__ void reduce_edges(float (&best)[N],
+                                             uint32_t (&bestE)[N],
+                                             const GatherSrc<float> &g,
+                                             uint32_t e, uint32_t col,
+                                             uint32_t G, uint32_t fend) {
+  const float *p[K];
+  float x[K][N];
+#pragma unroll
+  for (int k = 0; k < K; ++k) p[k] = reduce_row<MSG>(g, e + k, col);
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    if constexpr (ELEM == 1) {
+#pragma unroll
+      for (int j = 0; j < N; ++j)
+        x[k][j] = (col + j * G < fend) ? p[k][j * G] : 0.f;
+    } else {
+      load_lane<ELEM>(p[k], x[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+      if (SEED || reduce_beats<IS_MIN>(x[k][j], best[j])) {
+        best[j] = x[k][j];
+        bestE[j] = e + k;
+      }
+}
+
+template <int ELEM, bool IS_MIN, bool MSG, int N>
+__device__ __forceinline__ void reduce_item(float (&best)[N],
+                                            uint32_t (&bestE)[N],
+                                            const GatherSrc<float> &g,
+                                            const Item &im, uint32_t col,
+                                            uint32_t G, uint32_t fend) {
+  uint32_t e = im.e0;
+  const uint32_t e_end = im.e0 + im.cnt;
+  reduce_edges<ELEM, 1, IS_MIN, MSG, true>(best, bestE, g, e, col, G, fend);
+  for (++e; e + 4 <= e_end; e += 4)
+    reduce_edges<ELEM, 4, IS_MIN, MSG, false>(best, bestE, g, e, col, G, fend);
+  for (; e < e_end; ++e)
+    reduce_edges<ELEM, 1, IS_MIN, MSG, false>(best, bestE, g, e, col, G, fend);
+}
+
+template <int ELEM, bool IS_MIN, bool MSG>
+__global__ __launch_bounds__(NTS_BLOCK) void k_gather_reduce(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ nbr, const float *__restrict__ in,
+    float *__restrict__ out, uint32_t *__restrict__ arg,
+    unsigned long long *__restrict__ keys, uint32_t nbr_start, uint32_t f,
+    uint32_t G, uint32_t n_slabs) {
+  constexpr int NSTR = (ELEM == 1) ? 4 : 1;
+  constexpr int N = ELEM * NSTR;
+  using uvec = uint32_t __attribute__((ext_vector_type(ELEM)));
+  const uint32_t n_items = *n_items_p;
+  const uint32_t glane = threadIdx.x & (G - 1);
+  const uint32_t tilef = G * N;
+  const GatherSrc<float> g{nbr, nullptr, in, nbr_start, f};
+  const GatherPlan pl{NTS_SCHED_ITEM, tilef, n_slabs, 1u};
+  const XcdClass xc;
+  const uint64_t total = (uint64_t)n_items * n_slabs;
+  const uint64_t stride = (gridDim.x * NTS_BLOCK) / G;
+  for (uint64_t t = (blockIdx.x * NTS_BLOCK + threadIdx.x) / G; t < total;
+       t += stride) {
+    const Task tk = decode_task<false>(pl, xc, t, n_items, f, tilef);
+    const uint32_t col = tk.fbase + glane * ELEM;
+    if (col >= f) continue;
+    const Item im = load_item(items, tk.it);
+    const uint64_t o = (uint64_t)im.v * f + col;
+    float best[N];
+    uint32_t bestE[N];
+    if constexpr (ELEM == 1) {
+      reduce_item<1, IS_MIN, MSG>(best, bestE, g, im, col, G, f);
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        if (col + j * G >= f) continue;
+        if (im.shared) {
+          atomicMax(&keys[o + j * G], reduce_key<IS_MIN>(best[j], bestE[j]));
+        } else {
+          out[o + j * G] = best[j];
+          arg[o + j * G] = bestE[j];
+        }
+      }
+    } else {
+      const int nv = (col + ELEM <= f) ? ELEM : (int)(f - col);
+      if (nv == ELEM) {
+        reduce_item<ELEM, IS_MIN, MSG>(best, bestE, g, im, col, G, f);
+      } else { /* ragged last lane: scalar columns */
+        for (uint32_t e = im.e0; e < im.e0 + im.cnt; ++e) {
+          const float *p = reduce_row<MSG>(g, e, col);
+          for (int j = 0; j < nv; ++j) {
+            const float x = p[j];
+            if (e == im.e0 || reduce_beats<IS_MIN>(x, best[j])) {
+              best[j] = x;
+              bestE[j] = e;
+            }
+          }
+        }
+      }
+      if (im.shared) {
+        for (int j = 0; j < nv; ++j)
+          atomicMax(&keys[o + j], reduce_key<IS_MIN>(best[j], bestE[j]));
+      } else if (nv == ELEM) {
+        fvec<ELEM> y;
+        uvec a;
+#pragma unroll
+        for (int j = 0; j < ELEM; ++j) {
+          y[j] = best[j];
+          a[j] = bestE[j];
+        }
+        *reinterpret_cast<fvec<ELEM> *>(out + o) = y;
+        *reinterpret_cast<uvec *>(arg + o) = a;
+      } else {
+        for (int j = 0; j < nv; ++j) {
+          out[o + j] = best[j];
+          arg[o + j] = bestE[j];
+        }
+      }
+    }
+  }
+}
+
+/* The row passes around k_gather_reduce, one wave per vertex.  Before it
+ * (DECODE = false): a vertex with no edges gets out = 0 and arg =
+ * NTS_NO_EDGE, a split one (degree > split, as in k_build_items) gets its key
+ * row zeroed — key 0 is below every real key.  After it (DECODE = true): the
+ * split vertices' key rows are decoded into out and arg. */
+template <bool DECODE, bool IS_MIN>
+__global__ void k_reduce_rows(const uint32_t *__restrict__ offset,
+                              uint32_t batch, uint32_t split,
+                              float *__restrict__ out,
+                              uint32_t *__restrict__ arg,
+                              unsigned long long *__restrict__ keys,
+                              uint32_t f) {
+  const WaveId w = wave_id();
+  for (uint32_t v = w.wave; v < batch; v += w.n_waves) {
+    const uint32_t deg = offset[v + 1] - offset[v];
+    const uint64_t o = (uint64_t)v * f;
+    if (DECODE) {
+      if (deg <= split) continue;
+      for (uint32_t c = w.lane; c < f; c += 64)
+        reduce_unkey<IS_MIN>(keys[o + c], out[o + c], arg[o + c]);
+    } else if (!deg) {
+      for (uint32_t c = w.lane; c < f; c += 64) {
+        out[o + c] = 0.f;
+        arg[o + c] = NTS_NO_EDGE;
+      }
+    } else if (keys && deg > split) {
+      for (uint32_t c = w.lane; c < f; c += 64) keys[o + c] = 0ull;
+    }
+  }
+}
+
+/* backward of the max / min gather: one lane per (d, c) element scatters its
+ * gradient to the source row its arg names (idx == NULL: row arg itself) */
+__global__ void k_reduce_backward(const float *__restrict__ grad_out,
+                                  const uint32_t *__restrict__ arg,
+                                  const uint32_t *__restrict__ idx,
+                                  uint32_t idx_start, float *grad_in,
+                                  uint64_t n, uint32_t f) {
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n;
+       i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t a = arg[i];
+    if (a == NTS_NO_EDGE) continue;
+    const uint32_t row = idx ? idx[a] - idx_start : a;
+    atomicAdd(&grad_in[(uint64_t)row * f + i % f], grad_out[i]);
   }
 }
 
@@ -1753,6 +1980,84 @@ void launch_gather_heads(nts_stream *s, const char *entry, const float *in,
                      L.pl.n_windows, heads, f / heads);
   dbg_sync(s, "k_gather_spmm_heads");
 }
+
+/* ---- max / min gather ---- */
+void check_reduce_op(const char *entry, int op) {
+  if (op != NTS_REDUCE_MAX && op != NTS_REDUCE_MIN) {
+    fprintf(stderr, "%s: op %d is neither NTS_REDUCE_MAX nor NTS_REDUCE_MIN\n",
+            entry, op);
+    abort();
+  }
+}
+
+/* Launch decision of a max / min gather: the scalar gather's native launch
+ * (request (0, -1)), plus the bytes of key scratch the hub merge needs —
+ * none while no vertex can be split.  Pure, like plan_gather. */
+struct ReduceLaunch {
+  GatherLaunch L;
+  uint64_t key_elems; /* u64 keys: batch * f, or 0 */
+};
+ReduceLaunch plan_reduce(uint32_t f, uintptr_t alignment, uint32_t batch,
+                         uint32_t edges, const GatherEnv &env) {
+  ReduceLaunch r{};
+  if (!batch || !edges || !f) return r; /* no gather is launched */
+  r.L = plan_gather(f, alignment, sizeof(float), batch, batch, edges,
+                    NTS_SCHED_ITEM, -1, env);
+  r.key_elems = edges > env.split ? (uint64_t)batch * f : 0;
+  return r;
+}
+
+/* stream-owned key scratch, grown on demand (not cleared: the row pre-pass
+ * zeroes what the launch uses) */
+unsigned long long *get_keys(nts_stream *s, uint64_t n) {
+  if (s->keys_cap < n) {
+    NTS_CHECK(hipStreamSynchronize(s->stream)); /* old buffer may be in use */
+    if (s->keys_ws) NTS_CHECK(hipFree(s->keys_ws));
+    NTS_CHECK(hipMalloc(&s->keys_ws, n * sizeof(unsigned long long)));
+    s->keys_cap = n;
+  }
+  return s->keys_ws;
+}
+
+void launch_reduce(nts_stream *s, int op, const float *in, float *out,
+                   uint32_t *arg, const uint32_t *nbr, const uint32_t *offset,
+                   uint32_t nbr_start, uint32_t batch, uint32_t edges,
+                   uint32_t f) {
+  check_reduce_op("nts_reduce_by_dst_from_src", op);
+  if (!batch || !f) return;
+  const ReduceLaunch R = plan_reduce(
+      f, (uintptr_t)in | (uintptr_t)out | (uintptr_t)arg, batch, edges,
+      gather_env());
+  ItemsBuf *ib = edges ? &get_items(s, offset, batch, edges) : nullptr;
+  unsigned long long *keys = R.key_elems ? get_keys(s, R.key_elems) : nullptr;
+  const uint32_t row_grid = grid_for((uint64_t)batch * 64);
+  s->sched_last = NTS_SCHED_ITEM;
+  s->window_last = (int)R.L.pl.wf;
+  Tic t(s, NTS_KTAG_FWD);
+  hipLaunchKernelGGL((k_reduce_rows<false, false>), dim3(row_grid),
+                     dim3(NTS_BLOCK), 0, s->stream, offset, batch, NTS_SPLIT,
+                     out, arg, keys, f);
+  if (ib) {
+    using Kernel = decltype(&k_gather_reduce<1, false, false>);
+#define NTS_K(E)                                                              \
+  {{k_gather_reduce<E, false, false>, k_gather_reduce<E, false, true>},       \
+   {k_gather_reduce<E, true, false>, k_gather_reduce<E, true, true>}}
+    /* [log2(dwords per lane)][min][message form] */
+    static const Kernel kernels[3][2][2] = {NTS_K(1), NTS_K(2), NTS_K(4)};
+#undef NTS_K
+    hipLaunchKernelGGL(
+        kernels[__builtin_ctz((unsigned)R.L.elem)][op == NTS_REDUCE_MIN]
+               [nbr == nullptr],
+        dim3(R.L.grid), dim3(NTS_BLOCK), 0, s->stream, ib->items, ib->counter,
+        nbr, in, out, arg, keys, nbr_start, f, R.L.G, R.L.pl.n_windows);
+  }
+  if (keys)
+    hipLaunchKernelGGL((op == NTS_REDUCE_MIN ? k_reduce_rows<true, true>
+                                             : k_reduce_rows<true, false>),
+                       dim3(row_grid), dim3(NTS_BLOCK), 0, s->stream, offset,
+                       batch, NTS_SPLIT, out, arg, keys, f);
+  dbg_sync(s, "k_gather_reduce");
+}
 }  // namespace
 
 /* ================= C-ABI ================= */
@@ -1784,6 +2089,7 @@ void nts_stream_destroy(nts_stream *s) {
     if (slot.counter) hipFree(slot.counter);
   }
   if (s->sums_ws) hipFree(s->sums_ws);
+  if (s->keys_ws) hipFree(s->keys_ws);
   if (s->owned) hipStreamDestroy(s->stream);
   delete s;
 }
@@ -1945,6 +2251,43 @@ void nts_gather_plan_heads(nts_vid feature_size, nts_vid heads,
   if (lane_group) *lane_group = (int)L.G;
   if (vector_width) *vector_width = L.elem;
   if (grid) *grid = (int)L.grid;
+}
+
+void nts_reduce_by_dst_from_src(nts_stream *s, int op, const float *input,
+                                float *output, nts_vid *arg,
+                                const nts_vid *row_indices,
+                                const nts_vid *column_offset, nts_vid src_start,
+                                nts_vid src_end, nts_vid dst_start,
+                                nts_vid dst_end, nts_vid edges,
+                                nts_vid batch_size, nts_vid feature_size) {
+  (void)src_end; (void)dst_start; (void)dst_end;
+  launch_reduce(s, op, input, output, arg, row_indices, column_offset,
+                src_start, batch_size, edges, feature_size);
+}
+
+void nts_reduce_backward(nts_stream *s, const float *grad_output,
+                         const nts_vid *arg, const nts_vid *row_indices,
+                         nts_vid src_start, float *grad_input,
+                         nts_vid batch_size, nts_vid feature_size) {
+  const uint64_t n = (uint64_t)batch_size * feature_size;
+  if (!n) return;
+  Tic t(s, NTS_KTAG_BWD);
+  hipLaunchKernelGGL(k_reduce_backward, dim3(grid_for(n)), dim3(NTS_BLOCK), 0,
+                     s->stream, grad_output, arg, row_indices, src_start,
+                     grad_input, n, feature_size);
+  dbg_sync(s, "k_reduce_backward");
+}
+
+void nts_reduce_plan(nts_vid feature_size, unsigned alignment_bytes,
+                     nts_vid batch_size, nts_vid edges, int *lane_group,
+                     int *vector_width, int *grid,
+                     unsigned long long *scratch_bytes) {
+  const ReduceLaunch R = plan_reduce(feature_size, alignment_bytes, batch_size,
+                                     edges, gather_env());
+  if (lane_group) *lane_group = (int)R.L.G;
+  if (vector_width) *vector_width = R.L.elem;
+  if (grid) *grid = (int)R.L.grid;
+  if (scratch_bytes) *scratch_bytes = R.key_elems * sizeof(unsigned long long);
 }
 
 void nts_gather_schedule(nts_stream *s, int schedule, int window_floats) {

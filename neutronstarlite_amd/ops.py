@@ -114,6 +114,102 @@ class HipEngine:
             ch.edge_size, ch.src_n, f, with_weight)
 
 
+    def csc_reduce(self, ch: DeviceChunk, x: torch.Tensor, y: torch.Tensor,
+                   arg: torch.Tensor, op="max", message=False):
+        """y[d] = element-wise max / min over d's in-edges of the x rows,
+        arg[d] = the CSC edge position that attains it (int32 storage of the
+        u32; shim.NO_EDGE, with y = 0, where d has no in-edge).  OVERWRITES y
+        and arg.  x is dense over ch's src range, or with message=True an
+        [edge_size, f] tensor in CSC edge order (edge e reads row e)."""
+        _check_reduce(x, y, arg)
+        rows = ch.edge_size if message else ch.src_n
+        f = y.shape[1]
+        assert x.shape == (rows, f) and y.shape[0] == ch.dst_n
+        self.stream.reduce_by_dst_from_src(
+            op, x.data_ptr(), y.data_ptr(), arg.data_ptr(),
+            None if message else ch.row_indices.data_ptr(),
+            ch.column_offset.data_ptr(), ch.src_s, ch.src_e, ch.dst_s,
+            ch.dst_e, ch.edge_size, ch.dst_n, f)
+
+    def reduce_backward(self, ch: DeviceChunk, grad_y: torch.Tensor,
+                        arg: torch.Tensor, gx: torch.Tensor, message=False):
+        """gx[src of edge arg[d,c], c] += grad_y[d,c] wherever arg is an edge
+        (gx dense over ch's src range and caller-zeroed; message=True: gx is
+        [edge_size, f] and the row is arg[d,c] itself)."""
+        _check_reduce(gx, grad_y, arg)
+        rows = ch.edge_size if message else ch.src_n
+        f = grad_y.shape[1]
+        assert gx.shape == (rows, f) and grad_y.shape[0] == ch.dst_n
+        self.stream.reduce_backward(
+            "max", grad_y.data_ptr(), arg.data_ptr(),
+            None if message else ch.row_indices.data_ptr(), ch.src_s,
+            gx.data_ptr(), ch.dst_n, f)
+
+
+def _check_reduce(rows: torch.Tensor, per_dst: torch.Tensor,
+                  arg: torch.Tensor):
+    """The checks of gather_entry for the max / min pair: fp32 device rows on
+    both sides, arg the int32 storage of the u32 record, same shape as the
+    per-destination tensor, everything contiguous.  Raises before a launch."""
+    if not (rows.is_cuda and per_dst.is_cuda and arg.is_cuda):
+        raise TypeError("max / min aggregation needs device tensors")
+    for name, t in (("source rows", rows), ("destination rows", per_dst)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+    if arg.dtype != torch.int32:
+        raise TypeError(f"arg must be int32 (u32 storage), got {arg.dtype}")
+    assert rows.is_contiguous() and per_dst.is_contiguous()
+    assert arg.is_contiguous() and arg.shape == per_dst.shape
+    assert rows.dim() == 2 and per_dst.dim() == 2
+
+
+class _ReduceFn(torch.autograd.Function):
+    """Autograd bridge over the max / min aggregation: forward records the
+    winning edge per (destination, column), backward routes each gradient to
+    that edge's source row (the tape contract of the reference's
+    SingleCPUDstAggregateOpMax/Min, core/ntsSingleCPUGraphOp.hpp:206-340)."""
+
+    @staticmethod
+    def forward(ctx, x, dchunk, engine, op, message):
+        ctx.dchunk, ctx.engine, ctx.message = dchunk, engine, message
+        ctx.rows = x.shape[0]
+        f = x.shape[1]
+        y = torch.empty(dchunk.dst_n, f, dtype=torch.float32, device=x.device)
+        arg = torch.empty(dchunk.dst_n, f, dtype=torch.int32, device=x.device)
+        engine.csc_reduce(dchunk, x.contiguous(), y, arg, op, message)
+        ctx.save_for_backward(arg)
+        ctx.mark_non_differentiable(arg)
+        return y, arg
+
+    @staticmethod
+    def backward(ctx, grad_y, _grad_arg):
+        (arg,) = ctx.saved_tensors
+        gx = torch.zeros(ctx.rows, grad_y.shape[1], dtype=torch.float32,
+                         device=grad_y.device)
+        ctx.engine.reduce_backward(ctx.dchunk, grad_y.contiguous(), arg, gx,
+                                   ctx.message)
+        return gx, None, None, None, None
+
+
+def aggregate_reduce(x: torch.Tensor, dchunk: "DeviceChunk",
+                     engine: "HipEngine", op="max", return_arg=False):
+    """Autograd-aware max / min neighbour aggregation (single-GPU chunk):
+    y[d, c] = max (min) over d's in-edges of x[src, c]; 0 where d has none.
+    Ties go to the lowest CSC edge position.  return_arg=True also returns
+    the arg record (int32 storage of u32 positions, shim.NO_EDGE = no edge)."""
+    y, arg = _ReduceFn.apply(x, dchunk, engine, op, False)
+    return (y, arg) if return_arg else y
+
+
+def edge_reduce(msg: torch.Tensor, dchunk: "DeviceChunk",
+                engine: "HipEngine", op="max", return_arg=False):
+    """The reference's DstAggregateOpMax/Min contract: msg is an [E, f] edge
+    tensor in CSC edge order, y[d] its element-wise max (min) over d's
+    in-edges, and the gradient of y[d, c] goes to msg[arg[d, c], c]."""
+    y, arg = _ReduceFn.apply(msg, dchunk, engine, op, True)
+    return (y, arg) if return_arg else y
+
+
 class _AggregateFn(torch.autograd.Function):
     """torch.autograd bridge over the fused aggregation: forward = CSC pull,
     backward = CSR push (the ntsGraphOp tape contract of
@@ -213,6 +309,37 @@ class MiniBatchFuseOp:
             grad_y.data_ptr(), gx.data_ptr(), self.w_bwd.data_ptr(),
             self.row_offset.data_ptr(), self.column_indices.data_ptr(),
             0, ly.n_src, 0, ly.n_dst, ly.e_size, ly.n_src, f, True)
+        return gx
+
+    def reduce_forward(self, x_compact: torch.Tensor, op="max"):
+        """Max / min pooling over the sampled in-edges (the GraphSAGE-pool
+        aggregator), local ids: returns (y, arg) as HipEngine.csc_reduce
+        writes them, arg holding positions in this layer's CSC edge order."""
+        ly = self.layer
+        f = x_compact.shape[1]
+        y = torch.empty(ly.n_dst, f, dtype=torch.float32,
+                        device=x_compact.device)
+        arg = torch.empty(ly.n_dst, f, dtype=torch.int32,
+                          device=x_compact.device)
+        _check_reduce(x_compact, y, arg)
+        assert x_compact.shape[0] == ly.n_src
+        self.engine.stream.reduce_by_dst_from_src(
+            op, x_compact.data_ptr(), y.data_ptr(), arg.data_ptr(),
+            self.row_indices.data_ptr(), self.column_offset.data_ptr(),
+            0, ly.n_src, 0, ly.n_dst, ly.e_size, ly.n_dst, f)
+        return y, arg
+
+    def reduce_backward(self, grad_y: torch.Tensor,
+                        arg: torch.Tensor) -> torch.Tensor:
+        ly = self.layer
+        f = grad_y.shape[1]
+        gx = torch.zeros(ly.n_src, f, dtype=torch.float32,
+                         device=grad_y.device)
+        _check_reduce(gx, grad_y, arg)
+        assert grad_y.shape[0] == ly.n_dst
+        self.engine.stream.reduce_backward(
+            "max", grad_y.data_ptr(), arg.data_ptr(),
+            self.row_indices.data_ptr(), 0, gx.data_ptr(), ly.n_dst, f)
         return gx
 
 

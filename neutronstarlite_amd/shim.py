@@ -114,6 +114,11 @@ def lib():
     l.nts_edge_dot_heads.argtypes = [_vp] + [_vp] * 5 + [_u32] * 5
     l.nts_weight_sum_heads.argtypes = [_vp] + [_vp] * 3 + [_u32] * 3
     l.nts_heads_dbg_general.argtypes = [_vp, _i32]
+    # max / min aggregation
+    l.nts_reduce_by_dst_from_src.argtypes = (
+        [_vp, _i32] + [_vp] * 5 + [_u32] * 7)
+    l.nts_reduce_backward.argtypes = [_vp] + [_vp] * 3 + [_u32, _vp] + [_u32] * 2
+    l.nts_reduce_plan.argtypes = [_u32] * 4 + [_vp] * 4
     l.nts_items_reuse.argtypes = [_vp, _i32]
     l.nts_weight_sum.argtypes = [_vp, _vp, _vp, _vp, _u32]
     l.nts_permute_f32.argtypes = [_vp, _vp, _vp, _vp, _i64]
@@ -171,6 +176,34 @@ def gather_plan_heads(f, heads, alignment, batch, edges):
     lib().nts_gather_plan_heads(f, heads, alignment, batch, edges,
                                 *[_c.byref(o) for o in out])
     return {n: o.value for n, o in zip(names, out)}
+
+
+# enum nts_reduce_op and NTS_NO_EDGE in include/nts_hip.h
+REDUCE_OPS = {"max": 0, "min": 1}
+NO_EDGE = 0xFFFFFFFF
+
+
+def reduce_op(op):
+    """The library's code of a max / min aggregation, else ValueError — the
+    library aborts on any other op, so every binding checks before it calls."""
+    if not isinstance(op, str) or op not in REDUCE_OPS:
+        raise ValueError(f"op={op!r} must be 'max' or 'min'")
+    return REDUCE_OPS[op]
+
+
+def reduce_plan(f, alignment, batch, edges, op="max"):
+    """The forward launch decision of a max / min gather (no device access):
+    dict of lane_group, vector_width, grid (those of gather_plan for the
+    request (0, -1)) and scratch_bytes, the merge scratch for split hubs."""
+    reduce_op(op)
+    names = ("lane_group", "vector_width", "grid")
+    out = [_i32(0) for _ in names]
+    scratch = _c.c_ulonglong(0)
+    lib().nts_reduce_plan(f, alignment, batch, edges,
+                          *[_c.byref(o) for o in out], _c.byref(scratch))
+    plan = {n: o.value for n, o in zip(names, out)}
+    plan["scratch_bytes"] = scratch.value
+    return plan
 
 
 _live_streams = weakref.WeakSet()
@@ -450,6 +483,30 @@ class Stream:
         check_heads(heads, heads)
         self._lib.nts_weight_sum_heads(self.h, _vp(out), _vp(weights),
                                        _vp(offset), batch, edges, heads)
+
+    # ---- max / min aggregation; op is checked here, the library aborts on
+    # an invalid value ----
+    def reduce_by_dst_from_src(self, op, x_ptr, y_ptr, arg_ptr,
+                               row_indices_ptr, column_offset_ptr, src_s,
+                               src_e, dst_s, dst_e, edges, batch, f):
+        """y = max / min over in-edges of x rows, arg = the CSC edge position
+        that attains it (NO_EDGE and y = 0 without edges).  Overwrites y and
+        arg.  row_indices_ptr None/0: x is [edges, f], edge e reads row e."""
+        code = reduce_op(op)
+        self._lib.nts_reduce_by_dst_from_src(
+            self.h, code, _vp(x_ptr), _vp(y_ptr), _vp(arg_ptr),
+            _vp(row_indices_ptr), _vp(column_offset_ptr), src_s, src_e, dst_s,
+            dst_e, edges, batch, f)
+
+    def reduce_backward(self, op, grad_y_ptr, arg_ptr, row_indices_ptr, src_s,
+                        grad_x_ptr, batch, f):
+        """grad_x[row_indices[arg] - src_s] += grad_y where arg != NO_EDGE
+        (row_indices_ptr None/0: row arg itself).  The scatter is the same for
+        both ops; op is taken so a wrong one fails here, not silently."""
+        reduce_op(op)
+        self._lib.nts_reduce_backward(
+            self.h, _vp(grad_y_ptr), _vp(arg_ptr), _vp(row_indices_ptr),
+            src_s, _vp(grad_x_ptr), batch, f)
 
     def heads_dbg_general(self, enable):
         """TEST/MEASUREMENT hook: the general forms of the heads edge

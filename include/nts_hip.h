@@ -82,7 +82,9 @@ void nts_memcpy_d2h(nts_stream *s, void *h, const void *d, long bytes, int sync)
  * There is no <=512-feature special case: one kernel handles any
  * feature_size by slab decomposition, and power-law columns are split into
  * bounded work items on device (see nts_hip.hip).  with_weight=0 replaces the
- * _without_weight twins.
+ * _without_weight twins.  input holds src_end - src_start rows (backward:
+ * dst_end - dst_start) of feature_size floats; a non-empty range lets the
+ * launch decision count the matrix and, for row staging below, copy it.
  * tensor_weight: in these two entries an edge weight is ONE fp32 scalar per
  * edge.  The reference's tensor_weight form, a weight row of feature_size
  * values per edge multiplied element by element (the _tensor_weight kernels
@@ -263,7 +265,8 @@ enum nts_gather_sched {
  * 0 included) and NTS_GATHER_WINDOW; NTS_GATHER_BLOCKS caps the grid of the
  * column-blocked launches (default 2^20: one task per lane group up to
  * there, which is what lets NTS_SCHED_PHASE keep one window live).
- * The library reads no other environment than these three, NTS_SPLIT (max
+ * The library reads no other environment than these three, the two of row
+ * staging (nts_gather_staging), NTS_SPLIT (max
  * edges per work item, 256), NTS_MAX_BLOCKS (grid cap of every other launch,
  * 8192) and NTS_DEBUG_SYNC (synchronize and check after every launch). */
 void nts_gather_schedule(nts_stream *s, int schedule, int window_floats);
@@ -291,6 +294,60 @@ void nts_gather_plan_bf16(nts_vid feature_size, unsigned alignment_bytes,
     nts_vid rows, nts_vid batch_size, nts_vid edges, int schedule_req,
     int window_req, int *schedule, int *window_floats, int *lane_group,
     int *vector_width, int *grid, int *blocked);
+
+/* ---- row staging of the fp32 gather entry points (additive) ----
+ * A gather's time follows lane slots and touched 128-byte lines, not payload
+ * bytes.  A matrix whose row pitch is no multiple of 16 bytes (f = 602: 2408
+ * bytes) runs narrow lanes and most of its windows straddle one more line.
+ * Staging copies the gathered matrix, input[0 .. src_end-src_start) (forward;
+ * dst_end-dst_start backward) x feature_size, once per call into a buffer at
+ * a row pitch `ld` of whole 128-byte lines (feature_size rounded up to 32
+ * floats; kernel k_repitch), and the gather reads that buffer with dwordx4
+ * lanes, addressing rows by ld instead of feature_size.  Output rows keep
+ * pitch feature_size; their vector width (4, 2 or 1 floats) follows the
+ * output's own alignment.  Every output element is still one lane's fmaf
+ * chain in edge order: for a vertex that is not split into several work
+ * items a staged gather is bit-identical to the unstaged one.
+ * The buffer belongs to the stream: it grows on demand, is reused by every
+ * later staged gather (all uses are ordered on the stream) and is freed by
+ * nts_stream_destroy.  The copy runs inside the gather's timing bracket: the
+ * NTS_KTAG_FWD / NTS_KTAG_BWD time includes it and the launch count per
+ * gather stays 1.  The copy fills the 4-float vector that holds the last
+ * column up with zeros, which is as far as the gather reads; pad columns
+ * past it are never read.  With no schedule request, a staged launch that
+ * meets the blocked-schedule conditions runs NTS_SCHED_PHASE over 128-float
+ * windows (the sweep in profiles/bench_lines.md); requests apply to the
+ * staged launch as to any other, windows rounded up to 4 floats.
+ * mode 0 = automatic: fp32 rows, row count known (src_end > src_start), ld !=
+ * feature_size, the blocked-schedule conditions (matrix beyond the Infinity
+ * Cache, more than one native slab), at least 64 edges per gathered row (the
+ * copy then costs under 3% of the gather's row bytes), and a staged matrix of
+ * at most 4 GiB.  mode 1 forces staging for any width and alignment whenever
+ * the row count is known and the 4 GiB cap holds (a view at a 4-byte offset
+ * goes from strided dwords to dwordx4); mode -1 never stages.  The bf16,
+ * heads (heads > 1), max/min and fused-dot gathers never stage.
+ * Environment, for sweeps, when the stream has no request: NTS_GATHER_STAGE
+ * (1 / -1) and NTS_GATHER_STAGE_PITCH (the unit in floats the pitch is
+ * rounded up to, default 32). */
+void nts_gather_staging(nts_stream *s, int mode);
+
+/* Whether the stream's most recent gather staged its rows, and the pitch in
+ * floats it staged them at (0 if it did not). */
+void nts_gather_staging_last(nts_stream *s, int *staged, int *pitch_floats);
+
+/* nts_gather_plan with the staging decision: element size of the rows (4, or
+ * 2 for bf16), alignment of the input and of the output pointer in bytes,
+ * and the requests as for nts_gather_schedule and nts_gather_staging.
+ * Returns whether the rows are staged, the row pitch the gather reads
+ * (feature_size if not), the launch that runs (as nts_gather_plan) and the
+ * floats per vector access of the output.  Touches no device; any out pointer
+ * may be NULL.  nts_gather_plan itself keeps reporting the unstaged launch. */
+void nts_gather_stage_plan(nts_vid feature_size, unsigned elem_bytes,
+    unsigned in_alignment_bytes, unsigned out_alignment_bytes, nts_vid rows,
+    nts_vid batch_size, nts_vid edges, int schedule_req, int window_req,
+    int stage_req, int *staged, int *pitch_floats, int *schedule,
+    int *window_floats, int *lane_group, int *vector_width, int *store_width,
+    int *grid, int *blocked);
 
 /* The two gather entry points decompose (offset, batch) into bounded
  * per-wavefront work items on device, rebuilt on every call into a

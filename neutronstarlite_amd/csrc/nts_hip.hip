@@ -15,6 +15,10 @@
  *    rows may be stored as bfloat16 (half the bytes per edge): the same
  *    kernel, loading 16 / 8 / 4 bytes per lane and widening in registers;
  *    weights, accumulators and output stay fp32.
+ *  - Row staging: a large, much re-read fp32 matrix whose row pitch is not
+ *    whole 128-byte lines (f = 602) is first copied into a stream-owned
+ *    buffer at such a pitch (k_repitch, ~1% of the gather); the gather reads
+ *    that with dwordx4 lanes (row pitch `ld` apart from the width f).
  *  - Power-law load balance: columns are decomposed on device into bounded
  *    work items of <= NTS_SPLIT consecutive edges of one vertex (rebuilt
  *    per call into a stream scratch buffer — two launches, ~0.05% of a
@@ -112,6 +116,11 @@ struct nts_stream {
   uint64_t sums_cap = 0;
   unsigned long long *keys_ws = nullptr; /* hub merge keys (max/min gather) */
   uint64_t keys_cap = 0;
+  float *stage_ws = nullptr; /* gathered rows re-pitched (row staging) */
+  uint64_t stage_cap = 0;    /* in floats */
+  int stage_req = 0;         /* nts_gather_staging: 0 auto, 1 force, -1 never */
+  bool staged_last = false;  /* whether the last gather staged its rows ... */
+  uint32_t stage_ld_last = 0; /* ... and at which pitch (floats) */
   bool heads_general = false; /* nts_heads_dbg_general: no heads fast paths */
 };
 
@@ -406,6 +415,7 @@ struct GatherSrc {
   const float *ew;
   const T *in;
   uint32_t nbr_start, f;
+  uint32_t ld; /* row pitch of `in` in elements: f, or wider for staged rows */
 };
 
 /* acc += w[k] * row k for K full vector lanes; fmaf order edge-major,
@@ -447,7 +457,7 @@ __device__ __forceinline__ void accum_edges(float (&acc)[N],
   float wv[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    p[k] = g.in + (uint64_t)(g.nbr[e + k] - g.nbr_start) * g.f + col;
+    p[k] = g.in + (uint64_t)(g.nbr[e + k] - g.nbr_start) * g.ld + col;
     wv[k] = WITH_W ? g.ew[e + k] : 1.0f;
   }
   if constexpr (ELEM == 1) fma_strided<N, K>(acc, p, wv, G, col, fend);
@@ -480,20 +490,31 @@ __device__ __forceinline__ void accum_item(float (&acc)[N],
 /* with NSTR=4 strided dwords (any f, any 4-byte alignment).  bf16: 8  */
 /* (16-byte load), 4 (8-byte), 2 (4-byte), or 1 with NSTR=4 strided    */
 /* 2-byte loads (any f, any 2-byte alignment).                         */
+/* ld = row pitch of `in` in elements (>= f): f itself, or the pitch of */
+/* the stream's staging buffer; rows of `out` always have pitch f.     */
+/* OV = floats per vector access of `out` (ELEM % OV == 0): the lane   */
+/* width follows `in` (its alignment and ld), OV follows `out` (its    */
+/* alignment and f).  The default is their common alignment, which is  */
+/* all an unstaged launch can use; a staged launch runs ELEM = 4 with  */
+/* OV = 4, 2 or 1.                                                     */
 /* Forward CSC:  nbr = row_indices   (global src),  out rows = dst.    */
 /* Backward CSR: nbr = column_indices (global dst), out rows = src.    */
 /* ------------------------------------------------------------------ */
-template <typename T, int ELEM, bool WITH_W, bool BLOCKED>
+constexpr int common_ov(int elem, int elem_bytes) {
+  return elem * elem_bytes >= 4 ? elem * elem_bytes / 4 : 1;
+}
+template <typename T, int ELEM, bool WITH_W, bool BLOCKED,
+          int OV = common_ov(ELEM, (int)sizeof(T))>
 __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm(
     const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
     const uint32_t *__restrict__ nbr, const float *__restrict__ ew,
     const T *__restrict__ in, float *__restrict__ out, uint32_t nbr_start,
-    uint32_t f, uint32_t G, GatherPlan pl) {
+    uint32_t f, uint32_t ld, uint32_t G, GatherPlan pl) {
   constexpr int NSTR = (ELEM == 1) ? 4 : 1;  /* strided sub-elements */
   const uint32_t n_items = *n_items_p;
   const uint32_t glane = threadIdx.x & (G - 1);
   const uint32_t tilef = G * ELEM * NSTR;
-  const GatherSrc<T> g{nbr, ew, in, nbr_start, f};
+  const GatherSrc<T> g{nbr, ew, in, nbr_start, f, ld};
   /* group index and stride: over the whole grid, or (XCD-affine) over the
    * workgroups of this block's class (every launch is NTS_BLOCK wide) */
   XcdClass xc;
@@ -521,21 +542,63 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm(
     } else {
       const int nv = (col + ELEM <= tk.fend)
                          ? ELEM : (col < tk.fend ? (int)(tk.fend - col) : 0);
-      if (nv == ELEM) {
+      /* A ragged last lane (nv < ELEM, staged rows of a width that ELEM does
+       * not divide) still loads whole vectors while they lie inside the row
+       * pitch: k_repitch fills the vector that holds column f - 1 up with
+       * zeros, and store_acc drops the elements past nv.  Taking the scalar
+       * loop instead makes its wave run every edge twice, the second time
+       * one dependent load at a time (measured under PHASE 256 at the
+       * headline shape: 75.9 ms/step against 50.3). */
+      if (nv > 0 && col + ELEM <= ld) {
         accum_item<ELEM, WITH_W>(acc, g, im, col, G, tk.fend);
       } else if (nv > 0) { /* ragged last lane: scalar columns */
         for (uint32_t e = im.e0; e < im.e0 + im.cnt; ++e) {
           const float w = WITH_W ? ew[e] : 1.0f;
-          const T *p = in + (uint64_t)(nbr[e] - nbr_start) * f + col;
+          const T *p = in + (uint64_t)(nbr[e] - nbr_start) * ld + col;
           for (int j = 0; j < nv; ++j) acc[j] = fmaf(w, to_f32(p[j]), acc[j]);
         }
       }
-      /* the pointers' common alignment is ELEM elements of T: that many
-       * bytes of `out` per vector access (bf16 ELEM=8: two dwordx4) */
-      constexpr int OV = ELEM * (int)sizeof(T) / (int)sizeof(float);
+      /* OV floats of `out` per vector access (bf16 ELEM=8: two dwordx4) */
       if (nv > 0)
         store_acc<ELEM, OV>(out + (uint64_t)im.v * f + col, acc, nv,
                             im.shared);
+    }
+  }
+}
+
+/* ---- row staging: the gathered matrix at a wider row pitch ---- */
+/* dst[r*ld + c] = src[r*f + c] for r < rows, c < f.  dst is 16-byte aligned
+ * and ld % 4 == 0, so every row of dst starts on a 16-byte boundary whatever
+ * f and the alignment of src are.  A wave per row, grid-stride: each lane
+ * moves 4 consecutive floats per step, so a wave reads 1 KiB of one source
+ * row and writes 1 KiB of one staged row, contiguous on both sides; the
+ * store is one dwordx4, the load 4/SV accesses of SV floats (SV = 4, 2 or 1
+ * from the alignment of src and f).  The vector that holds column f - 1 is
+ * filled up with zeros, which is as far as the gather reads (its lanes are
+ * vectors of 4 starting below f); pad columns past that vector are left
+ * unwritten and never read. */
+template <int SV>
+__global__ __launch_bounds__(NTS_BLOCK) void k_repitch(
+    const float *__restrict__ src, float *__restrict__ dst, uint32_t rows,
+    uint32_t f, uint32_t ld) {
+  const WaveId w = wave_id();
+  for (uint32_t r = w.wave; r < rows; r += w.n_waves) {
+    const float *s = src + (uint64_t)r * f;
+    float *d = dst + (uint64_t)r * ld;
+    for (uint32_t c = w.lane * 4; c < f; c += 64 * 4) {
+      fvec<4> v;
+      if (c + 4 <= f) {
+#pragma unroll
+        for (int k = 0; k < 4 / SV; ++k) {
+          const fvec<SV> x = *reinterpret_cast<const fvec<SV> *>(s + c + k * SV);
+#pragma unroll
+          for (int j = 0; j < SV; ++j) v[k * SV + j] = x[j];
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = (c + j < f) ? s[c + j] : 0.f;
+      }
+      *reinterpret_cast<fvec<4> *>(d + c) = v;
     }
   }
 }
@@ -558,7 +621,7 @@ __device__ __forceinline__ void heads_edges_vec(float (&acc)[ELEM],
   float wv[NE];
 #pragma unroll
   for (int k = 0; k < NE; ++k) {
-    p[k] = g.in + (uint64_t)(g.nbr[e + k] - g.nbr_start) * g.f + col;
+    p[k] = g.in + (uint64_t)(g.nbr[e + k] - g.nbr_start) * g.ld + col;
     wv[k] = g.ew[(uint64_t)(e + k) * K + head];
   }
   fma_vec<ELEM, NE>(acc, p, wv);
@@ -573,7 +636,7 @@ __device__ __forceinline__ void heads_edges_strided(
   const float *wrow[NE];
 #pragma unroll
   for (int k = 0; k < NE; ++k) {
-    p[k] = g.in + (uint64_t)(g.nbr[e + k] - g.nbr_start) * g.f + col;
+    p[k] = g.in + (uint64_t)(g.nbr[e + k] - g.nbr_start) * g.ld + col;
     wrow[k] = g.ew + (uint64_t)(e + k) * K;
   }
 #pragma unroll
@@ -594,7 +657,7 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm_heads(
   const uint32_t n_items = *n_items_p;
   const uint32_t glane = threadIdx.x & (G - 1);
   const uint32_t tilef = G * ELEM * NSTR;
-  const GatherSrc<float> g{nbr, ew, in, nbr_start, f};
+  const GatherSrc<float> g{nbr, ew, in, nbr_start, f, f};
   const GatherPlan pl{NTS_SCHED_ITEM, tilef, n_slabs, 1u};
   const XcdClass xc;
   const uint64_t total = (uint64_t)n_items * n_slabs;
@@ -674,7 +737,7 @@ template <bool MSG>
 __device__ __forceinline__ const float *reduce_row(const GatherSrc<float> &g,
                                                    uint32_t e, uint32_t col) {
   const uint32_t row = MSG ? e : g.nbr[e] - g.nbr_start;
-  return g.in + (uint64_t)row * g.f + col;
+  return g.in + (uint64_t)row * g.ld + col;
 }
 
 /* K consecutive edges from e on, this lane's columns from col on: all K row
@@ -739,7 +802,7 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gather_reduce(
   const uint32_t n_items = *n_items_p;
   const uint32_t glane = threadIdx.x & (G - 1);
   const uint32_t tilef = G * N;
-  const GatherSrc<float> g{nbr, nullptr, in, nbr_start, f};
+  const GatherSrc<float> g{nbr, nullptr, in, nbr_start, f, f};
   const GatherPlan pl{NTS_SCHED_ITEM, tilef, n_slabs, 1u};
   const XcdClass xc;
   const uint64_t total = (uint64_t)n_items * n_slabs;
@@ -1759,14 +1822,30 @@ constexpr uint32_t NTS_AUTO_WINDOW = 0;
  * >= 8 runs the native launch, as for any XCD request. */
 constexpr int NTS_AUTO_SCHED_BF16 = NTS_SCHED_XCD;
 constexpr uint32_t NTS_AUTO_WINDOW_BF16 = 302;
+/* The same for staged fp32 rows (dwordx4 lanes at a pitch of whole lines),
+ * from the sweep in profiles/bench_lines.md (Row staging), ms/step at the
+ * headline shape with the copy included, unstaged 57.0 in the same process:
+ * phase-major over 128-float windows (32 lanes) 44.4; PHASE 256, the native
+ * slab, 50.3; PHASE 304 52.5; ITEM 128 at the 2^20 grid 53.1; the native
+ * launch 54.8; XCD 2x304 53.8; XCD 4x152 57.6.  A pitch of 640 floats (20
+ * lines) instead of 608 (19): 44.7 / 50.1 / 54.0 / 59.0 for PHASE 128 /
+ * PHASE 256 / XCD 304 / XCD 152 - no better, so the pitch unit stays one
+ * line. */
+constexpr int NTS_AUTO_SCHED_STAGED = NTS_SCHED_PHASE;
+constexpr uint32_t NTS_AUTO_WINDOW_STAGED = 128;
 
 /* What the environment adds to a gather launch decision, read once like
  * NTS_SPLIT.  Sweep overrides: NTS_GATHER_SCHED forces a schedule (0 = the
  * current order), NTS_GATHER_WINDOW its window width in floats (unset/0 =
- * the schedule's default). */
+ * the schedule's default); NTS_GATHER_STAGE is the row staging request of
+ * streams that set none (1 force, -1 never, unset/0 automatic) and
+ * NTS_GATHER_STAGE_PITCH the unit in floats the staged pitch is rounded up
+ * to (a multiple of 4; unset/0 = NTS_STAGE_PITCH_UNIT). */
 struct GatherEnv {
   bool forced = false;
   int sched = 0, window = 0;
+  int stage = 0;                /* NTS_GATHER_STAGE: 0 auto, 1 force, -1 never */
+  uint32_t stage_pitch = 0;     /* NTS_GATHER_STAGE_PITCH, 0 = the default */
   uint32_t split, max_blocks, gather_blocks;
 };
 const GatherEnv &gather_env() {
@@ -1779,6 +1858,9 @@ const GatherEnv &gather_env() {
       const char *w = getenv("NTS_GATHER_WINDOW");
       if (w && *w) v.window = atoi(w);
     }
+    const char *st = getenv("NTS_GATHER_STAGE");
+    if (st && *st) v.stage = atoi(st) > 0 ? 1 : atoi(st) < 0 ? -1 : 0;
+    v.stage_pitch = env_u32("NTS_GATHER_STAGE_PITCH", 0);
     v.split = NTS_SPLIT;
     v.max_blocks = NTS_MAX_BLOCKS;
     v.gather_blocks = nts_gather_blocks();
@@ -1826,11 +1908,13 @@ struct GatherLaunch {
 };
 
 /* Pure: no HIP call, no stream.  rows == 0 (row count unknown to the caller)
- * never engages the automatic choice. */
-GatherLaunch plan_gather(uint32_t f, uintptr_t alignment, uint32_t elem_bytes,
-                         uint32_t rows, uint32_t batch, uint32_t edges,
-                         int sched_req, int window_req, const GatherEnv &env) {
-  const GatherGeom geo = gather_geometry(f, alignment, elem_bytes);
+ * never engages the automatic choice.  geo is the lane geometry the launch
+ * runs with: gather_geometry's, or that of staged rows (staged = true: the
+ * automatic choice is then NTS_AUTO_*_STAGED). */
+GatherLaunch plan_gather(const GatherGeom &geo, uint32_t f,
+                         uint32_t elem_bytes, uint32_t rows, uint32_t batch,
+                         uint32_t edges, int sched_req, int window_req,
+                         const GatherEnv &env, bool staged = false) {
   const uint32_t elem = geo.elem;
   const uint32_t unit = elem * geo.nstr; /* elements per lane */
   const uint32_t slabf = geo.G * unit;
@@ -1849,8 +1933,12 @@ GatherLaunch plan_gather(uint32_t f, uintptr_t alignment, uint32_t elem_bytes,
   } else if (n_slabs > 1 &&
              (uint64_t)rows * f * elem_bytes > NTS_BLOCK_MIN_BYTES &&
              edges / NTS_BLOCK_MIN_REUSE >= rows) {
-    sched = elem_bytes == 2 ? NTS_AUTO_SCHED_BF16 : NTS_AUTO_SCHED;
-    wf = elem_bytes == 2 ? NTS_AUTO_WINDOW_BF16 : NTS_AUTO_WINDOW;
+    sched = elem_bytes == 2 ? NTS_AUTO_SCHED_BF16
+            : staged        ? NTS_AUTO_SCHED_STAGED
+                            : NTS_AUTO_SCHED;
+    wf = elem_bytes == 2 ? NTS_AUTO_WINDOW_BF16
+         : staged        ? NTS_AUTO_WINDOW_STAGED
+                         : NTS_AUTO_WINDOW;
   }
   if (sched < NTS_SCHED_ITEM || sched > NTS_SCHED_XCD) sched = NTS_SCHED_ITEM;
   if (wf == 0) {
@@ -1896,6 +1984,110 @@ GatherLaunch plan_gather(uint32_t f, uintptr_t alignment, uint32_t elem_bytes,
       grid_for(bound_items * n_slabs * geo.G, env.max_blocks), false,
       GatherPlan{NTS_SCHED_ITEM, slabf, n_slabs, 1u}};
 }
+/* the unstaged launch: lanes from the pointers' common alignment */
+GatherLaunch plan_gather(uint32_t f, uintptr_t alignment, uint32_t elem_bytes,
+                         uint32_t rows, uint32_t batch, uint32_t edges,
+                         int sched_req, int window_req, const GatherEnv &env) {
+  return plan_gather(gather_geometry(f, alignment, elem_bytes), f, elem_bytes,
+                     rows, batch, edges, sched_req, window_req, env);
+}
+
+/* Row staging.  A gather's time follows lane slots and touched 128-byte
+ * lines, not payload bytes: at f = 602 a row is 2408
+ * bytes, 8-byte aligned and never a whole number of lines, so it runs
+ * dwordx2 lanes over five windows, most of which straddle an extra line.
+ * Staging copies the gathered matrix once per launch (k_repitch) into a
+ * stream-owned buffer whose rows start on a line and are a whole number of
+ * lines long; the gather then reads it with dwordx4 lanes, whatever the
+ * caller's width and alignment (automatic choice: NTS_AUTO_*_STAGED).
+ *
+ * Automatic staging engages for fp32 rows when
+ *  - rows is known and the staged pitch differs from f;
+ *  - the blocked-schedule conditions hold (more than one native slab, matrix
+ *    beyond NTS_BLOCK_MIN_BYTES): below them the rows stay cached and the
+ *    straddled lines cost no HBM traffic;
+ *  - edges / rows >= NTS_STAGE_MIN_REUSE.  The copy reads and writes each
+ *    row once where the gather reads it edges / rows times: 2 / reuse of the
+ *    gather's row bytes, 3% at 64, a quarter of the 12% that the padded
+ *    width is worth at the headline shape (f = 608 against 602 in
+ *    profiles/bench_lines.md), so the copy cannot eat the gain;
+ *  - the staged matrix is at most NTS_STAGE_MAX_BYTES. */
+constexpr uint32_t NTS_STAGE_MIN_REUSE = 64;
+/* Staged pitch: f rounded up to this many floats (one 128-byte line), so
+ * every row starts on a line and is a whole number of lines. */
+constexpr uint32_t NTS_STAGE_PITCH_UNIT = 32;
+/* Cap of the staging buffer, which lives as long as its stream: 4 GiB is
+ * seven times the headline matrix (567 MB) and 1.4% of the 288 GB of HBM; a
+ * matrix beyond it is one a caller partitions into chunks anyway.  It holds
+ * for forced requests too. */
+constexpr uint64_t NTS_STAGE_MAX_BYTES = 4ull << 30;
+
+/* Floats per vector access of `out` in a staged launch: from the output's
+ * alignment and f alone (the lanes are dwordx4 whatever the output is) */
+int stage_store_width(uint32_t f, uintptr_t out_alignment) {
+  if (f % 4 == 0 && out_alignment % 16 == 0) return 4;
+  if (f % 2 == 0 && out_alignment % 8 == 0) return 2;
+  return 1;
+}
+
+/* The whole decision of one gather: whether its rows are staged, at which
+ * pitch, and the launch that runs.  Pure, like plan_gather.  stage_req is the
+ * stream's nts_gather_staging request (0: the environment's, else automatic). */
+struct StagePlan {
+  bool staged;
+  uint32_t ld;  /* row pitch of the gathered rows in elements: f if unstaged */
+  int ov;       /* floats per vector access of `out` */
+  GatherLaunch L;
+};
+StagePlan plan_stage(uint32_t f, uint32_t elem_bytes, uintptr_t in_alignment,
+                     uintptr_t out_alignment, uint32_t rows, uint32_t batch,
+                     uint32_t edges, int sched_req, int window_req,
+                     int stage_req, const GatherEnv &env) {
+  const int req = stage_req ? stage_req : env.stage;
+  const uint32_t unit =
+      env.stage_pitch ? (env.stage_pitch + 3u) / 4u * 4u : NTS_STAGE_PITCH_UNIT;
+  const uint64_t ld = ((uint64_t)f + unit - 1) / unit * unit;
+  bool staged = elem_bytes == sizeof(float) && rows && req >= 0 &&
+                ld <= 0xffffffffu &&
+                (uint64_t)rows * ld * sizeof(float) <= NTS_STAGE_MAX_BYTES;
+  if (staged && req == 0) {
+    const GatherGeom native =
+        gather_geometry(f, in_alignment | out_alignment, elem_bytes);
+    const uint32_t slabf = native.G * native.elem * native.nstr;
+    staged = ld != f && f > slabf &&
+             (uint64_t)rows * f * elem_bytes > NTS_BLOCK_MIN_BYTES &&
+             edges / NTS_STAGE_MIN_REUSE >= rows;
+  }
+  if (!staged) {
+    const GatherLaunch L =
+        plan_gather(f, in_alignment | out_alignment, elem_bytes, rows, batch,
+                    edges, sched_req, window_req, env);
+    return StagePlan{false, f, common_ov(L.elem, (int)elem_bytes), L};
+  }
+  /* staged rows: dwordx4 lanes, the smallest lane group covering f */
+  GatherGeom geo{4, 1, 64};
+  while (geo.G / 2 >= (f + 3) / 4 && geo.G > 16) geo.G /= 2;
+  return StagePlan{true, (uint32_t)ld, stage_store_width(f, out_alignment),
+                   plan_gather(geo, f, elem_bytes, rows, batch, edges,
+                               sched_req, window_req, env, true)};
+}
+
+/* The stream's staging buffer, grown on demand.  One per stream suffices:
+ * the copy into it and the gather that reads it are ordered on the stream,
+ * and so is the next call's copy behind that gather.  It is rebuilt on every
+ * call: the rows are new data each time, and caching by pointer is unsound
+ * for the reason get_items gives. */
+float *get_stage(nts_stream *s, uint64_t n) {
+  if (s->stage_cap < n) {
+    NTS_CHECK(hipStreamSynchronize(s->stream)); /* old buffer may be in use */
+    if (s->stage_ws) NTS_CHECK(hipFree(s->stage_ws));
+    s->stage_ws = nullptr;
+    s->stage_cap = 0;
+    NTS_CHECK(hipMalloc(&s->stage_ws, n * sizeof(float)));
+    s->stage_cap = n;
+  }
+  return s->stage_ws;
+}
 
 /* T = row element type of `in` (float, or uint16_t for bfloat16) */
 template <typename T>
@@ -1905,9 +2097,10 @@ void launch_gather(nts_stream *s, const T *in, float *out, const float *ew,
                    uint32_t f, int with_weight, int tag, uint32_t rows) {
   if (!batch || !edges || !f) return;
   ItemsBuf &ib = get_items(s, offset, batch, edges);
-  const GatherLaunch L =
-      plan_gather(f, (uintptr_t)in | (uintptr_t)out, sizeof(T), rows, batch,
-                  edges, s->sched_req, s->window_req, gather_env());
+  const StagePlan P = plan_stage(f, sizeof(T), (uintptr_t)in, (uintptr_t)out,
+                                 rows, batch, edges, s->sched_req,
+                                 s->window_req, s->stage_req, gather_env());
+  const GatherLaunch &L = P.L;
   using Kernel = decltype(&k_gather_spmm<T, 1, false, false>);
 #define NTS_K(E)                                                              \
   {{k_gather_spmm<T, E, false, false>, k_gather_spmm<T, E, false, true>},     \
@@ -1920,11 +2113,42 @@ void launch_gather(nts_stream *s, const T *in, float *out, const float *ew,
 #undef NTS_K
   s->sched_last = (int)L.pl.sched;
   s->window_last = (int)L.pl.wf;
+  s->staged_last = P.staged;
+  s->stage_ld_last = P.staged ? P.ld : 0;
+  if constexpr (sizeof(T) == sizeof(float)) {
+    if (P.staged) {
+#define NTS_K(OV)                                                             \
+  {{k_gather_spmm<float, 4, false, false, OV>,                                \
+    k_gather_spmm<float, 4, false, true, OV>},                                \
+   {k_gather_spmm<float, 4, true, false, OV>,                                 \
+    k_gather_spmm<float, 4, true, true, OV>}}
+      /* dwordx4 lanes; indexed by log2(floats per access of `out`) */
+      static const Kernel staged_kernels[3][2][2] = {NTS_K(1), NTS_K(2),
+                                                     NTS_K(4)};
+#undef NTS_K
+      float *stage = get_stage(s, (uint64_t)rows * P.ld);
+      const int sv = stage_store_width(f, (uintptr_t)in); /* source side */
+      /* one bracket: the copy's cost is part of the gather's tag */
+      Tic t(s, tag);
+      hipLaunchKernelGGL(sv == 4   ? k_repitch<4>
+                         : sv == 2 ? k_repitch<2>
+                                   : k_repitch<1>,
+                         dim3(grid_for((uint64_t)rows * 64)), dim3(NTS_BLOCK),
+                         0, s->stream, in, stage, rows, f, P.ld);
+      hipLaunchKernelGGL(staged_kernels[__builtin_ctz((unsigned)P.ov)]
+                                       [with_weight != 0][L.blocked],
+                         dim3(L.grid), dim3(NTS_BLOCK), 0, s->stream, ib.items,
+                         ib.counter, nbr, ew, (const float *)stage, out,
+                         nbr_start, f, P.ld, L.G, L.pl);
+      dbg_sync(s, "k_gather_spmm (staged)");
+      return;
+    }
+  }
   Tic t(s, tag);
   hipLaunchKernelGGL(kernels[__builtin_ctz((unsigned)L.elem)]
                             [with_weight != 0][L.blocked],
                      dim3(L.grid), dim3(NTS_BLOCK), 0, s->stream, ib.items,
-                     ib.counter, nbr, ew, in, out, nbr_start, f, L.G, L.pl);
+                     ib.counter, nbr, ew, in, out, nbr_start, f, f, L.G, L.pl);
   dbg_sync(s, "k_gather_spmm");
 }
 
@@ -2090,6 +2314,7 @@ void nts_stream_destroy(nts_stream *s) {
   }
   if (s->sums_ws) hipFree(s->sums_ws);
   if (s->keys_ws) hipFree(s->keys_ws);
+  if (s->stage_ws) hipFree(s->stage_ws);
   if (s->owned) hipStreamDestroy(s->stream);
   delete s;
 }
@@ -2337,6 +2562,40 @@ void nts_gather_plan_bf16(nts_vid feature_size, unsigned alignment_bytes,
   report_plan(sizeof(uint16_t), feature_size, alignment_bytes, rows,
               batch_size, edges, schedule_req, window_req, schedule,
               window_floats, lane_group, vector_width, grid, blocked);
+}
+
+void nts_gather_staging(nts_stream *s, int mode) {
+  s->stage_req = mode > 0 ? 1 : mode < 0 ? -1 : 0;
+}
+
+void nts_gather_staging_last(nts_stream *s, int *staged, int *pitch_floats) {
+  if (staged) *staged = s->staged_last ? 1 : 0;
+  if (pitch_floats) *pitch_floats = (int)s->stage_ld_last;
+}
+
+void nts_gather_stage_plan(nts_vid feature_size, unsigned elem_bytes,
+                           unsigned in_alignment_bytes,
+                           unsigned out_alignment_bytes, nts_vid rows,
+                           nts_vid batch_size, nts_vid edges, int schedule_req,
+                           int window_req, int stage_req, int *staged,
+                           int *pitch_floats, int *schedule,
+                           int *window_floats, int *lane_group,
+                           int *vector_width, int *store_width, int *grid,
+                           int *blocked) {
+  StagePlan P{};
+  if (batch_size && edges && feature_size) /* else nothing is launched */
+    P = plan_stage(feature_size, elem_bytes, in_alignment_bytes,
+                   out_alignment_bytes, rows, batch_size, edges, schedule_req,
+                   window_req, stage_req, gather_env());
+  if (staged) *staged = P.staged ? 1 : 0;
+  if (pitch_floats) *pitch_floats = (int)P.ld;
+  if (schedule) *schedule = (int)P.L.pl.sched;
+  if (window_floats) *window_floats = (int)P.L.pl.wf;
+  if (lane_group) *lane_group = (int)P.L.G;
+  if (vector_width) *vector_width = P.L.elem;
+  if (store_width) *store_width = P.ov;
+  if (grid) *grid = (int)P.L.grid;
+  if (blocked) *blocked = P.L.blocked ? 1 : 0;
 }
 
 void nts_items_cache_clear(nts_stream *s) {

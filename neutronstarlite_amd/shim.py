@@ -81,6 +81,9 @@ def lib():
     l.nts_gather_schedule_last.argtypes = [_vp, _vp, _vp]
     l.nts_gather_plan.argtypes = [_u32] * 5 + [_i32] * 2 + [_vp] * 6
     l.nts_gather_plan_bf16.argtypes = l.nts_gather_plan.argtypes
+    l.nts_gather_staging.argtypes = [_vp, _i32]
+    l.nts_gather_staging_last.argtypes = [_vp, _vp, _vp]
+    l.nts_gather_stage_plan.argtypes = [_u32] * 7 + [_i32] * 3 + [_vp] * 9
     l.nts_deserialize_to_gpu.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _i32]
     l.nts_aggregate_comm_result.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _i32]
     l.nts_gather_rows.argtypes = [_vp, _vp, _vp, _vp, _u32, _u32, _u32]
@@ -156,6 +159,24 @@ def gather_plan_bf16(f, alignment, rows, batch, edges, schedule=0, window=0):
     lane (8, 4, 2 or 1), window in columns."""
     return _plan(lib().nts_gather_plan_bf16, f, alignment, rows, batch, edges,
                  schedule, window)
+
+
+def gather_stage_plan(f, in_alignment, out_alignment, rows, batch, edges,
+                      schedule=0, window=0, stage=0, elem_bytes=4):
+    """gather_plan with the row-staging decision (no device access): the
+    gather_plan dict of the launch that runs plus staged, pitch (row pitch
+    the gather reads, in elements) and store_width (floats per access of the
+    output).  stage is a request as for Stream.gather_staging."""
+    names = ("staged", "pitch", "schedule", "window", "lane_group",
+             "vector_width", "store_width", "grid", "blocked")
+    out = [_i32(0) for _ in names]
+    lib().nts_gather_stage_plan(f, elem_bytes, in_alignment, out_alignment,
+                                rows, batch, edges, schedule, window, stage,
+                                *[_c.byref(o) for o in out])
+    plan = {n: o.value for n, o in zip(names, out)}
+    plan["staged"] = bool(plan["staged"])
+    plan["blocked"] = bool(plan["blocked"])
+    return plan
 
 
 def check_heads(f, heads):
@@ -418,6 +439,19 @@ class Stream:
         self._lib.nts_gather_schedule_last(self.h, _c.byref(sched),
                                            _c.byref(window))
         return sched.value, window.value
+
+    def gather_staging(self, mode=0):
+        """Row staging of the following fp32 gathers: 0 automatic, 1 force,
+        -1 never."""
+        self._lib.nts_gather_staging(self.h, mode)
+
+    def gather_staging_last(self):
+        """(staged, pitch_floats) of the most recent gather; pitch 0 if it
+        did not stage."""
+        staged, pitch = _i32(0), _i32(0)
+        self._lib.nts_gather_staging_last(self.h, _c.byref(staged),
+                                          _c.byref(pitch))
+        return bool(staged.value), pitch.value
 
     def items_cache_clear(self):
         self._lib.nts_items_cache_clear(self.h)

@@ -17,7 +17,10 @@ bytes/s against each dtype's byte model, per step (forward + backward)
 --f 608 repeats the run at the padded width (16-byte rows: the 8-wide bf16
 lanes instead of the 2-wide ones of f=602).  --schedule / --window forward a
 request to the kernel for both dtypes; --sweep-bf16 "0:-1,1:0,1:64" times
-further bf16 requests (schedule:window) in the same alternation.  --rounds R
+further bf16 requests (schedule:window) in the same alternation, and
+--sweep-stage "1:0:0,1:1:128,-1:1:0" further fp32 requests with a row-staging
+mode in front (stage:schedule:window; 1 force, -1 never, 0 automatic; the
+first two variants run with staging off).  --rounds R
 repeats the whole alternation R times and reports every round, which is the
 run-to-run spread to judge the ratio by.
 
@@ -62,6 +65,9 @@ def main(argv=None):
     ap.add_argument("--window", type=int, default=0)
     ap.add_argument("--sweep-bf16", default="",
                     help="comma list of schedule:window requests, bf16 only")
+    ap.add_argument("--sweep-stage", default="",
+                    help="comma list of stage:schedule:window requests, "
+                         "fp32 only")
     ap.add_argument("--graph", default="reddit", choices=["reddit", "small"])
     args = ap.parse_args(argv)
 
@@ -100,19 +106,26 @@ def main(argv=None):
     gx = torch.zeros(v, f, device=dev)
 
     request = (args.schedule, args.window)
-    variants = [("fp32", request), ("bf16", request)]
+    # (dtype, schedule request, staging mode)
+    variants = [("fp32", request, -1), ("bf16", request, -1)]
     if args.sweep_bf16:
-        variants += [("bf16", parse_request(r))
+        variants += [("bf16", parse_request(r), -1)
                      for r in args.sweep_bf16.split(",")]
+    n_bf16 = len(variants)
+    if args.sweep_stage:
+        for r in args.sweep_stage.split(","):
+            stage, req = r.split(":", 1)
+            variants.append(("fp32", parse_request(req), int(stage)))
 
     def gather_ns():
         return (eng.stream.kernel_ns(shim.KTAG_FWD)
                 + eng.stream.kernel_ns(shim.KTAG_BWD))
 
-    def step(dtype, req):
+    def step(dtype, req, stage):
         """One forward + backward; returns (kernel ms, wall ms, what ran)."""
         x, g = inputs[dtype]
         eng.stream.gather_schedule(*req)
+        eng.stream.gather_staging(stage)
         torch.cuda.synchronize()
         k0, t = gather_ns(), time.perf_counter()
         y.zero_()
@@ -121,18 +134,20 @@ def main(argv=None):
         eng.csr_backward(dch, g, gx)
         torch.cuda.synchronize()
         wall = (time.perf_counter() - t) * 1e3
-        return (gather_ns() - k0) / 1e6, wall, eng.stream.gather_schedule_last()
+        ran = (eng.stream.gather_schedule_last()
+               + eng.stream.gather_staging_last()[1:])
+        return (gather_ns() - k0) / 1e6, wall, ran
 
     for _ in range(args.warmup):
-        for dtype, req in variants:
-            step(dtype, req)
+        for dtype, req, stage in variants:
+            step(dtype, req, stage)
 
     rounds = []
     for _ in range(args.rounds):
         acc = [[0.0, 0.0, None] for _ in variants]
         for _ in range(args.steps):
-            for i, (dtype, req) in enumerate(variants):
-                k, wall, ran = step(dtype, req)
+            for i, (dtype, req, stage) in enumerate(variants):
+                k, wall, ran = step(dtype, req, stage)
                 acc[i][0] += k
                 acc[i][1] += wall
                 acc[i][2] = ran
@@ -140,14 +155,14 @@ def main(argv=None):
                        for k, wall, ran in acc])
 
     def report(i):
-        dtype, req = variants[i]
+        dtype, req, stage = variants[i]
         ks = [r[i][0] for r in rounds]
         walls = [r[i][1] for r in rounds]
         k = sum(ks) / len(ks)
         model = model_bytes(v, e_total, f, 4 if dtype == "fp32" else 2)
         gbps = model / (k * 1e-3) / 1e9
-        return {"dtype": dtype, "request": list(req),
-                "ran": list(rounds[-1][i][2]),
+        return {"dtype": dtype, "request": list(req), "stage": stage,
+                "ran": list(rounds[-1][i][2]),  # schedule, window, pitch
                 "ms_per_step": round(k, 3),
                 "wall_ms_per_step": round(sum(walls) / len(walls), 3),
                 "rounds_ms_per_step": [round(x, 3) for x in ks],
@@ -164,7 +179,8 @@ def main(argv=None):
            "rounds_ratio": [round(r[1][0] / r[0][0], 4) for r in rounds],
            "model_ratio": round(bf16["model_bytes_per_step"]
                                 / fp32["model_bytes_per_step"], 4),
-           "sweep_bf16": [report(i) for i in range(2, len(variants))]}
+           "sweep_bf16": [report(i) for i in range(2, n_bf16)],
+           "sweep_stage": [report(i) for i in range(n_bf16, len(variants))]}
     print(json.dumps(out), flush=True)
 
 

@@ -266,7 +266,8 @@ enum nts_gather_sched {
  * column-blocked launches (default 2^20: one task per lane group up to
  * there, which is what lets NTS_SCHED_PHASE keep one window live).
  * The library reads no other environment than these three, the two of row
- * staging (nts_gather_staging), NTS_SPLIT (max
+ * staging (nts_gather_staging), the two of stripes (nts_gather_stripes),
+ * NTS_SPLIT (max
  * edges per work item, 256), NTS_MAX_BLOCKS (grid cap of every other launch,
  * 8192) and NTS_DEBUG_SYNC (synchronize and check after every launch). */
 void nts_gather_schedule(nts_stream *s, int schedule, int window_floats);
@@ -348,6 +349,85 @@ void nts_gather_stage_plan(nts_vid feature_size, unsigned elem_bytes,
     int stage_req, int *staged, int *pitch_floats, int *schedule,
     int *window_floats, int *lane_group, int *vector_width, int *store_width,
     int *grid, int *blocked);
+
+/* ---- stripes of a staged NTS_SCHED_PHASE launch (additive) ----
+ * Under NTS_SCHED_PHASE every XCD sweeps the same window, so all eight L2s
+ * cache pieces of the same hot rows.  With stripes the window of
+ * window_floats is cut into S = window_floats / stripe_floats stripes (S = 1,
+ * 2, 4 or 8); workgroups with blockIdx.x % 8 = c (one XCD under round-robin
+ * placement) own stripe c % S of every window, and the 8 / S classes of a
+ * stripe deal the work items among themselves.  The chip is still on one
+ * window at a time, but each L2 holds narrower pieces of S times as many
+ * rows.  A stripe is stripe_floats / 4 dwordx4 lanes (4 to 64), so a wave
+ * holds P = 256 / stripe_floats sub-groups: they share ONE work item and
+ * split its edges (sub-group j takes edges j, j + P, ..., four at a time),
+ * their partial sums are added by a fixed xor butterfly across the wave, and
+ * one sub-group stores.  A wave takes R consecutive tasks (item, window,
+ * stripe) of its class, window-major; R is the fewest that fit the grid cap
+ * NTS_GATHER_BLOCKS unless more are asked for.  The stripes of a short last
+ * window are dealt out over all eight classes task by task (no affinity in
+ * that window).  Kernel: k_gather_spmm_stripe, launched instead of
+ * k_gather_spmm inside the same timing bracket; launch counts and tags are
+ * unchanged.  nts_gather_schedule_last keeps reporting (NTS_SCHED_PHASE,
+ * window) and nts_gather_staging_last the pitch: stripes are an attribute of
+ * a PHASE launch, not a schedule of their own.
+ * Summation order: the sum of a vertex that is not split into several work
+ * items is fixed by (first edge, edge count, P), so it is bit-reproducible
+ * from run to run, but it is NOT bit-identical to the unstriped launch any
+ * more: P fmaf chains and a tree replace one chain.  Split vertices merge
+ * with atomics as before.
+ * stripe_floats 0 = automatic: fp32 rows, staged and NTS_SCHED_PHASE both by
+ * automatic choice (no schedule, window or staging request on the stream or
+ * in the environment), automatic width as recorded in profiles/bench_lines.md
+ * (Stripes).  -1 never.  > 0 forces that width on any staged launch that runs
+ * NTS_SCHED_PHASE or was asked to (a launch of a single window then keeps the
+ * window asked for); a width that does not cut the window into 1, 2, 4 or 8
+ * stripes of 4 to 64 lanes runs the unstriped launch.
+ * Environment, for sweeps, when the stream has no request:
+ * NTS_GATHER_STRIPE (floats; -1 never) and NTS_GATHER_STRIPE_RUN (R). */
+void nts_gather_stripes(nts_stream *s, int stripe_floats);
+
+/* Ask for at least this many tasks per wave in striped launches (0 = the
+ * fewest that fit the grid cap); a sweep parameter. */
+void nts_gather_stripes_run(nts_stream *s, int tasks_per_wave);
+
+/* Stripe width in floats and tasks per wave of the stream's most recent
+ * gather (0, 0 if it ran without stripes). */
+void nts_gather_stripes_last(nts_stream *s, int *stripe_floats,
+    int *tasks_per_wave);
+
+/* nts_gather_stage_plan with the stripe decision: its arguments plus the
+ * requests as for nts_gather_stripes and nts_gather_stripes_run.  Returns
+ * what that one returns for the launch that really runs (a striped launch
+ * reports its own grid, a multiple of 8, and its lanes per stripe as the lane
+ * group), plus the stripe width in floats (0 = no stripes), lanes per stripe,
+ * sub-groups per wave, stripes per window and tasks per wave.  Touches no
+ * device; any out pointer may be NULL.  nts_gather_stage_plan and
+ * nts_gather_plan keep reporting the launch without stripes. */
+void nts_gather_stripe_plan(nts_vid feature_size, unsigned elem_bytes,
+    unsigned in_alignment_bytes, unsigned out_alignment_bytes, nts_vid rows,
+    nts_vid batch_size, nts_vid edges, int schedule_req, int window_req,
+    int stage_req, int stripe_req, int run_req, int *staged,
+    int *pitch_floats, int *schedule, int *window_floats, int *lane_group,
+    int *vector_width, int *store_width, int *grid, int *blocked,
+    int *stripe_floats, int *stripe_lanes, int *subgroups, int *stripes,
+    int *tasks_per_wave);
+
+/* The kernel's task decode, evaluated on the host: for the plan of the same
+ * arguments and a launch that finds n_items work items, the tasks of `count`
+ * consecutive wave slots from first_slot on, where slot = ((workgroup * 4 +
+ * wave in the workgroup) * tasks_per_wave + run index).  item[k],
+ * first_column[k], column_bound[k] describe slot first_slot + k; first_column
+ * >= column_bound marks a slot without a task (also every slot past the grid,
+ * and every slot when the plan has no stripes).  Returns the number of slots
+ * that hold a task.  The device runs the very same function, so coverage is
+ * checkable without a GPU. */
+long long nts_gather_stripe_task(nts_vid feature_size, unsigned elem_bytes,
+    unsigned in_alignment_bytes, unsigned out_alignment_bytes, nts_vid rows,
+    nts_vid batch_size, nts_vid edges, int schedule_req, int window_req,
+    int stage_req, int stripe_req, int run_req, nts_vid n_items,
+    unsigned long long first_slot, unsigned long long count, nts_vid *item,
+    nts_vid *first_column, nts_vid *column_bound);
 
 /* The two gather entry points decompose (offset, batch) into bounded
  * per-wavefront work items on device, rebuilt on every call into a

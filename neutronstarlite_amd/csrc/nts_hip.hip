@@ -19,6 +19,12 @@
  *    whole 128-byte lines (f = 602) is first copied into a stream-owned
  *    buffer at such a pitch (k_repitch, ~1% of the gather); the gather reads
  *    that with dwordx4 lanes (row pitch `ld` apart from the width f).
+ *  - Stripes: such a staged launch cuts each column window into stripes
+ *    owned by XCD classes (blockIdx.x % 8), so the eight L2s stop caching
+ *    the same rows; the sub-groups of a wave share one work item, split its
+ *    edges and add their partial sums in a fixed butterfly, and a wave takes
+ *    a contiguous run of tasks (k_gather_spmm_stripe).  Unsplit vertices
+ *    stay bit-reproducible but are not bit-identical to k_gather_spmm.
  *  - Power-law load balance: columns are decomposed on device into bounded
  *    work items of <= NTS_SPLIT consecutive edges of one vertex (rebuilt
  *    per call into a stream scratch buffer — two launches, ~0.05% of a
@@ -122,6 +128,9 @@ struct nts_stream {
   bool staged_last = false;  /* whether the last gather staged its rows ... */
   uint32_t stage_ld_last = 0; /* ... and at which pitch (floats) */
   bool heads_general = false; /* nts_heads_dbg_general: no heads fast paths */
+  int stripe_req = 0;        /* nts_gather_stripes: 0 auto, -1 never, > 0 floats */
+  int stripe_run_req = 0;    /* nts_gather_stripes_run: 0 = from the grid cap */
+  uint32_t stripe_last = 0, stripe_run_last = 0; /* what the last gather ran */
 };
 
 namespace {
@@ -600,6 +609,166 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_repitch(
       }
       *reinterpret_cast<fvec<4> *>(d + c) = v;
     }
+  }
+}
+
+/* ---- stripes: edge-parallel waves over XCD-owned column stripes ---- */
+/* Sibling of k_gather_spmm<float, 4, WITH_W, true, OV> for staged rows under
+ * PHASE, on the same helpers (load_item, load_lane, store_acc, GatherSrc).
+ * A window of wf floats is cut into S = wf / sf stripes of sf floats; a
+ * stripe is GS = sf / ELEM lanes and a wave holds P = 64 / GS sub-groups.
+ * One wave runs one task = (work item, window, stripe) at a time: sub-group j
+ * takes the item's edges e0 + j, e0 + j + P, ... four at a time, so a wave
+ * step issues the index, weight and row loads of 4 P consecutive edges before
+ * its first fmaf.  The P partial sums are combined by an xor butterfly over
+ * the lane bits above log2(GS) (xor 32 first, GS last) and sub-group 0 stores
+ * once.  The order of the sum is fixed by (e0, cnt, P): unsplit vertices are
+ * bit-reproducible run to run, but NOT bit-identical to k_gather_spmm, whose
+ * output element is one fmaf chain.
+ * Workgroups of class blockIdx.x % 8 (one XCD under round-robin placement)
+ * own stripe class % S of every window, so that XCD's L2 caches sf-float
+ * pieces of wf / sf times as many rows as under plain PHASE; the 8 / S
+ * classes of a stripe deal the items among themselves.  Inside a class the
+ * tasks run window-major and every wave takes a contiguous run of R tasks,
+ * so launch order is task order and the whole chip stays on one window. */
+struct StripePlan {
+  uint32_t wf;        /* window width in floats */
+  uint32_t sf;        /* stripe width in floats: 4 * GS */
+  uint32_t S;         /* stripes per window: 1, 2, 4 or 8 */
+  uint32_t R;         /* consecutive tasks of its class per wave */
+  uint32_t n_windows; /* ceil(f / wf) */
+  uint32_t n_full;    /* leading windows in which all S stripes are live */
+  uint32_t last_live; /* live stripes of a short last window, else 0 */
+};
+
+/* a / b and a % b; the tasks of a class nearly always fit 32 bits */
+__host__ __device__ inline void stripe_divmod(uint64_t a, uint32_t b,
+                                              uint64_t &q, uint32_t &r) {
+  if (a <= 0xffffffffu) {
+    q = (uint32_t)a / b;
+    r = (uint32_t)a % b;
+  } else {
+    q = a / b;
+    r = (uint32_t)(a % b);
+  }
+}
+
+/* The task of (workgroup, wave in the workgroup, run index), or fbase >= fend
+ * for none.  Class c = block % 8 owns stripe c % S and, among the 8 / S
+ * classes of that stripe, the items c / S, c / S + 8 / S, ...: its tasks are
+ * window-major over the n_full full windows.  The tasks of a short last
+ * window (item-major over its live stripes) follow, dealt out over all eight
+ * classes task by task.  Depends on block and grid alone, never on
+ * placement; every live (item, window, stripe) comes out exactly once when
+ * grid / 8 * 4 * R covers the largest class (plan_stripe sees to that). */
+__host__ __device__ inline Task stripe_task(uint32_t grid, uint32_t n_items,
+                                            uint32_t f, const StripePlan &sp,
+                                            uint32_t block, uint32_t wave,
+                                            uint32_t run) {
+  const Task none{0u, 0u, 0u};
+  if (block >= grid || run >= sp.R) return none;
+  const uint32_t cls = block & 7u, cpw = 8u / sp.S;
+  const uint32_t stripe = cls % sp.S, sub = cls / sp.S;
+  const uint64_t t =
+      ((uint64_t)(block >> 3) * (NTS_BLOCK / 64) + wave) * sp.R + run;
+  const uint32_t ni = n_items > sub ? (n_items - sub + cpw - 1) / cpw : 0u;
+  const uint64_t own = (uint64_t)sp.n_full * ni;
+  uint32_t it, win, st;
+  if (t < own) {
+    uint64_t w;
+    uint32_t slot;
+    stripe_divmod(t, ni, w, slot);
+    win = (uint32_t)w;
+    it = sub + cpw * slot;
+    st = stripe;
+  } else {
+    if (!sp.last_live) return none;
+    const uint64_t u = cls + 8u * (t - own);
+    if (u >= (uint64_t)n_items * sp.last_live) return none;
+    uint64_t q;
+    stripe_divmod(u, sp.last_live, q, st);
+    it = (uint32_t)q;
+    win = sp.n_windows - 1;
+  }
+  const uint32_t fbase = win * sp.wf + st * sp.sf;
+  const uint32_t fend = fbase + sp.sf;
+  return Task{it, fbase, fend < f ? fend : f};
+}
+
+/* one wave step: 4 edges per sub-group, P apart.  FULL: all 4 P edges from
+ * eb on exist.  Otherwise the step is the item's tail: an edge slot past
+ * e_end reads the item's last edge instead (a valid address) and is left
+ * out of the sum */
+template <int ELEM, bool WITH_W, bool FULL>
+__device__ __forceinline__ void stripe_edges(float (&acc)[ELEM],
+                                             const GatherSrc<float> &g,
+                                             uint32_t eb, uint32_t e_end,
+                                             uint32_t sub, uint32_t P,
+                                             uint32_t col) {
+  uint32_t idx[4];
+  float wv[4];
+  bool live[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    uint32_t e = eb + k * P + sub;
+    live[k] = FULL || e < e_end;
+    if (!FULL) e = min(e, e_end - 1);
+    idx[k] = g.nbr[e];
+    wv[k] = WITH_W ? g.ew[e] : 1.0f;
+  }
+  float x[4][ELEM];
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    load_lane<ELEM>(g.in + (uint64_t)(idx[k] - g.nbr_start) * g.ld + col,
+                    x[k]);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (live[k]) {
+#pragma unroll
+      for (int j = 0; j < ELEM; ++j) acc[j] = fmaf(wv[k], x[k][j], acc[j]);
+    }
+}
+
+template <int ELEM, bool WITH_W, int OV, int GS>
+__global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm_stripe(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ nbr, const float *__restrict__ ew,
+    const float *__restrict__ in, float *__restrict__ out, uint32_t nbr_start,
+    uint32_t f, uint32_t ld, StripePlan sp) {
+  static_assert(GS >= 4 && GS <= 64 && (GS & (GS - 1)) == 0, "lanes a stripe");
+  constexpr uint32_t P = 64 / GS;
+  const uint32_t n_items = *n_items_p;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t sub = lane / GS, glane = lane % GS;
+  const uint32_t wave = threadIdx.x >> 6;
+  const GatherSrc<float> g{nbr, ew, in, nbr_start, f, ld};
+  for (uint32_t run = 0; run < sp.R; ++run) {
+    const Task tk =
+        stripe_task(gridDim.x, n_items, f, sp, blockIdx.x, wave, run);
+    if (tk.fbase >= tk.fend) continue; /* the same for the whole wave */
+    const Item im = load_item(items, tk.it);
+    const uint32_t col = tk.fbase + glane * ELEM;
+    const int nv = (col + ELEM <= tk.fend)
+                       ? ELEM : (col < tk.fend ? (int)(tk.fend - col) : 0);
+    float acc[ELEM] = {};
+    /* col and ld are multiples of ELEM and col < f <= ld: a live lane's
+     * vector lies inside the row pitch, and k_repitch has filled the vector
+     * that holds column f - 1 up with zeros (the ragged last lane) */
+    if (nv > 0) {
+      const uint32_t e_end = im.e0 + im.cnt;
+      uint32_t eb = im.e0;
+      for (; eb + 4 * P <= e_end; eb += 4 * P)
+        stripe_edges<ELEM, WITH_W, true>(acc, g, eb, e_end, sub, P, col);
+      if (eb < e_end)
+        stripe_edges<ELEM, WITH_W, false>(acc, g, eb, e_end, sub, P, col);
+    }
+    /* whole-wave butterfly (lanes past the stripe's columns add zeros) */
+#pragma unroll
+    for (int w = 32; w >= GS; w >>= 1)
+#pragma unroll
+      for (int j = 0; j < ELEM; ++j) acc[j] += __shfl_xor(acc[j], w, 64);
+    if (sub == 0 && nv > 0)
+      store_acc<ELEM, OV>(out + (uint64_t)im.v * f + col, acc, nv, im.shared);
   }
 }
 
@@ -1840,12 +2009,17 @@ constexpr uint32_t NTS_AUTO_WINDOW_STAGED = 128;
  * the schedule's default); NTS_GATHER_STAGE is the row staging request of
  * streams that set none (1 force, -1 never, unset/0 automatic) and
  * NTS_GATHER_STAGE_PITCH the unit in floats the staged pitch is rounded up
- * to (a multiple of 4; unset/0 = NTS_STAGE_PITCH_UNIT). */
+ * to (a multiple of 4; unset/0 = NTS_STAGE_PITCH_UNIT); NTS_GATHER_STRIPE is
+ * the stripe request of streams that set none (floats; -1 never, unset/0
+ * automatic) and NTS_GATHER_STRIPE_RUN the tasks per wave of a striped launch
+ * (unset/0 = the fewest that fit the grid cap). */
 struct GatherEnv {
   bool forced = false;
   int sched = 0, window = 0;
   int stage = 0;                /* NTS_GATHER_STAGE: 0 auto, 1 force, -1 never */
   uint32_t stage_pitch = 0;     /* NTS_GATHER_STAGE_PITCH, 0 = the default */
+  int stripe = 0;               /* NTS_GATHER_STRIPE: floats, -1 never, 0 auto */
+  uint32_t stripe_run = 0;      /* NTS_GATHER_STRIPE_RUN, 0 = from the grid cap */
   uint32_t split, max_blocks, gather_blocks;
 };
 const GatherEnv &gather_env() {
@@ -1861,6 +2035,9 @@ const GatherEnv &gather_env() {
     const char *st = getenv("NTS_GATHER_STAGE");
     if (st && *st) v.stage = atoi(st) > 0 ? 1 : atoi(st) < 0 ? -1 : 0;
     v.stage_pitch = env_u32("NTS_GATHER_STAGE_PITCH", 0);
+    const char *sp = getenv("NTS_GATHER_STRIPE");
+    if (sp && *sp) v.stripe = atoi(sp) < 0 ? -1 : atoi(sp);
+    v.stripe_run = env_u32("NTS_GATHER_STRIPE_RUN", 0);
     v.split = NTS_SPLIT;
     v.max_blocks = NTS_MAX_BLOCKS;
     v.gather_blocks = nts_gather_blocks();
@@ -2072,6 +2249,107 @@ StagePlan plan_stage(uint32_t f, uint32_t elem_bytes, uintptr_t in_alignment,
                                sched_req, window_req, env, true)};
 }
 
+/* Stripes (k_gather_spmm_stripe) are an attribute of a staged PHASE launch.
+ * Automatic stripe width in floats (0 = none) and the least tasks per wave
+ * of an automatic launch, from the sweep in profiles/bench_lines.md
+ * (Stripes), kernel ms per forward + backward step at the headline shape,
+ * the launch without stripes 44.7 to 45.1 in the same processes.  Window 128,
+ * width / R: 128 (two sub-groups, no XCD split) 42.9 / 1, 40.0 / 4, 39.9 / 8,
+ * 40.4 / 16; 64 (two stripes) 45.0 / 1, 37.4 / 4, 36.5 / 8, 36.0 / 16,
+ * 36.3 / 32, 37.6 / 64; 32 (four) 53.6 / 1, 42.2 / 4, 38.8 / 8, 36.9 / 16,
+ * 36.4 / 32, 38.6 / 64; 16 (eight) 74.1 / 4, 69.1 / 8.  Window 256: 64
+ * (four stripes) 35.3 / 16, 35.5 / 32; 32 (eight) 42.2 / 4, 40.7 / 32; 128
+ * (two) 39.8 / 8.  Window 256 / 64 is 0.7 ms below window 128 / 64 in both
+ * sweeps that held the two; the window stays the 128 of the staged launch. */
+constexpr uint32_t NTS_AUTO_STRIPE_STAGED = 64;
+constexpr uint32_t NTS_AUTO_STRIPE_RUN = 16;
+
+/* The stripe decision on top of a staged launch decision.  Pure, like
+ * plan_stage.  stripe_req is the stream's nts_gather_stripes request (0: the
+ * environment's, else automatic), run_req its tasks per wave (0: the
+ * environment's, else NTS_AUTO_STRIPE_RUN for an automatic launch and the
+ * fewest that fit the grid cap for a forced width; never fewer than fit).
+ * Automatic: fp32 rows, staged by automatic choice, PHASE by automatic choice
+ * (no schedule, window or staging request from the stream or the environment,
+ * which implies the blocked-schedule conditions), and the automatic width
+ * cuts the window into 1, 2, 4 or 8 stripes.  A request > 0 forces that width
+ * on any staged launch that runs PHASE or was asked to (a width of one window
+ * runs the native launch unstriped; striped it keeps the window asked for);
+ * a width that does not cut the window into 1, 2, 4 or 8 stripes of 4 to 64
+ * dwordx4 lanes runs without stripes. */
+struct StripeLaunch {
+  bool on;
+  uint32_t Gs, P, grid; /* lanes per stripe, sub-groups per wave, workgroups */
+  StripePlan sp;
+};
+StripeLaunch plan_stripe(const StagePlan &P, uint32_t f, uint32_t elem_bytes,
+                         uint32_t batch, uint32_t edges, int sched_req,
+                         int window_req, int stage_req, int stripe_req,
+                         int run_req, const GatherEnv &env) {
+  StripeLaunch off{};
+  const int req = stripe_req ? stripe_req : env.stripe;
+  if (req < 0 || !P.staged || elem_bytes != sizeof(float)) return off;
+  /* the schedule request as plan_gather reads it */
+  int rs = 0;
+  uint32_t rw = 0;
+  bool asked = false;
+  if (sched_req || window_req) {
+    asked = true;
+    rs = sched_req;
+    rw = window_req > 0 ? (uint32_t)window_req : 0;
+  } else if (env.forced) {
+    asked = true;
+    rs = env.sched;
+    rw = env.window > 0 ? (uint32_t)env.window : 0;
+  }
+  const bool phase = P.L.blocked && P.L.pl.sched == NTS_SCHED_PHASE;
+  uint32_t sf, wf = P.L.pl.wf;
+  if (req == 0) {
+    if (asked || stage_req || env.stage || !phase) return off;
+    sf = NTS_AUTO_STRIPE_STAGED;
+  } else {
+    if (!phase && !(asked && rs == NTS_SCHED_PHASE)) return off;
+    if (!P.L.blocked && rw) wf = (rw + 3u) / 4u * 4u;
+    sf = (uint32_t)req;
+  }
+  if (!sf || sf % 4u || wf % sf) return off;
+  const uint32_t S = wf / sf, Gs = sf / 4u;
+  if (S != 1 && S != 2 && S != 4 && S != 8) return off;
+  if (Gs < 4 || Gs > 64 || (Gs & (Gs - 1))) return off;
+  const uint32_t cap8 = env.gather_blocks & ~7u;
+  if (cap8 < 8) return off;
+
+  StripePlan sp{};
+  sp.wf = wf;
+  sp.sf = sf;
+  sp.S = S;
+  sp.n_windows = (f + wf - 1) / wf;
+  const uint32_t last_w = f - (sp.n_windows - 1) * wf;
+  const uint32_t last_live = (last_w + sf - 1) / sf;
+  sp.n_full = last_live == S ? sp.n_windows : sp.n_windows - 1;
+  sp.last_live = last_live == S ? 0u : last_live;
+  /* the largest class: items dealt among the 8 / S classes of a stripe, the
+   * short window's tasks among all eight */
+  const uint64_t bound_items = (uint64_t)batch + edges / env.split + 1;
+  const uint32_t cpw = 8u / S;
+  const uint64_t tasks = (uint64_t)sp.n_full * ((bound_items + cpw - 1) / cpw) +
+                         (bound_items * sp.last_live + 7u) / 8u;
+  const uint64_t waves_cap = (uint64_t)(cap8 / 8u) * (NTS_BLOCK / 64);
+  uint64_t R = (tasks + waves_cap - 1) / waves_cap;
+  const uint32_t want = run_req > 0       ? (uint32_t)run_req
+                        : env.stripe_run ? env.stripe_run
+                        : req == 0       ? NTS_AUTO_STRIPE_RUN
+                                         : 0u;
+  if (R < want) R = want;
+  if (R < 1) R = 1;
+  if (R > 0xffffffffu) return off;
+  sp.R = (uint32_t)R;
+  const uint64_t waves = (tasks + R - 1) / R;
+  uint64_t blocks = (waves + NTS_BLOCK / 64 - 1) / (NTS_BLOCK / 64);
+  if (blocks < 1) blocks = 1;
+  return StripeLaunch{true, Gs, 64u / Gs, (uint32_t)(blocks * 8u), sp};
+}
+
 /* The stream's staging buffer, grown on demand.  One per stream suffices:
  * the copy into it and the gather that reads it are ordered on the stream,
  * and so is the next call's copy behind that gather.  It is rebuilt on every
@@ -2084,6 +2362,13 @@ float *get_stage(nts_stream *s, uint64_t n) {
     s->stage_ws = nullptr;
     s->stage_cap = 0;
     NTS_CHECK(hipMalloc(&s->stage_ws, n * sizeof(float)));
+    /* rows start on a 128-byte line: a 32-float stripe of a row is then
+     * exactly one line (k_gather_spmm_stripe) */
+    if ((uintptr_t)s->stage_ws % 128 != 0) {
+      fprintf(stderr, "nts_hip: staging buffer %p is not 128-byte aligned\n",
+              (void *)s->stage_ws);
+      abort();
+    }
     s->stage_cap = n;
   }
   return s->stage_ws;
@@ -2115,6 +2400,7 @@ void launch_gather(nts_stream *s, const T *in, float *out, const float *ew,
   s->window_last = (int)L.pl.wf;
   s->staged_last = P.staged;
   s->stage_ld_last = P.staged ? P.ld : 0;
+  s->stripe_last = s->stripe_run_last = 0;
   if constexpr (sizeof(T) == sizeof(float)) {
     if (P.staged) {
 #define NTS_K(OV)                                                             \
@@ -2135,6 +2421,33 @@ void launch_gather(nts_stream *s, const T *in, float *out, const float *ew,
                                    : k_repitch<1>,
                          dim3(grid_for((uint64_t)rows * 64)), dim3(NTS_BLOCK),
                          0, s->stream, in, stage, rows, f, P.ld);
+      const StripeLaunch SL = plan_stripe(
+          P, f, sizeof(T), batch, edges, s->sched_req, s->window_req,
+          s->stage_req, s->stripe_req, s->stripe_run_req, gather_env());
+      if (SL.on) {
+        using SKernel = decltype(&k_gather_spmm_stripe<4, false, 1, 4>);
+#define NTS_K(OV, GS)                                                         \
+  {k_gather_spmm_stripe<4, false, OV, GS>, k_gather_spmm_stripe<4, true, OV, GS>}
+#define NTS_KG(OV)                                                            \
+  {NTS_K(OV, 4), NTS_K(OV, 8), NTS_K(OV, 16), NTS_K(OV, 32), NTS_K(OV, 64)}
+        /* indexed by log2(floats per access of `out`), log2(lanes / 4) */
+        static const SKernel stripe_kernels[3][5][2] = {NTS_KG(1), NTS_KG(2),
+                                                        NTS_KG(4)};
+#undef NTS_KG
+#undef NTS_K
+        s->sched_last = NTS_SCHED_PHASE;
+        s->window_last = (int)SL.sp.wf;
+        s->stripe_last = SL.sp.sf;
+        s->stripe_run_last = SL.sp.R;
+        hipLaunchKernelGGL(stripe_kernels[__builtin_ctz((unsigned)P.ov)]
+                                         [__builtin_ctz(SL.Gs) - 2]
+                                         [with_weight != 0],
+                           dim3(SL.grid), dim3(NTS_BLOCK), 0, s->stream,
+                           ib.items, ib.counter, nbr, ew, (const float *)stage,
+                           out, nbr_start, f, P.ld, SL.sp);
+        dbg_sync(s, "k_gather_spmm_stripe");
+        return;
+      }
       hipLaunchKernelGGL(staged_kernels[__builtin_ctz((unsigned)P.ov)]
                                        [with_weight != 0][L.blocked],
                          dim3(L.grid), dim3(NTS_BLOCK), 0, s->stream, ib.items,
@@ -2195,6 +2508,7 @@ void launch_gather_heads(nts_stream *s, const char *entry, const float *in,
       f, heads, (uintptr_t)in | (uintptr_t)out, batch, edges, gather_env());
   s->sched_last = (int)L.pl.sched;
   s->window_last = (int)L.pl.wf;
+  s->stripe_last = s->stripe_run_last = 0;
   Tic t(s, tag);
   hipLaunchKernelGGL(L.elem == 4   ? k_gather_spmm_heads<4>
                      : L.elem == 2 ? k_gather_spmm_heads<2>
@@ -2257,6 +2571,7 @@ void launch_reduce(nts_stream *s, int op, const float *in, float *out,
   const uint32_t row_grid = grid_for((uint64_t)batch * 64);
   s->sched_last = NTS_SCHED_ITEM;
   s->window_last = (int)R.L.pl.wf;
+  s->stripe_last = s->stripe_run_last = 0;
   Tic t(s, NTS_KTAG_FWD);
   hipLaunchKernelGGL((k_reduce_rows<false, false>), dim3(row_grid),
                      dim3(NTS_BLOCK), 0, s->stream, offset, batch, NTS_SPLIT,
@@ -2596,6 +2911,103 @@ void nts_gather_stage_plan(nts_vid feature_size, unsigned elem_bytes,
   if (store_width) *store_width = P.ov;
   if (grid) *grid = (int)P.L.grid;
   if (blocked) *blocked = P.L.blocked ? 1 : 0;
+}
+
+void nts_gather_stripes(nts_stream *s, int stripe_floats) {
+  s->stripe_req = stripe_floats < 0 ? -1 : stripe_floats;
+}
+
+void nts_gather_stripes_run(nts_stream *s, int tasks_per_wave) {
+  s->stripe_run_req = tasks_per_wave > 0 ? tasks_per_wave : 0;
+}
+
+void nts_gather_stripes_last(nts_stream *s, int *stripe_floats,
+                             int *tasks_per_wave) {
+  if (stripe_floats) *stripe_floats = (int)s->stripe_last;
+  if (tasks_per_wave) *tasks_per_wave = (int)s->stripe_run_last;
+}
+
+/* the stage plan plus the stripe decision of the same arguments */
+static StripeLaunch stripe_plan_of(nts_vid feature_size, unsigned elem_bytes,
+                                   unsigned in_alignment_bytes,
+                                   unsigned out_alignment_bytes, nts_vid rows,
+                                   nts_vid batch_size, nts_vid edges,
+                                   int schedule_req, int window_req,
+                                   int stage_req, int stripe_req, int run_req,
+                                   StagePlan &P) {
+  P = StagePlan{};
+  if (!batch_size || !edges || !feature_size) /* nothing is launched */
+    return StripeLaunch{};
+  P = plan_stage(feature_size, elem_bytes, in_alignment_bytes,
+                 out_alignment_bytes, rows, batch_size, edges, schedule_req,
+                 window_req, stage_req, gather_env());
+  return plan_stripe(P, feature_size, elem_bytes, batch_size, edges,
+                     schedule_req, window_req, stage_req, stripe_req, run_req,
+                     gather_env());
+}
+
+void nts_gather_stripe_plan(nts_vid feature_size, unsigned elem_bytes,
+                            unsigned in_alignment_bytes,
+                            unsigned out_alignment_bytes, nts_vid rows,
+                            nts_vid batch_size, nts_vid edges, int schedule_req,
+                            int window_req, int stage_req, int stripe_req,
+                            int run_req, int *staged, int *pitch_floats,
+                            int *schedule, int *window_floats, int *lane_group,
+                            int *vector_width, int *store_width, int *grid,
+                            int *blocked, int *stripe_floats,
+                            int *stripe_lanes, int *subgroups, int *stripes,
+                            int *tasks_per_wave) {
+  StagePlan P;
+  const StripeLaunch SL = stripe_plan_of(
+      feature_size, elem_bytes, in_alignment_bytes, out_alignment_bytes, rows,
+      batch_size, edges, schedule_req, window_req, stage_req, stripe_req,
+      run_req, P);
+  if (staged) *staged = P.staged ? 1 : 0;
+  if (pitch_floats) *pitch_floats = (int)P.ld;
+  if (schedule) *schedule = SL.on ? (int)NTS_SCHED_PHASE : (int)P.L.pl.sched;
+  if (window_floats) *window_floats = (int)(SL.on ? SL.sp.wf : P.L.pl.wf);
+  if (lane_group) *lane_group = (int)(SL.on ? SL.Gs : P.L.G);
+  if (vector_width) *vector_width = P.L.elem;
+  if (store_width) *store_width = P.ov;
+  if (grid) *grid = (int)(SL.on ? SL.grid : P.L.grid);
+  if (blocked) *blocked = (SL.on || P.L.blocked) ? 1 : 0;
+  if (stripe_floats) *stripe_floats = (int)SL.sp.sf;
+  if (stripe_lanes) *stripe_lanes = (int)SL.Gs;
+  if (subgroups) *subgroups = (int)SL.P;
+  if (stripes) *stripes = (int)SL.sp.S;
+  if (tasks_per_wave) *tasks_per_wave = (int)SL.sp.R;
+}
+
+long long nts_gather_stripe_task(
+    nts_vid feature_size, unsigned elem_bytes, unsigned in_alignment_bytes,
+    unsigned out_alignment_bytes, nts_vid rows, nts_vid batch_size,
+    nts_vid edges, int schedule_req, int window_req, int stage_req,
+    int stripe_req, int run_req, nts_vid n_items, unsigned long long first_slot,
+    unsigned long long count, nts_vid *item, nts_vid *first_column,
+    nts_vid *column_bound) {
+  StagePlan P;
+  const StripeLaunch SL = stripe_plan_of(
+      feature_size, elem_bytes, in_alignment_bytes, out_alignment_bytes, rows,
+      batch_size, edges, schedule_req, window_req, stage_req, stripe_req,
+      run_req, P);
+  long long live = 0;
+  constexpr uint32_t WAVES = NTS_BLOCK / 64;
+  for (unsigned long long k = 0; k < count; ++k) {
+    Task tk{0u, 0u, 0u};
+    if (SL.on) {
+      const unsigned long long slot = first_slot + k;
+      const unsigned long long w = slot / SL.sp.R;
+      if (w / WAVES < SL.grid)
+        tk = stripe_task(SL.grid, n_items, feature_size, SL.sp,
+                         (uint32_t)(w / WAVES), (uint32_t)(w % WAVES),
+                         (uint32_t)(slot % SL.sp.R));
+    }
+    if (item) item[k] = tk.it;
+    if (first_column) first_column[k] = tk.fbase;
+    if (column_bound) column_bound[k] = tk.fend;
+    live += tk.fbase < tk.fend;
+  }
+  return live;
 }
 
 void nts_items_cache_clear(nts_stream *s) {

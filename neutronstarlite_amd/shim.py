@@ -84,6 +84,13 @@ def lib():
     l.nts_gather_staging.argtypes = [_vp, _i32]
     l.nts_gather_staging_last.argtypes = [_vp, _vp, _vp]
     l.nts_gather_stage_plan.argtypes = [_u32] * 7 + [_i32] * 3 + [_vp] * 9
+    l.nts_gather_stripes.argtypes = [_vp, _i32]
+    l.nts_gather_stripes_run.argtypes = [_vp, _i32]
+    l.nts_gather_stripes_last.argtypes = [_vp, _vp, _vp]
+    l.nts_gather_stripe_plan.argtypes = [_u32] * 7 + [_i32] * 5 + [_vp] * 14
+    l.nts_gather_stripe_task.argtypes = (
+        [_u32] * 7 + [_i32] * 5 + [_u32] + [_c.c_ulonglong] * 2 + [_vp] * 3)
+    l.nts_gather_stripe_task.restype = _c.c_longlong
     l.nts_deserialize_to_gpu.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _i32]
     l.nts_aggregate_comm_result.argtypes = [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _i32]
     l.nts_gather_rows.argtypes = [_vp, _vp, _vp, _vp, _u32, _u32, _u32]
@@ -177,6 +184,45 @@ def gather_stage_plan(f, in_alignment, out_alignment, rows, batch, edges,
     plan["staged"] = bool(plan["staged"])
     plan["blocked"] = bool(plan["blocked"])
     return plan
+
+
+def gather_stripe_plan(f, in_alignment, out_alignment, rows, batch, edges,
+                       schedule=0, window=0, stage=0, stripe=0, run=0,
+                       elem_bytes=4):
+    """gather_stage_plan with the stripe decision (no device access): the
+    gather_stage_plan dict of the launch that really runs plus stripe (width
+    in floats, 0 = no stripes), stripe_lanes, subgroups (per wave), stripes
+    (per window) and tasks_per_wave.  stripe / run are requests as for
+    Stream.gather_stripes."""
+    names = ("staged", "pitch", "schedule", "window", "lane_group",
+             "vector_width", "store_width", "grid", "blocked", "stripe",
+             "stripe_lanes", "subgroups", "stripes", "tasks_per_wave")
+    out = [_i32(0) for _ in names]
+    lib().nts_gather_stripe_plan(f, elem_bytes, in_alignment, out_alignment,
+                                 rows, batch, edges, schedule, window, stage,
+                                 stripe, run, *[_c.byref(o) for o in out])
+    plan = {n: o.value for n, o in zip(names, out)}
+    plan["staged"] = bool(plan["staged"])
+    plan["blocked"] = bool(plan["blocked"])
+    return plan
+
+
+def gather_stripe_tasks(f, in_alignment, out_alignment, rows, batch, edges,
+                        n_items, first_slot, count, schedule=0, window=0,
+                        stage=0, stripe=0, run=0, elem_bytes=4):
+    """The kernel's task decode on the host (no device access): for the
+    plan of gather_stripe_plan's arguments and n_items work items, the tasks
+    of `count` wave slots from first_slot on, slot = (workgroup * 4 + wave) *
+    tasks_per_wave + run index.  Returns (item, first_column, column_bound)
+    as numpy uint32 arrays; first_column >= column_bound is a slot without a
+    task."""
+    import numpy as np
+    arrs = [np.zeros(count, dtype=np.uint32) for _ in range(3)]
+    lib().nts_gather_stripe_task(f, elem_bytes, in_alignment, out_alignment,
+                                 rows, batch, edges, schedule, window, stage,
+                                 stripe, run, n_items, first_slot, count,
+                                 *[a.ctypes.data for a in arrs])
+    return tuple(arrs)
 
 
 def check_heads(f, heads):
@@ -452,6 +498,20 @@ class Stream:
         self._lib.nts_gather_staging_last(self.h, _c.byref(staged),
                                           _c.byref(pitch))
         return bool(staged.value), pitch.value
+
+    def gather_stripes(self, stripe_floats=0, tasks_per_wave=0):
+        """Stripes of the following staged PHASE gathers: 0 automatic, -1
+        never, > 0 that width in floats; tasks_per_wave 0 = the fewest that
+        fit the grid cap."""
+        self._lib.nts_gather_stripes(self.h, stripe_floats)
+        self._lib.nts_gather_stripes_run(self.h, tasks_per_wave)
+
+    def gather_stripes_last(self):
+        """(stripe_floats, tasks_per_wave) of the most recent gather; (0, 0)
+        if it ran without stripes."""
+        sf, run = _i32(0), _i32(0)
+        self._lib.nts_gather_stripes_last(self.h, _c.byref(sf), _c.byref(run))
+        return sf.value, run.value
 
     def items_cache_clear(self):
         self._lib.nts_items_cache_clear(self.h)

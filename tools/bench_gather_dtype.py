@@ -20,7 +20,12 @@ request to the kernel for both dtypes; --sweep-bf16 "0:-1,1:0,1:64" times
 further bf16 requests (schedule:window) in the same alternation, and
 --sweep-stage "1:0:0,1:1:128,-1:1:0" further fp32 requests with a row-staging
 mode in front (stage:schedule:window; 1 force, -1 never, 0 automatic; the
-first two variants run with staging off).  --rounds R
+first two variants run with staging off), and --sweep-stripe
+"128:128:0,128:32:0,128:32:8,256:32:0" further staged fp32 PHASE launches with
+stripes forced (window:stripe floats:tasks per wave, 0 = the fewest that fit
+the grid cap; R = 1 at the headline shape needs NTS_GATHER_BLOCKS=4194304),
+after one variant that is the automatic launch with stripes off (-1) and one
+that is fully automatic.  --rounds R
 repeats the whole alternation R times and reports every round, which is the
 run-to-run spread to judge the ratio by.
 
@@ -68,6 +73,9 @@ def main(argv=None):
     ap.add_argument("--sweep-stage", default="",
                     help="comma list of stage:schedule:window requests, "
                          "fp32 only")
+    ap.add_argument("--sweep-stripe", default="",
+                    help="comma list of window:stripe:run requests, staged "
+                         "fp32 PHASE only")
     ap.add_argument("--graph", default="reddit", choices=["reddit", "small"])
     args = ap.parse_args(argv)
 
@@ -106,26 +114,36 @@ def main(argv=None):
     gx = torch.zeros(v, f, device=dev)
 
     request = (args.schedule, args.window)
-    # (dtype, schedule request, staging mode)
-    variants = [("fp32", request, -1), ("bf16", request, -1)]
+    # (dtype, schedule request, staging mode, (stripe floats, tasks per wave));
+    # all but the stripe sweep run with stripes off
+    off = (-1, 0)
+    variants = [("fp32", request, -1, off), ("bf16", request, -1, off)]
     if args.sweep_bf16:
-        variants += [("bf16", parse_request(r), -1)
+        variants += [("bf16", parse_request(r), -1, off)
                      for r in args.sweep_bf16.split(",")]
     n_bf16 = len(variants)
     if args.sweep_stage:
         for r in args.sweep_stage.split(","):
             stage, req = r.split(":", 1)
-            variants.append(("fp32", parse_request(req), int(stage)))
+            variants.append(("fp32", parse_request(req), int(stage), off))
+    n_stage = len(variants)
+    if args.sweep_stripe:
+        variants.append(("fp32", (0, 0), 0, off))     # the launch without
+        variants.append(("fp32", (0, 0), 0, (0, 0)))  # the automatic launch
+        for r in args.sweep_stripe.split(","):
+            window, stripe, run = (int(x) for x in r.split(":"))
+            variants.append(("fp32", (1, window), 1, (stripe, run)))
 
     def gather_ns():
         return (eng.stream.kernel_ns(shim.KTAG_FWD)
                 + eng.stream.kernel_ns(shim.KTAG_BWD))
 
-    def step(dtype, req, stage):
+    def step(dtype, req, stage, stripe):
         """One forward + backward; returns (kernel ms, wall ms, what ran)."""
         x, g = inputs[dtype]
         eng.stream.gather_schedule(*req)
         eng.stream.gather_staging(stage)
+        eng.stream.gather_stripes(*stripe)
         torch.cuda.synchronize()
         k0, t = gather_ns(), time.perf_counter()
         y.zero_()
@@ -135,19 +153,20 @@ def main(argv=None):
         torch.cuda.synchronize()
         wall = (time.perf_counter() - t) * 1e3
         ran = (eng.stream.gather_schedule_last()
-               + eng.stream.gather_staging_last()[1:])
+               + eng.stream.gather_staging_last()[1:]
+               + eng.stream.gather_stripes_last())
         return (gather_ns() - k0) / 1e6, wall, ran
 
     for _ in range(args.warmup):
-        for dtype, req, stage in variants:
-            step(dtype, req, stage)
+        for variant in variants:
+            step(*variant)
 
     rounds = []
     for _ in range(args.rounds):
         acc = [[0.0, 0.0, None] for _ in variants]
         for _ in range(args.steps):
-            for i, (dtype, req, stage) in enumerate(variants):
-                k, wall, ran = step(dtype, req, stage)
+            for i, variant in enumerate(variants):
+                k, wall, ran = step(*variant)
                 acc[i][0] += k
                 acc[i][1] += wall
                 acc[i][2] = ran
@@ -155,14 +174,16 @@ def main(argv=None):
                        for k, wall, ran in acc])
 
     def report(i):
-        dtype, req, stage = variants[i]
+        dtype, req, stage, stripe = variants[i]
         ks = [r[i][0] for r in rounds]
         walls = [r[i][1] for r in rounds]
         k = sum(ks) / len(ks)
         model = model_bytes(v, e_total, f, 4 if dtype == "fp32" else 2)
         gbps = model / (k * 1e-3) / 1e9
         return {"dtype": dtype, "request": list(req), "stage": stage,
-                "ran": list(rounds[-1][i][2]),  # schedule, window, pitch
+                "stripe": list(stripe),
+                # schedule, window, pitch, stripe floats, tasks per wave
+                "ran": list(rounds[-1][i][2]),
                 "ms_per_step": round(k, 3),
                 "wall_ms_per_step": round(sum(walls) / len(walls), 3),
                 "rounds_ms_per_step": [round(x, 3) for x in ks],
@@ -180,7 +201,8 @@ def main(argv=None):
            "model_ratio": round(bf16["model_bytes_per_step"]
                                 / fp32["model_bytes_per_step"], 4),
            "sweep_bf16": [report(i) for i in range(2, n_bf16)],
-           "sweep_stage": [report(i) for i in range(n_bf16, len(variants))]}
+           "sweep_stage": [report(i) for i in range(n_bf16, n_stage)],
+           "sweep_stripe": [report(i) for i in range(n_stage, len(variants))]}
     print(json.dumps(out), flush=True)
 
 

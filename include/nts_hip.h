@@ -587,6 +587,40 @@ void nts_weight_sum_heads(nts_stream *s, float *out, const float *weights,
  * tested and timed on the same input. */
 void nts_heads_dbg_general(nts_stream *s, int enable);
 
+/* ---- numerically stable edge softmax (additive) ----
+ * A request on the stream, as nts_gather_staging is; it reads no environment.
+ * With enable != 0 the stream's following nts_edge_softmax_forward,
+ * nts_edge_softmax_forward_dual, nts_edge_attention_forward and
+ * nts_edge_attention_forward_heads calls compute, per destination and per
+ * column or head,
+ *   s[e] = exp(a[e] - M) / sum_e' exp(a[e'] - M),  M = max_e' a[e'],
+ * over the destination's in-edges, where a is what each entry exponentiates
+ * today: the input score, or leaky_relu(s_src[..] + s_dst[..]).  The default
+ * (enable == 0) is the reference's exp(a) / sum exp(a), which is NaN once a
+ * score passes about 88.7 or all scores of a destination lie below about
+ * -103; with enable == 0 the four entries launch exactly the kernels, with
+ * the arguments, they launched before this request existed.
+ * Everything else the entries promise holds in both modes: m_sum_out (one
+ * fp32 add), msg_cached and its aliasing, the dual emission through
+ * perm_pos, mirror_index NULL, heads == 1 running the single-head kernel,
+ * nts_heads_dbg_general, item reuse, the NTS_KTAG_EDGE tag, no device-to-host
+ * copy or synchronize beyond the default's, and destinations without edges
+ * writing nothing.  The two passes move the same bytes as the default's; the
+ * per-destination state is a (max, sum) pair in a scratch of the stream.  A
+ * destination that is one work item stores it without an atomic; one split
+ * into several merges the maxima with a 32-bit atomic max, and a third
+ * launch, which skips every unsplit item, re-reads the split items' stash
+ * and adds their sums with fp32 atomics as the default does.  The
+ * backward entries work from the cached softmax output and are not affected.
+ * Scores must be finite, except that -inf on a strict subset of a
+ * destination's edges gives exactly +0.0f there and the softmax of the rest
+ * elsewhere.  A destination whose scores are all -inf, or that has a +inf or
+ * a NaN score, is unspecified. */
+void nts_edge_softmax_stable(nts_stream *s, int enable);   /* default 0 */
+/* Whether the most recent of those four calls ran the stable form (a call
+ * that had no edge to work on counts, with the mode it was made in). */
+void nts_edge_softmax_stable_last(nts_stream *s, int *stable);
+
 /* Opt-in work-item reuse: with enable=1 the stream caches its two most
  * recent item decompositions keyed on (offset pointer, batch, edges) and
  * skips identical rebuilds.  ONLY safe while the caller keeps those

@@ -120,6 +120,11 @@ struct nts_stream {
   int sched_last = 0, window_last = 0; /* what the last gather ran */
   float *sums_ws = nullptr;  /* per-dst reduction scratch (softmax) */
   uint64_t sums_cap = 0;
+  unsigned long long *pairs_ws = nullptr; /* per-dst (max, sum) pairs (stable
+                                             softmax) */
+  uint64_t pairs_cap = 0;
+  bool softmax_stable = false;      /* nts_edge_softmax_stable */
+  bool softmax_stable_last = false; /* what the last softmax forward ran */
   unsigned long long *keys_ws = nullptr; /* hub merge keys (max/min gather) */
   uint64_t keys_cap = 0;
   float *stage_ws = nullptr; /* gathered rows re-pitched (row staging) */
@@ -1784,6 +1789,269 @@ __global__ void k_weight_sum_heads(const uint4 *__restrict__ items,
   }
 }
 
+/* ---------------- stable (max-subtracted) edge softmax ---------------- */
+/* nts_edge_softmax_stable: the twins of k_edge_softmax_sum<false>,
+ * k_edge_att_sum, both forms of k_edge_att_sum_heads and
+ * k_edge_softmax_norm<false>, same two item-driven passes over the same
+ * bytes.  Pass 1 stashes the activation a (not exp a) in out and leaves, per
+ * (destination, column or head), the pair (M, S) = (max a, sum exp(a - M))
+ * in a stream-owned scratch; pass 2 writes exp(a - M) / S.
+ *
+ * A pair is one 64-bit word: reduce_key's ordered-uint map of M in the low
+ * half, S in the high half; the all-zero word of the memset is below every
+ * real key and is a sum of 0.
+ * An unsplit destination (one item): a lane keeps a running pair over the
+ * values it strides (one exp per value, nothing re-read at any NTS_SPLIT or
+ * K); M is a butterfly max, every lane rescales its sum to M once, S is the
+ * butterfly sum, and the pair is stored with a plain store, no atomic.
+ * A split destination: its items reduce their maxima in pass 1 and merge
+ * them with a u32 atomicMax on the key; k_edge_softmax_splitsum, which skips
+ * every unsplit item, then re-reads the split items' stash and adds
+ * sum exp(a - M) with the default's fp32 atomicAdd.  (A 64-bit
+ * compare-and-swap merge of whole pairs in pass 1 was measured and removed:
+ * DESIGN section 3.)  A score of -inf adds nothing anywhere, and an item of
+ * nothing but -inf leaves the slot alone (no exp(-inf + inf)). */
+struct MaxSum { float m, s; }; /* s = sum of exp(a - m); (-inf, 0) = nothing */
+
+__device__ __forceinline__ void ms_add(MaxSum &p, float a) {
+  if (a > p.m) {
+    p.s = p.s * __expf(p.m - a) + 1.f; /* first value: 0 * exp(-inf) + 1 */
+    p.m = a;
+  } else if (a > -INFINITY) {
+    p.s += __expf(a - p.m);
+  }
+}
+
+__device__ __forceinline__ float wave_max(float x) {
+#pragma unroll
+  for (int w = 32; w >= 1; w >>= 1) x = fmaxf(x, __shfl_xor(x, w, 64));
+  return x;
+}
+/* heads_lane_sum's steps: head k's max on lanes == k mod K */
+__device__ __forceinline__ float heads_lane_max(float x, uint32_t K) {
+  for (uint32_t w = 32; w >= K; w >>= 1) x = fmaxf(x, __shfl_xor(x, w, 64));
+  return x;
+}
+/* a lane's sum rescaled to the item's maximum (0 from a lane or an item that
+ * saw nothing but -inf) */
+__device__ __forceinline__ float ms_rescaled(const MaxSum &p, float Mi) {
+  return (p.m > -INFINITY) ? p.s * __expf(p.m - Mi) : 0.f;
+}
+
+/* reduce_key's monotone float -> uint map (never 0 for a non-NaN) */
+__device__ __forceinline__ uint32_t ms_key(float x) {
+  const uint32_t u = __float_as_uint(x);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ms_unkey(uint32_t u) {
+  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+__device__ __forceinline__ unsigned long long ms_pack(float M, float S) {
+  return ((unsigned long long)__float_as_uint(S) << 32) | ms_key(M);
+}
+__device__ __forceinline__ MaxSum ms_unpack(unsigned long long x) {
+  return MaxSum{ms_unkey((uint32_t)x), __uint_as_float((uint32_t)(x >> 32))};
+}
+
+/* a value into a lane's pair; an item of a split destination needs the
+ * maximum only (its sum is k_edge_softmax_splitsum's) */
+__device__ __forceinline__ void ms_add(MaxSum &p, float a, bool maxonly) {
+  if (maxonly) p.m = fmaxf(p.m, a);
+  else ms_add(p, a);
+}
+
+/* one item's result into its destination's slot: the whole pair of an
+ * unsplit destination, the maximum of a split one's item */
+__device__ __forceinline__ void ms_put(unsigned long long *slot, float Mi,
+                                       float Si, bool shared) {
+  if (!(Mi > -INFINITY)) return;
+  if (shared) atomicMax(reinterpret_cast<uint32_t *>(slot), ms_key(Mi));
+  else *slot = ms_pack(Mi, Si);
+}
+
+/* Between the passes: an item of a split destination re-reads its stash and adds
+ * sum exp(a - M) to its destination's S with the default's fp32 atomicAdd.
+ * FLAT (f a power of two <= 64) as k_edge_att_sum_heads. */
+template <bool FLAT>
+__global__ void k_edge_softmax_splitsum(const uint4 *__restrict__ items,
+                                        const uint32_t *__restrict__ n_items_p,
+                                        const float *__restrict__ out,
+                                        unsigned long long *__restrict__ pairs,
+                                        uint32_t f) {
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    if (!im.shared) continue;
+    unsigned long long *slots = pairs + (uint64_t)im.v * f;
+    if constexpr (FLAT) {
+      const uint32_t k = w.lane & (f - 1);
+      const float M = ms_unkey((uint32_t)slots[k]);
+      const float *o = out + (uint64_t)im.e0 * f;
+      const uint64_t nel = (uint64_t)im.cnt * f;
+      float part = 0.f;
+      for (uint64_t i = w.lane; i < nel; i += 64) part += __expf(o[i] - M);
+      part = heads_lane_sum(part, f);
+      if (w.lane < f && part > 0.f)
+        atomicAdd(reinterpret_cast<float *>(&slots[w.lane]) + 1, part);
+    } else {
+      for (uint32_t r = 0; r < f; ++r) {
+        const float M = ms_unkey((uint32_t)slots[r]);
+        float part = 0.f;
+        for (uint32_t k = w.lane; k < im.cnt; k += 64)
+          part += __expf(out[(uint64_t)(im.e0 + k) * f + r] - M);
+        part = wave_sum(part);
+        if (w.lane == 0 && part > 0.f)
+          atomicAdd(reinterpret_cast<float *>(&slots[r]) + 1, part);
+      }
+    }
+  }
+}
+
+/* softmax forward, pass 1 (k_edge_softmax_sum<false>'s twin) */
+__global__ void k_edge_softmax_maxsum(const uint4 *__restrict__ items,
+                                      const uint32_t *__restrict__ n_items_p,
+                                      float *__restrict__ out,
+                                      const float *__restrict__ in,
+                                      unsigned long long *__restrict__ pairs,
+                                      uint32_t f) {
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    const bool maxonly = im.shared;
+    for (uint32_t r = 0; r < f; ++r) {
+      MaxSum p{-INFINITY, 0.f};
+      for (uint32_t k = w.lane; k < im.cnt; k += 64) {
+        const uint64_t m = (uint64_t)(im.e0 + k) * f + r;
+        const float a = in[m];
+        out[m] = a;          /* stash the score; normalized in pass 2 */
+        ms_add(p, a, maxonly);
+      }
+      const float Mi = wave_max(p.m);
+      const float Si = wave_sum(ms_rescaled(p, Mi));
+      if (w.lane == 0)
+        ms_put(&pairs[(uint64_t)im.v * f + r], Mi, Si, im.shared);
+    }
+  }
+}
+
+/* pass 2 (k_edge_softmax_norm<false>'s twin): out = exp(out - M) / S, also
+ * emitted at out2[pos2[e]] */
+__global__ void k_edge_softmax_norm_stable(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    float *__restrict__ out, const unsigned long long *__restrict__ pairs,
+    float *__restrict__ out2, const uint32_t *__restrict__ pos2, uint32_t f) {
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    const uint32_t d = im.v, e0 = im.e0;
+    const uint64_t nel = (uint64_t)im.cnt * f;
+    for (uint64_t i = w.lane; i < nel; i += 64) {
+      const uint32_t e = e0 + (uint32_t)(i / f);
+      const uint32_t r = (uint32_t)(i % f);
+      const uint64_t m = (uint64_t)e * f + r;
+      const MaxSum q = ms_unpack(pairs[(uint64_t)d * f + r]);
+      const float v = __expf(out[m] - q.m) / q.s;
+      out[m] = v;
+      if (out2) out2[(uint64_t)pos2[e] * f + r] = v;
+    }
+  }
+}
+
+/* attention forward, pass 1 (k_edge_att_sum's twin) */
+__global__ void k_edge_att_maxsum(const uint4 *__restrict__ items,
+                                  const uint32_t *__restrict__ n_items_p,
+                                  float *__restrict__ out /* a stash */,
+                                  float *__restrict__ m_sum_out,
+                                  const float *__restrict__ s_src,
+                                  const float *__restrict__ s_dst,
+                                  const uint32_t *__restrict__ row_indices,
+                                  const uint32_t *__restrict__ mirror_index,
+                                  float slope,
+                                  unsigned long long *__restrict__ pairs) {
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    const bool maxonly = im.shared;
+    const uint32_t d = im.v;
+    const float sd = s_dst[d];
+    MaxSum p{-INFINITY, 0.f};
+    for (uint32_t k = w.lane; k < im.cnt; k += 64) {
+      const uint32_t e = im.e0 + k;
+      const uint32_t src = row_indices[e];
+      const float m = s_src[mirror_index ? mirror_index[src] : src] + sd;
+      m_sum_out[e] = m;
+      const float a = (m > 0.f) ? m : slope * m;
+      out[e] = a;
+      ms_add(p, a, maxonly);
+    }
+    const float Mi = wave_max(p.m);
+    const float Si = wave_sum(ms_rescaled(p, Mi));
+    if (w.lane == 0) ms_put(&pairs[d], Mi, Si, im.shared);
+  }
+}
+
+/* attention forward, pass 1, K heads (k_edge_att_sum_heads' twin) */
+template <bool FLAT>
+__global__ void k_edge_att_maxsum_heads(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    float *__restrict__ out /* a stash */, float *__restrict__ m_sum_out,
+    const float *__restrict__ s_src, const float *__restrict__ s_dst,
+    const uint32_t *__restrict__ row_indices,
+    const uint32_t *__restrict__ mirror_index, float slope,
+    unsigned long long *__restrict__ pairs, uint32_t K) {
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    const bool maxonly = im.shared;
+    const uint32_t d = im.v;
+    if constexpr (FLAT) {
+      const uint32_t k = w.lane & (K - 1);
+      const uint32_t lgk = 31u - (uint32_t)__clz(K);
+      const float sd = s_dst[(uint64_t)d * K + k];
+      const uint64_t m0 = (uint64_t)im.e0 * K;
+      const uint64_t nel = (uint64_t)im.cnt * K;
+      MaxSum p{-INFINITY, 0.f};
+      for (uint64_t i = w.lane; i < nel; i += 64) {
+        const uint32_t src = row_indices[im.e0 + (uint32_t)(i >> lgk)];
+        const uint64_t row = mirror_index ? mirror_index[src] : src;
+        const float m = s_src[row * K + k] + sd;
+        m_sum_out[m0 + i] = m;
+        const float a = (m > 0.f) ? m : slope * m;
+        out[m0 + i] = a;
+        ms_add(p, a, maxonly);
+      }
+      const float Mi = heads_lane_max(p.m, K);
+      const float Si = heads_lane_sum(ms_rescaled(p, Mi), K);
+      if (w.lane < K)
+        ms_put(&pairs[(uint64_t)d * K + w.lane], Mi, Si, im.shared);
+    } else {
+      for (uint32_t k = 0; k < K; ++k) {
+        const float sd = s_dst[(uint64_t)d * K + k];
+        MaxSum p{-INFINITY, 0.f};
+        for (uint32_t j = w.lane; j < im.cnt; j += 64) {
+          const uint32_t e = im.e0 + j;
+          const uint32_t src = row_indices[e];
+          const uint64_t row = mirror_index ? mirror_index[src] : src;
+          const float m = s_src[row * K + k] + sd;
+          m_sum_out[(uint64_t)e * K + k] = m;
+          const float a = (m > 0.f) ? m : slope * m;
+          out[(uint64_t)e * K + k] = a;
+          ms_add(p, a, maxonly);
+        }
+        const float Mi = wave_max(p.m);
+        const float Si = wave_sum(ms_rescaled(p, Mi));
+        if (w.lane == 0)
+          ms_put(&pairs[(uint64_t)d * K + k], Mi, Si, im.shared);
+      }
+    }
+  }
+}
+
 /* per-head edge dot: out[e*K + k] = dot over head k's C columns.
  * The general form runs a wave per (edge, head): lanes stride the head's C
  * columns, wave_sum (64 - C lanes idle when C < 64).
@@ -2628,6 +2896,7 @@ void nts_stream_destroy(nts_stream *s) {
     if (slot.counter) hipFree(slot.counter);
   }
   if (s->sums_ws) hipFree(s->sums_ws);
+  if (s->pairs_ws) hipFree(s->pairs_ws);
   if (s->keys_ws) hipFree(s->keys_ws);
   if (s->stage_ws) hipFree(s->stage_ws);
   if (s->owned) hipStreamDestroy(s->stream);
@@ -3119,6 +3388,42 @@ static float *get_sums(nts_stream *s, uint64_t n) {
   return s->sums_ws;
 }
 
+/* the stable softmax's (max, sum) pairs; all-zero = empty */
+static unsigned long long *get_pairs(nts_stream *s, uint64_t n) {
+  if (s->pairs_cap < n) {
+    NTS_CHECK(hipStreamSynchronize(s->stream));
+    if (s->pairs_ws) NTS_CHECK(hipFree(s->pairs_ws));
+    NTS_CHECK(hipMalloc(&s->pairs_ws, n * sizeof(unsigned long long)));
+    s->pairs_cap = n;
+  }
+  NTS_CHECK(hipMemsetAsync(s->pairs_ws, 0, n * sizeof(unsigned long long),
+                           s->stream));
+  return s->pairs_ws;
+}
+
+void nts_edge_softmax_stable(nts_stream *s, int enable) {
+  s->softmax_stable = enable != 0;
+}
+
+void nts_edge_softmax_stable_last(nts_stream *s, int *stable) {
+  if (stable) *stable = s->softmax_stable_last ? 1 : 0;
+}
+
+/* what follows pass 1 of the stable forward entries: the split items' sum
+ * pass, then pass 2 */
+static void launch_norm_stable(nts_stream *s, const EdgeItems &p, float *out,
+                               unsigned long long *pairs, float *out2,
+                               const nts_vid *pos2, nts_vid f) {
+  const bool flat = !s->heads_general && f <= 64 && (f & (f - 1)) == 0;
+  hipLaunchKernelGGL(flat ? k_edge_softmax_splitsum<true>
+                          : k_edge_softmax_splitsum<false>,
+                     dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                     p.ib->counter, out, pairs, f);
+  hipLaunchKernelGGL(k_edge_softmax_norm_stable, dim3(p.grid),
+                     dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                     p.ib->counter, out, pairs, out2, pos2, f);
+}
+
 static void launch_edge_op(nts_stream *s, EdgeOp op, float *message,
                            float *vfeat, const nts_vid *row_indices,
                            const nts_vid *column_offset,
@@ -3149,9 +3454,20 @@ static uint32_t launch_edge_softmax(nts_stream *s, bool backward, float *out,
                                     float slope = 0.f,
                                     float *dst_accum = nullptr) {
   if (dst_accum && f != 1) abort(); /* per-dst sum emission is f==1 only */
+  if (!backward) s->softmax_stable_last = s->softmax_stable;
   if (!f) return 0;
   const EdgeItems p = edge_items(s, column_offset, batch);
   if (!p.ib) return 0;
+  if (!backward && s->softmax_stable) {
+    unsigned long long *pairs = get_pairs(s, (uint64_t)batch * f);
+    Tic t(s, NTS_KTAG_EDGE);
+    hipLaunchKernelGGL(k_edge_softmax_maxsum, dim3(p.grid), dim3(NTS_BLOCK),
+                       0, s->stream, p.ib->items, p.ib->counter, out, in,
+                       pairs, f);
+    launch_norm_stable(s, p, out, pairs, out2, pos2, f);
+    dbg_sync(s, "k_edge_softmax_stable");
+    return p.edges;
+  }
   float *sums = get_sums(s, (uint64_t)batch * f);
   Tic t(s, NTS_KTAG_EDGE);
   hipLaunchKernelGGL(
@@ -3306,10 +3622,23 @@ void nts_edge_attention_forward(nts_stream *s, float *softmax_out,
                                 const nts_vid *mirror_index, float slope,
                                 const nts_vid *column_offset,
                                 nts_vid batch_size) {
+  s->softmax_stable_last = s->softmax_stable;
   const EdgeItems p = edge_items(s, column_offset, batch_size);
   if (!p.ib) return;
   const ItemsBuf &ib = *p.ib;
   const uint32_t grid = p.grid;
+  if (s->softmax_stable) {
+    unsigned long long *pairs = get_pairs(s, batch_size);
+    Tic t(s, NTS_KTAG_EDGE);
+    hipLaunchKernelGGL(k_edge_att_maxsum, dim3(grid), dim3(NTS_BLOCK), 0,
+                       s->stream, ib.items, ib.counter, softmax_out, m_sum_out,
+                       s_src_mirror, s_dst, row_indices, mirror_index, slope,
+                       pairs);
+    launch_norm_stable(s, p, softmax_out, pairs, softmax_out_perm, perm_pos,
+                       1u);
+    dbg_sync(s, "k_edge_att_stable");
+    return;
+  }
   float *sums = get_sums(s, batch_size);
   Tic t(s, NTS_KTAG_EDGE);
   hipLaunchKernelGGL(k_edge_att_sum, dim3(grid), dim3(NTS_BLOCK), 0,
@@ -3353,9 +3682,29 @@ void nts_edge_attention_forward_heads(
     const nts_vid *mirror_index, float slope, const nts_vid *column_offset,
     nts_vid batch_size, nts_vid edges, nts_vid heads) {
   check_heads("nts_edge_attention_forward_heads", heads, heads);
+  s->softmax_stable_last = s->softmax_stable;
   const EdgeItems p = edge_items_known(s, column_offset, batch_size, edges);
   if (!p.ib) return;
   const ItemsBuf &ib = *p.ib;
+  if (s->softmax_stable) {
+    unsigned long long *pairs = get_pairs(s, (uint64_t)batch_size * heads);
+    Tic t(s, NTS_KTAG_EDGE);
+    if (heads == 1)
+      hipLaunchKernelGGL(k_edge_att_maxsum, dim3(p.grid), dim3(NTS_BLOCK), 0,
+                         s->stream, ib.items, ib.counter, softmax_out,
+                         m_sum_out, s_src_mirror, s_dst, row_indices,
+                         mirror_index, slope, pairs);
+    else
+      hipLaunchKernelGGL(heads_flat(s, heads) ? k_edge_att_maxsum_heads<true>
+                                              : k_edge_att_maxsum_heads<false>,
+                         dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream, ib.items,
+                         ib.counter, softmax_out, m_sum_out, s_src_mirror,
+                         s_dst, row_indices, mirror_index, slope, pairs, heads);
+    launch_norm_stable(s, p, softmax_out, pairs, softmax_out_perm, perm_pos,
+                       heads);
+    dbg_sync(s, "k_edge_att_heads_stable");
+    return;
+  }
   float *sums = get_sums(s, (uint64_t)batch_size * heads);
   Tic t(s, NTS_KTAG_EDGE);
   if (heads == 1)

@@ -42,19 +42,28 @@ class GATLayer:
     """Attention-weighted aggregation on one chunk (whole graph on 1 GPU)."""
 
     def __init__(self, ch: Chunk, v: int, device, heads: int = 1,
-                 _heads_path: bool = False):
+                 stable: bool = False, _heads_path: bool = False):
         """heads = K attention heads over head-major column blocks.  With
         heads == 1 the layer makes exactly the single-head calls.
+        stable=True runs the max-subtracted softmax (Stream.
+        edge_softmax_stable) on the layer's own stream wrapper, single-head
+        and heads path alike; the default is the reference's exp / sum exp,
+        which is NaN once a logit passes about 88.  The backward is the same.
         _heads_path (private, for tools/bench_gat_heads.py) runs the heads
         call chain at heads == 1 too: unfused CSR gather + edge dot."""
         if not isinstance(heads, int) or heads < 1:
             raise ValueError(f"heads must be a positive int, got {heads!r}")
+        if not isinstance(stable, bool):
+            raise ValueError(f"stable must be a bool, got {stable!r}")
         self.heads = heads
+        self.stable = stable
         self._heads_path = heads > 1 or _heads_path
         self.v = v
         self.np_ch = ch
         self.ch = DeviceChunk(ch, device)
         self.stream = shim.Stream.wrap_torch_current()
+        if stable:
+            self.stream.edge_softmax_stable(1)
         self.mirror_index = _u32_cuda(np.arange(v, dtype=np.uint32), device)
         self.device = device
         self.E = ch.edge_size

@@ -124,6 +124,8 @@ def lib():
     l.nts_edge_dot_heads.argtypes = [_vp] + [_vp] * 5 + [_u32] * 5
     l.nts_weight_sum_heads.argtypes = [_vp] + [_vp] * 3 + [_u32] * 3
     l.nts_heads_dbg_general.argtypes = [_vp, _i32]
+    l.nts_edge_softmax_stable.argtypes = [_vp, _i32]
+    l.nts_edge_softmax_stable_last.argtypes = [_vp, _vp]
     # max / min aggregation
     l.nts_reduce_by_dst_from_src.argtypes = (
         [_vp, _i32] + [_vp] * 5 + [_u32] * 7)
@@ -606,6 +608,19 @@ class Stream:
         """TEST/MEASUREMENT hook: the general forms of the heads edge
         kernels even where a faster one exists for the shape."""
         self._lib.nts_heads_dbg_general(self.h, 1 if enable else 0)
+
+    def edge_softmax_stable(self, enable):
+        """Max-subtracted softmax in the following edge_softmax_forward,
+        edge_softmax_forward_dual, edge_attention_forward and
+        edge_attention_forward_heads calls of this wrapper (default off: the
+        reference's exp / sum exp, NaN past a score of about 88)."""
+        self._lib.nts_edge_softmax_stable(self.h, 1 if enable else 0)
+
+    def edge_softmax_stable_last(self):
+        """1 if the most recent of those calls ran the stable form, else 0."""
+        stable = _i32(0)
+        self._lib.nts_edge_softmax_stable_last(self.h, _c.byref(stable))
+        return stable.value
 
     def destroy(self):
         if self.h:

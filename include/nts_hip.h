@@ -587,6 +587,60 @@ void nts_weight_sum_heads(nts_stream *s, float *out, const float *weights,
  * tested and timed on the same input. */
 void nts_heads_dbg_general(nts_stream *s, int enable);
 
+/* ---- GATv2 attention (additive): the f-wide per-edge score and its backward
+ * GATv2 applies the non-linearity before the dot with the attention vector:
+ *   t[e, c]     = x_l[src(e), c] + x_r[dst(e), c]        c < f = K*C, head-major
+ *   score[e, k] = sum_{j<C} att[k*C + j] * lrelu(t[e, k*C + j])
+ * and the [edges, f] tensor t is never stored.  Everything after the score
+ * (nts_edge_softmax_forward_dual at feature_size = K, the heads gathers,
+ * nts_edge_dot_heads, nts_edge_softmax_backward_fused with lrelu_input NULL)
+ * is generic in its input.  Conventions of both entries:
+ *   lrelu(t)  = t > 0 ? t : slope*t
+ *   lrelu'(t) = t > 0 ? 1 : slope        (slope at t == 0, the rule of
+ *                                          nts_edge_softmax_backward_fused)
+ *   t is ONE fp32 add of the two loaded row values, so a caller can rebuild
+ *   the mask bit for bit from the float32 inputs.
+ * att is fp32 [K, C] row-major, that is f floats indexed by column.  As for
+ * nts_edge_dot_heads: item-driven with the host-known edge count (no
+ * device-to-host copy, no synchronize), timing tag NTS_KTAG_EDGE, invalid
+ * heads abort, heads == 1 means C = f, batch_size == 0 or edges == 0 launches
+ * nothing and writes nothing.  Correct for every f, every heads dividing f and
+ * any 4-byte alignment of each pointer; the fast forms (score: C a power of
+ * two with C / R <= 64 lanes per head; backward: R > 1) hold R = 4 / 2 / 1
+ * columns per lane by C and the pointers' common alignment, and
+ * nts_heads_dbg_general selects the general forms (score: a wave per (edge,
+ * head); backward: one column per lane) on the same input. */
+
+/* score[e*K + k] = sum_{j<C} att[k*C+j] * lrelu(dst_rows[d, k*C+j] +
+ * src_rows[row_indices[e]-src_start, k*C+j]), e in CSC order, overwritten.
+ * Moves the bytes of nts_edge_dot_heads plus att. */
+void nts_edge_gatv2_score(nts_stream *s, float *score, const float *dst_rows,
+    const float *src_rows, const float *att, float slope,
+    const nts_vid *row_indices, const nts_vid *column_offset, nts_vid src_start,
+    nts_vid batch_size, nts_vid edges, nts_vid feature_size, nts_vid heads);
+
+/* One walk over an offset array (CSC: own = x_r, nbr = x_l; CSR: own = x_l,
+ * nbr = x_r), grad_score [edges, K] in THAT array's edge order:
+ *   grad_own[v, c] += sum_{e in v's range} grad_score[e, c/C] * att[c] *
+ *                     lrelu'(own[v,c] + nbr[nbr_indices[e]-nbr_start, c])
+ *   grad_att[c]    += sum_v sum_e grad_score[e, c/C] *
+ *                     lrelu(own[v,c] + nbr[...])      (grad_att NULL: skipped,
+ *                                                      nothing is written)
+ * Both outputs keep the += contract (caller-zeroed or pre-filled).  grad_own:
+ * a lane sums a vertex's edges in edge order and stores with a plain
+ * read-add-write; a vertex split into several work items merges with fp32
+ * atomics.  grad_att: a lane group sums its columns over all its work items
+ * in registers, a workgroup combines its groups through LDS, and one fp32
+ * atomic add per (workgroup, column) reaches memory.  The order of those
+ * additions is NOT fixed (work-item slots are handed out by an atomic, as
+ * for nts_reduce_backward): grad_att, and grad_own on split vertices, vary
+ * in the last bits from launch to launch. */
+void nts_edge_gatv2_backward(nts_stream *s, float *grad_own, float *grad_att,
+    const float *grad_score, const float *own_rows, const float *nbr_rows,
+    const float *att, float slope, const nts_vid *offset,
+    const nts_vid *nbr_indices, nts_vid nbr_start, nts_vid batch_size,
+    nts_vid edges, nts_vid feature_size, nts_vid heads);
+
 /* ---- numerically stable edge softmax (additive) ----
  * A request on the stream, as nts_gather_staging is; it reads no environment.
  * With enable != 0 the stream's following nts_edge_softmax_forward,

@@ -2151,6 +2151,201 @@ __global__ void k_edge_dot_heads(const uint4 *__restrict__ items,
   }
 }
 
+/* ---- GATv2 attention: the f-wide per-edge score and its backward ---- */
+/* t is ONE fp32 add of the two loaded values; lrelu(t) = t > 0 ? t : slope*t,
+ * lrelu'(t) = t > 0 ? 1 : slope (slope at t == 0, as k_edge_softmax_norm). */
+__device__ __forceinline__ float lrelu(float t, float slope) {
+  return t > 0.f ? t : slope * t;
+}
+
+/* score[e*K + k] = sum_{j<C} att[k*C+j] * lrelu(own[d, k*C+j] + nbr[src, k*C+j]):
+ * k_edge_dot_heads_seg with the product a*b replaced by att*lrelu(a+b); the
+ * lane's R att columns are loaded once per (item, slab) beside its own-row
+ * columns.  Same lane layout, clamping and writer rule as the dot. */
+template <int R>
+__global__ void k_gatv2_score_seg(const uint4 *__restrict__ items,
+                                  const uint32_t *__restrict__ n_items_p,
+                                  float *__restrict__ out,
+                                  const float *__restrict__ dst_rows,
+                                  const float *__restrict__ src_rows,
+                                  const float *__restrict__ att, float slope,
+                                  const uint32_t *__restrict__ row_indices,
+                                  uint32_t src_start, uint32_t f, uint32_t K,
+                                  uint32_t C, uint32_t G) {
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  const uint32_t L = C / R;          /* lanes per head */
+  const uint32_t gl = w.lane & (G - 1);
+  const uint32_t gi = w.lane / G;    /* which of the wave's edge slots */
+  const uint32_t ng = 64 / G;
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    const uint32_t e0 = im.e0, cnt = im.cnt;
+    for (uint32_t base = 0; base < f; base += G * R) {
+      const uint32_t col = base + gl * R;
+      const bool live = col < f;     /* f % R == 0: a live lane is full */
+      const uint32_t cc = live ? col : 0u;
+      const bool writer = live && (gl & (L - 1)) == 0;
+      const uint32_t head = cc / C;
+      float av[R], at[R];
+      if constexpr (R == 1) {
+        av[0] = dst_rows[(uint64_t)im.v * f + cc];
+        at[0] = att[cc];
+      } else {
+        load_lane<R>(dst_rows + (uint64_t)im.v * f + cc, av);
+        load_lane<R>(att + cc, at);
+      }
+      /* 4 edge slots per lane group in flight */
+      for (uint32_t k0 = 0; k0 < cnt; k0 += 4 * ng) {
+        float pr[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const uint32_t k = min(k0 + q * ng + gi, cnt - 1);
+          const float *b = src_rows +
+              (uint64_t)(row_indices[e0 + k] - src_start) * f + cc;
+          float bv[R];
+          if constexpr (R == 1) bv[0] = b[0];
+          else load_lane<R>(b, bv);
+          pr[q] = 0.f;
+#pragma unroll
+          for (int j = 0; j < R; ++j)
+            pr[q] = fmaf(at[j], lrelu(av[j] + bv[j], slope), pr[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const uint32_t k = k0 + q * ng + gi;
+          const float sum = seg_sum(pr[q], L);
+          if (writer && k < cnt) out[(uint64_t)(e0 + k) * K + head] = sum;
+        }
+      }
+    }
+  }
+}
+
+/* general form, any K and C: a wave per (edge, head), lanes stride the head */
+__global__ void k_gatv2_score(const uint4 *__restrict__ items,
+                              const uint32_t *__restrict__ n_items_p,
+                              float *__restrict__ out,
+                              const float *__restrict__ dst_rows,
+                              const float *__restrict__ src_rows,
+                              const float *__restrict__ att, float slope,
+                              const uint32_t *__restrict__ row_indices,
+                              uint32_t src_start, uint32_t f, uint32_t K,
+                              uint32_t C) {
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  const uint32_t lane = w.lane;
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    const uint32_t e0 = im.e0, cnt = im.cnt;
+    const float *a = dst_rows + (uint64_t)im.v * f;
+    for (uint32_t k = 0; k < cnt; ++k) {
+      const uint32_t e = e0 + k;
+      const float *b = src_rows + (uint64_t)(row_indices[e] - src_start) * f;
+      for (uint32_t h = 0; h < K; ++h) {
+        float sum = 0.f;
+        for (uint32_t j = h * C + lane; j < (h + 1) * C; j += 64)
+          sum = fmaf(att[j], lrelu(a[j] + b[j], slope), sum);
+        sum = wave_sum(sum);
+        if (lane == 0) out[(uint64_t)e * K + h] = sum;
+      }
+    }
+  }
+}
+
+/* One walk over an offset array, the shape of k_gather_spmm_heads: a group of
+ * G lanes per work item, a lane owning R consecutive columns of one head
+ * (R = 1: any f, any K, the head is the column's own).  Per edge the lane
+ * loads its R columns of the neighbour row and ONE grad_score[e, head]:
+ *   dOwn[j] += gs * lrelu'(t)      -> grad_own[v, col+j] += att[col+j]*dOwn[j]
+ *   dAtt[j] += gs * lrelu (t)      (WITH_ATT)
+ * The column slab is the outer loop and the group's items the inner one, so
+ * dAtt is R registers at any f; after the items the workgroup's 256/G groups
+ * meet in LDS and ONE atomicAdd per (workgroup, column) reaches grad_att. */
+template <int R, int NE>
+__device__ __forceinline__ void gatv2_bwd_edges(
+    float (&down)[R], float (&datt)[R], const float (&ov)[R],
+    const float *__restrict__ nbr_rows, const uint32_t *__restrict__ nbr,
+    const float *__restrict__ gscore, uint32_t nbr_start, uint32_t f,
+    uint32_t K, uint32_t e, uint32_t col, uint32_t head, float slope,
+    bool with_att) {
+  float x[NE][R], gs[NE];
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    const float *p = nbr_rows + (uint64_t)(nbr[e + k] - nbr_start) * f + col;
+    if constexpr (R == 1) x[k][0] = p[0];
+    else load_lane<R>(p, x[k]);
+    gs[k] = gscore[(uint64_t)(e + k) * K + head];
+  }
+#pragma unroll
+  for (int k = 0; k < NE; ++k)
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const float t = ov[j] + x[k][j];
+      down[j] = fmaf(gs[k], t > 0.f ? 1.f : slope, down[j]);
+      if (with_att) datt[j] = fmaf(gs[k], lrelu(t, slope), datt[j]);
+    }
+}
+
+template <int R, bool WITH_ATT>
+__global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_backward(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    float *__restrict__ grad_own, float *__restrict__ grad_att,
+    const float *__restrict__ gscore, const float *__restrict__ own_rows,
+    const float *__restrict__ nbr_rows, const float *__restrict__ att,
+    float slope, const uint32_t *__restrict__ nbr, uint32_t nbr_start,
+    uint32_t f, uint32_t K, uint32_t C, uint32_t G) {
+  __shared__ float part[WITH_ATT ? NTS_BLOCK * R : 1];
+  const uint32_t n_items = *n_items_p;
+  const uint32_t glane = threadIdx.x & (G - 1);
+  const uint32_t group = (blockIdx.x * NTS_BLOCK + threadIdx.x) / G;
+  const uint32_t n_groups = (gridDim.x * NTS_BLOCK) / G;
+  for (uint32_t base = 0; base < f; base += G * R) {
+    const uint32_t col = base + glane * R;
+    const bool live = col < f;       /* f % R == 0: a live lane is full */
+    float datt[R] = {};
+    if (live) {
+      const uint32_t head = col / C;
+      float at[R];
+      if constexpr (R == 1) at[0] = att[col];
+      else load_lane<R>(att + col, at);
+      for (uint32_t it = group; it < n_items; it += n_groups) {
+        const Item im = load_item(items, it);
+        const uint32_t e_end = im.e0 + im.cnt;
+        uint32_t e = im.e0;
+        float ov[R], down[R] = {};
+        if constexpr (R == 1) ov[0] = own_rows[(uint64_t)im.v * f + col];
+        else load_lane<R>(own_rows + (uint64_t)im.v * f + col, ov);
+        for (; e + 4 <= e_end; e += 4)
+          gatv2_bwd_edges<R, 4>(down, datt, ov, nbr_rows, nbr, gscore,
+                                nbr_start, f, K, e, col, head, slope, WITH_ATT);
+        for (; e < e_end; ++e)
+          gatv2_bwd_edges<R, 1>(down, datt, ov, nbr_rows, nbr, gscore,
+                                nbr_start, f, K, e, col, head, slope, WITH_ATT);
+#pragma unroll
+        for (int j = 0; j < R; ++j) down[j] *= at[j];
+        store_acc<R>(grad_own + (uint64_t)im.v * f + col, down, R, im.shared);
+      }
+    }
+    if constexpr (WITH_ATT) {
+      /* every thread of the workgroup arrives: the slab loop is uniform */
+#pragma unroll
+      for (int j = 0; j < R; ++j) part[threadIdx.x * R + j] = datt[j];
+      __syncthreads();
+      if (threadIdx.x < G && live) {
+        float sum[R] = {};
+        for (uint32_t g = 0; g < NTS_BLOCK / G; ++g)
+#pragma unroll
+          for (int j = 0; j < R; ++j)
+            sum[j] += part[(g * G + threadIdx.x) * R + j];
+#pragma unroll
+        for (int j = 0; j < R; ++j) atomicAdd(&grad_att[col + j], sum[j]);
+      }
+      __syncthreads();
+    }
+  }
+}
+
 /* forward softmax also fills msg_cached */
 __global__ void k_copy(float *__restrict__ dst, const float *__restrict__ src,
                        uint64_t n) {
@@ -3763,6 +3958,77 @@ void nts_edge_dot_heads(nts_stream *s, float *out, const float *dst_rows,
     }
   }
   dbg_sync(s, "k_edge_dot_heads");
+}
+
+void nts_edge_gatv2_score(nts_stream *s, float *score, const float *dst_rows,
+                          const float *src_rows, const float *att, float slope,
+                          const nts_vid *row_indices,
+                          const nts_vid *column_offset, nts_vid src_start,
+                          nts_vid batch_size, nts_vid edges,
+                          nts_vid feature_size, nts_vid heads) {
+  check_heads("nts_edge_gatv2_score", feature_size, heads);
+  const EdgeItems p = edge_items_known(s, column_offset, batch_size, edges);
+  if (!p.ib) return;
+  const uint32_t C = feature_size / heads;
+  /* columns per lane as for nts_edge_dot_heads, att's alignment included */
+  const GatherGeom geo = gather_geometry(
+      C, (uintptr_t)dst_rows | (uintptr_t)src_rows | (uintptr_t)att,
+      sizeof(float));
+  const uint32_t R = (uint32_t)geo.elem, L = C / R;
+  Tic t(s, NTS_KTAG_EDGE);
+  if (!s->heads_general && (L & (L - 1)) == 0 && L <= 64) {
+    uint32_t G = 64;
+    while (G / 2 >= feature_size / R) G /= 2;
+    hipLaunchKernelGGL(R == 4   ? k_gatv2_score_seg<4>
+                       : R == 2 ? k_gatv2_score_seg<2>
+                                : k_gatv2_score_seg<1>,
+                       dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream,
+                       p.ib->items, p.ib->counter, score, dst_rows, src_rows,
+                       att, slope, row_indices, src_start, feature_size, heads,
+                       C, G);
+  } else {
+    hipLaunchKernelGGL(k_gatv2_score, dim3(p.grid), dim3(NTS_BLOCK), 0,
+                       s->stream, p.ib->items, p.ib->counter, score, dst_rows,
+                       src_rows, att, slope, row_indices, src_start,
+                       feature_size, heads, C);
+  }
+  dbg_sync(s, "k_gatv2_score");
+}
+
+void nts_edge_gatv2_backward(nts_stream *s, float *grad_own, float *grad_att,
+                             const float *grad_score, const float *own_rows,
+                             const float *nbr_rows, const float *att,
+                             float slope, const nts_vid *offset,
+                             const nts_vid *nbr_indices, nts_vid nbr_start,
+                             nts_vid batch_size, nts_vid edges,
+                             nts_vid feature_size, nts_vid heads) {
+  check_heads("nts_edge_gatv2_backward", feature_size, heads);
+  const EdgeItems p = edge_items_known(s, offset, batch_size, edges);
+  if (!p.ib) return;
+  const uint32_t f = feature_size, C = f / heads;
+  /* columns per lane: 4 / 2 dividing C (a lane stays inside one head) where
+   * every row pointer and att permit the vector access, else 1, which is
+   * also the general form nts_heads_dbg_general asks for */
+  uint32_t R = 1;
+  if (!s->heads_general)
+    R = (uint32_t)gather_geometry(
+            C, (uintptr_t)grad_own | (uintptr_t)own_rows |
+                   (uintptr_t)nbr_rows | (uintptr_t)att,
+            sizeof(float)).elem;
+  uint32_t G = 64;
+  while (G / 2 >= f / R && G > 16) G /= 2;
+  const uint64_t bound_items = (uint64_t)batch_size + edges / NTS_SPLIT + 1;
+  const uint32_t grid = grid_for(bound_items * G);
+  Tic t(s, NTS_KTAG_EDGE);
+#define NTS_K(RR)                                                             \
+  (grad_att ? k_gatv2_backward<RR, true> : k_gatv2_backward<RR, false>)
+  hipLaunchKernelGGL(R == 4 ? NTS_K(4) : R == 2 ? NTS_K(2) : NTS_K(1),
+                     dim3(grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                     p.ib->counter, grad_own, grad_att, grad_score, own_rows,
+                     nbr_rows, att, slope, nbr_indices, nbr_start, f, heads, C,
+                     G);
+#undef NTS_K
+  dbg_sync(s, "k_gatv2_backward");
 }
 
 void nts_weight_sum_heads(nts_stream *s, float *out, const float *weights,

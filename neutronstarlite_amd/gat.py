@@ -29,6 +29,11 @@ per pass and E×f messages still never materialize.  The chain is the one
 above through the *_heads entries of include/nts_hip.h, except that the CSR
 gather and the per-head edge dot run as two kernels (the fused gather-dot is
 single-head).  `attend` wraps forward/backward as a torch.autograd.Function.
+
+GATv2 (GATv2Layer, `attend_v2`): the score is att . leaky_relu(x_l[src] +
+x_r[dst]) per head, one f-wide edge pass and two backward walks of their own
+(nts_edge_gatv2_score, nts_edge_gatv2_backward); softmax, aggregation and the
+gradient with respect to the softmax are the heads entries above.
 """
 import numpy as np
 import torch
@@ -38,26 +43,17 @@ from .graph import Chunk
 from .ops import DeviceChunk, _u32_cuda
 
 
-class GATLayer:
-    """Attention-weighted aggregation on one chunk (whole graph on 1 GPU)."""
+class _EdgeLayer:
+    """What the attention layers on one chunk share: the constructor checks,
+    the device chunk, the stream wrappers and the CSC <-> CSR slot maps."""
 
-    def __init__(self, ch: Chunk, v: int, device, heads: int = 1,
-                 stable: bool = False, _heads_path: bool = False):
-        """heads = K attention heads over head-major column blocks.  With
-        heads == 1 the layer makes exactly the single-head calls.
-        stable=True runs the max-subtracted softmax (Stream.
-        edge_softmax_stable) on the layer's own stream wrapper, single-head
-        and heads path alike; the default is the reference's exp / sum exp,
-        which is NaN once a logit passes about 88.  The backward is the same.
-        _heads_path (private, for tools/bench_gat_heads.py) runs the heads
-        call chain at heads == 1 too: unfused CSR gather + edge dot."""
+    def _setup(self, ch: Chunk, v: int, device, heads, stable):
         if not isinstance(heads, int) or heads < 1:
             raise ValueError(f"heads must be a positive int, got {heads!r}")
         if not isinstance(stable, bool):
             raise ValueError(f"stable must be a bool, got {stable!r}")
         self.heads = heads
         self.stable = stable
-        self._heads_path = heads > 1 or _heads_path
         self.v = v
         self.np_ch = ch
         self.ch = DeviceChunk(ch, device)
@@ -100,6 +96,39 @@ class GATLayer:
         if self._soe is None:
             self._soe = torch.from_numpy(self._src_of_edge_np).to(self.device)
         return self._soe
+
+    @staticmethod
+    def _check_rows(name, t, rows, cols):
+        """The kernels take raw pointers: anything but a contiguous float32
+        device matrix of the expected shape raises before a launch."""
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+        if not t.is_cuda:
+            raise TypeError(f"{name} must be a device tensor")
+        if tuple(t.shape) != (rows, cols):
+            raise ValueError(
+                f"{name} must have shape ({rows}, {cols}), got {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+
+
+class GATLayer(_EdgeLayer):
+    """Attention-weighted aggregation on one chunk (whole graph on 1 GPU)."""
+
+    def __init__(self, ch: Chunk, v: int, device, heads: int = 1,
+                 stable: bool = False, _heads_path: bool = False):
+        """heads = K attention heads over head-major column blocks.  With
+        heads == 1 the layer makes exactly the single-head calls.
+        stable=True runs the max-subtracted softmax (Stream.
+        edge_softmax_stable) on the layer's own stream wrapper, single-head
+        and heads path alike; the default is the reference's exp / sum exp,
+        which is NaN once a logit passes about 88.  The backward is the same.
+        _heads_path (private, for tools/bench_gat_heads.py) runs the heads
+        call chain at heads == 1 too: unfused CSR gather + edge dot."""
+        self._setup(ch, v, device, heads, stable)
+        self._heads_path = heads > 1 or _heads_path
 
     def forward(self, h: torch.Tensor, s_src: torch.Tensor,
                 s_dst: torch.Tensor, negative_slope: float = 0.2):
@@ -200,22 +229,6 @@ class GATLayer:
         return grad_h, g_src[:, 0], g_dst[:, 0]
 
     # ---- multi-head path (heads = K > 1) ----
-    @staticmethod
-    def _check_rows(name, t, rows, cols):
-        """The kernels take raw pointers: anything but a contiguous float32
-        device matrix of the expected shape raises before a launch."""
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{name} must be a torch.Tensor")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {t.dtype}")
-        if not t.is_cuda:
-            raise TypeError(f"{name} must be a device tensor")
-        if tuple(t.shape) != (rows, cols):
-            raise ValueError(
-                f"{name} must have shape ({rows}, {cols}), got {tuple(t.shape)}")
-        if not t.is_contiguous():
-            raise ValueError(f"{name} must be contiguous")
-
     def _width(self, name, t):
         if not isinstance(t, torch.Tensor) or t.dim() != 2:
             raise ValueError(f"{name} must be a 2-d tensor")
@@ -321,3 +334,146 @@ def attend(h: torch.Tensor, s_src: torch.Tensor, s_dst: torch.Tensor,
     projections stay in torch, e.g. for K heads of C columns
     s_src = (h.view(V, K, C) * a_src).sum(-1) with a_src of shape [K, C]."""
     return _AttendFn.apply(h, s_src, s_dst, layer, negative_slope)
+
+
+class GATv2Layer(_EdgeLayer):
+    """GATv2 attention (Brody et al., "How Attentive are Graph Attention
+    Networks?") on one chunk: the non-linearity sits before the dot with the
+    attention vector,
+
+      score[e, k] = att[k] . leaky_relu(x_l[src(e), head k] + x_r[dst(e), head k])
+      alpha       = softmax of score over dst(e)'s in-edges, per head
+      y[d, c]     = sum_{e into d} alpha[e, c // C] * x_l[src(e), c]
+
+    so the score is no sum of two per-vertex scalars and runs as one f-wide
+    edge pass (nts_edge_gatv2_score); its backward is one walk over the CSC
+    and one over the CSR (nts_edge_gatv2_backward).  Softmax, aggregation
+    and the gradient with respect to alpha are the entries GATLayer's heads
+    path uses.  The [E, f] tensor x_l[src] + x_r[dst] never materializes."""
+
+    def __init__(self, ch: Chunk, v: int, device, heads: int = 1,
+                 stable: bool = False):
+        """heads = K heads over head-major column blocks (heads == 1: C = f);
+        stable=True runs the max-subtracted softmax, as for GATLayer."""
+        self._setup(ch, v, device, heads, stable)
+
+    def _check_inputs(self, x_l, x_r, att):
+        ch, K = self.ch, self.heads
+        if not isinstance(x_l, torch.Tensor) or x_l.dim() != 2:
+            raise ValueError("x_l must be a 2-d tensor")
+        f = int(x_l.shape[1])
+        if f < K or f % K != 0:
+            raise ValueError(
+                f"x_l has {f} columns, not a multiple of heads={K}")
+        self._check_rows("x_l", x_l, ch.src_n, f)
+        self._check_rows("x_r", x_r, ch.dst_n, f)
+        self._check_rows("att", att, K, f // K)
+        return f
+
+    def forward(self, x_l: torch.Tensor, x_r: torch.Tensor, att: torch.Tensor,
+                negative_slope: float = 0.2):
+        """x_l: [src_n, K*C], x_r: [dst_n, K*C], att: [K, C].  Returns
+        (y[dst_n, K*C], saved)."""
+        ch, st, E, K = self.ch, self.stream, self.E, self.heads
+        f = self._check_inputs(x_l, x_r, att)
+        dev = x_l.device
+        st.items_reuse(1)
+        score = torch.empty(E, K, device=dev)
+        st.edge_gatv2_score(
+            score.data_ptr(), x_r.data_ptr(), x_l.data_ptr(), att.data_ptr(),
+            negative_slope, ch.row_indices.data_ptr(),
+            ch.column_offset.data_ptr(), ch.src_s, ch.dst_n, E, f, K)
+        # per-(destination, head) softmax, dual-emitted in CSC (alpha) and
+        # CSR (alpha_csr) edge order; cache = output
+        alpha = torch.empty(E, K, device=dev)
+        alpha_csr = torch.empty(E, K, device=dev)
+        st.edge_softmax_forward_dual(
+            alpha.data_ptr(), alpha_csr.data_ptr(),
+            self._inv_perm_u32.data_ptr(), score.data_ptr(), alpha.data_ptr(),
+            ch.column_offset.data_ptr(), ch.dst_n, K)
+        y = torch.zeros(ch.dst_n, f, device=dev)
+        st.gather_by_dst_from_src_heads(
+            x_l.data_ptr(), y.data_ptr(), alpha.data_ptr(),
+            ch.row_indices.data_ptr(), ch.column_offset.data_ptr(),
+            ch.src_s, ch.src_e, ch.dst_s, ch.dst_e, E, ch.dst_n, f, K)
+        saved = {"x_l": x_l, "x_r": x_r, "att": att, "alpha": alpha,
+                 "alpha_csr": alpha_csr}
+        return y, saved
+
+    def backward(self, grad_y: torch.Tensor, saved,
+                 negative_slope: float = 0.2):
+        """Returns (grad_x_l[src_n, K*C], grad_x_r[dst_n, K*C],
+        grad_att[K, C])."""
+        ch, st, E, K = self.ch, self.stream, self.E, self.heads
+        x_l, x_r, att = saved["x_l"], saved["x_r"], saved["att"]
+        f = int(x_l.shape[1])
+        if not isinstance(grad_y, torch.Tensor) or grad_y.dim() != 2 \
+                or int(grad_y.shape[1]) != f:
+            raise ValueError("grad_y does not match the saved forward input")
+        self._check_rows("grad_y", grad_y, ch.dst_n, f)
+        dev = grad_y.device
+        st.items_reuse(1)
+        # through alpha: the aggregation's own gradient to x_l, and the
+        # per-head dot that is the gradient with respect to alpha
+        grad_xl = torch.zeros(ch.src_n, f, device=dev)
+        st.gather_by_src_from_dst_heads(
+            grad_y.data_ptr(), grad_xl.data_ptr(),
+            saved["alpha_csr"].data_ptr(), ch.row_offset.data_ptr(),
+            ch.column_indices.data_ptr(), ch.src_s, ch.src_e, ch.dst_s,
+            ch.dst_e, E, ch.src_n, f, K)
+        galpha = torch.empty(E, K, device=dev)
+        st.edge_dot_heads(galpha.data_ptr(), grad_y.data_ptr(),
+                          x_l.data_ptr(), ch.row_indices.data_ptr(),
+                          ch.column_offset.data_ptr(), ch.src_s, ch.dst_n, E,
+                          f, K)
+        # softmax backward without a leaky-relu mask (the GATv2 mask is
+        # per column, inside the two walks below), dual-emitted
+        gscore = torch.empty(E, K, device=dev)
+        gscore_csr = torch.empty(E, K, device=dev)
+        st.edge_softmax_backward_fused(
+            gscore.data_ptr(), gscore_csr.data_ptr(),
+            self._inv_perm_u32.data_ptr(), galpha.data_ptr(),
+            saved["alpha"].data_ptr(), None, negative_slope,
+            ch.column_offset.data_ptr(), ch.dst_n, K, dst_sum=None)
+        # CSC walk: own = x_r, nbr = x_l -> grad_x_r and grad_att
+        grad_xr = torch.zeros(ch.dst_n, f, device=dev)
+        grad_att = torch.zeros(K, f // K, device=dev)
+        st.edge_gatv2_backward(
+            grad_xr.data_ptr(), grad_att.data_ptr(), gscore.data_ptr(),
+            x_r.data_ptr(), x_l.data_ptr(), att.data_ptr(), negative_slope,
+            ch.column_offset.data_ptr(), ch.row_indices.data_ptr(), ch.src_s,
+            ch.dst_n, E, f, K)
+        # CSR walk: own = x_l, nbr = x_r, accumulated into grad_x_l
+        st.edge_gatv2_backward(
+            grad_xl.data_ptr(), None, gscore_csr.data_ptr(), x_l.data_ptr(),
+            x_r.data_ptr(), att.data_ptr(), negative_slope,
+            ch.row_offset.data_ptr(), ch.column_indices.data_ptr(), ch.dst_s,
+            ch.src_n, E, f, K)
+        return grad_xl, grad_xr, grad_att
+
+
+class _AttendV2Fn(torch.autograd.Function):
+    """torch.autograd bridge over GATv2Layer.forward/backward."""
+
+    @staticmethod
+    def forward(ctx, x_l, x_r, att, layer, negative_slope):
+        y, saved = layer.forward(x_l.detach(), x_r.detach(), att.detach(),
+                                 negative_slope)
+        ctx.layer, ctx.saved, ctx.slope = layer, saved, negative_slope
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        grad_xl, grad_xr, grad_att = ctx.layer.backward(
+            grad_y.contiguous(), ctx.saved, ctx.slope)
+        return grad_xl, grad_xr, grad_att, None, None
+
+
+def attend_v2(x_l: torch.Tensor, x_r: torch.Tensor, att: torch.Tensor,
+              layer: GATv2Layer, negative_slope: float = 0.2) -> torch.Tensor:
+    """Autograd-aware GATv2 aggregation on `layer`'s graph, differentiable in
+    x_l [src_n, K*C], x_r [dst_n, K*C] and att [K, C] (all float32,
+    contiguous, on the device; anything else raises before a launch).  The
+    projections stay in torch: x_l = x @ W_l, x_r = x @ W_r.  Weight sharing
+    (x_l is x_r) needs no special case: autograd adds the two gradients."""
+    return _AttendV2Fn.apply(x_l, x_r, att, layer, negative_slope)

@@ -124,6 +124,11 @@ def lib():
     l.nts_edge_dot_heads.argtypes = [_vp] + [_vp] * 5 + [_u32] * 5
     l.nts_weight_sum_heads.argtypes = [_vp] + [_vp] * 3 + [_u32] * 3
     l.nts_heads_dbg_general.argtypes = [_vp, _i32]
+    # GATv2 score and backward
+    l.nts_edge_gatv2_score.argtypes = (
+        [_vp] + [_vp] * 4 + [_c.c_float] + [_vp] * 2 + [_u32] * 5)
+    l.nts_edge_gatv2_backward.argtypes = (
+        [_vp] + [_vp] * 6 + [_c.c_float] + [_vp] * 2 + [_u32] * 5)
     l.nts_edge_softmax_stable.argtypes = [_vp, _i32]
     l.nts_edge_softmax_stable_last.argtypes = [_vp, _vp]
     # max / min aggregation
@@ -579,6 +584,30 @@ class Stream:
         check_heads(heads, heads)
         self._lib.nts_weight_sum_heads(self.h, _vp(out), _vp(weights),
                                        _vp(offset), batch, edges, heads)
+
+    # ---- GATv2: the f-wide per-edge score and its backward ----
+    def edge_gatv2_score(self, score, dst_rows, src_rows, att, slope,
+                         row_indices, column_offset, src_start, batch, edges,
+                         f, heads):
+        """score[e, k] = att[head k] . leaky_relu(dst_rows[dst] + src_rows[src])
+        over head k's columns, e in CSC order (overwrites)."""
+        check_heads(f, heads)
+        self._lib.nts_edge_gatv2_score(
+            self.h, _vp(score), _vp(dst_rows), _vp(src_rows), _vp(att), slope,
+            _vp(row_indices), _vp(column_offset), src_start, batch, edges, f,
+            heads)
+
+    def edge_gatv2_backward(self, grad_own, grad_att, grad_score, own_rows,
+                            nbr_rows, att, slope, offset, nbr_indices,
+                            nbr_start, batch, edges, f, heads):
+        """One walk over `offset` (CSC: own = x_r, nbr = x_l; CSR the other
+        way round) with grad_score in that order: grad_own += ..., and
+        grad_att += ... unless grad_att is None/0."""
+        check_heads(f, heads)
+        self._lib.nts_edge_gatv2_backward(
+            self.h, _vp(grad_own), _vp(grad_att), _vp(grad_score),
+            _vp(own_rows), _vp(nbr_rows), _vp(att), slope, _vp(offset),
+            _vp(nbr_indices), nbr_start, batch, edges, f, heads)
 
     # ---- max / min aggregation; op is checked here, the library aborts on
     # an invalid value ----

@@ -45,6 +45,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -1484,51 +1485,308 @@ __global__ void k_edge_items(const uint4 *__restrict__ items,
   }
 }
 
-/* edge softmax, two item-parallel passes over per-dst partial sums:
- * pass 1: out[e] = exp(in[e]) (fwd) or g*s (bwd), item-partial sums
- *         reduced once into sums[dst*f + r] by fp32 atomics;
- * pass 2: out[e] = exp/sum (fwd) or g*s - sum*s (bwd). */
-template <bool BACKWARD>
-__global__ void k_edge_softmax_sum(const uint4 *__restrict__ items,
-                                   const uint32_t *__restrict__ n_items_p,
-                                   float *__restrict__ out,
-                                   const float *__restrict__ in,
-                                   const float *__restrict__ cached,
-                                   float *__restrict__ sums, uint32_t f) {
-  const uint32_t n_items = *n_items_p;
-  const WaveId w = wave_id();
-  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
-    const Item im = load_item(items, it);
-    for (uint32_t r = 0; r < f; ++r) {
-      float part = 0.f;
-      for (uint32_t k = w.lane; k < im.cnt; k += 64) {
-        const uint64_t m = (uint64_t)(im.e0 + k) * f + r;
-        float v;
-        if (BACKWARD) v = in[m] * cached[m];
-        else v = __expf(in[m]);
-        out[m] = v;          /* stash pass-1 value; normalized in pass 2 */
-        part += v;
+/* t > 0 ? t : slope*t;  lrelu'(t) = t > 0 ? 1 : slope (slope at t == 0) */
+__device__ __forceinline__ float lrelu(float t, float slope) {
+  return t > 0.f ? t : slope * t;
+}
+
+/* ---- per-destination reductions over an item's [cnt, K] values ---- */
+/* Per-edge values are [E, K] row-major, per-vertex ones [rows, K]: K is the
+ * softmax's f, the attention's heads, 1 for one scalar per edge.  A wave
+ * takes an item and reduces each of its K columns.  Every such pass is
+ * k_edge_reduce over a lane layout, a value rule (what an edge's value is)
+ * and a reduce rule (what is kept per value and left per column).
+ *
+ * Lane layouts.  Strided, any K: column by column, lanes stride the item's
+ * edges, a 64-lane butterfly, lane 0 owns column k.  FLAT, K a power of two
+ * <= 64: lanes stride the item's cnt*K values in memory order (coalesced);
+ * 64 % K == 0, so a lane stays on column lane % K, the butterfly steps
+ * xor 32..K leave column k's result on lanes == k mod K, and lanes < K own
+ * column `lane`.  At one column the two are the same walk (lanes stride the
+ * edges, xor 32..1, lane 0 owns); it runs as the strided one at a
+ * compile-time K of 1 (KC), whose column loop and K-scaled indices fold
+ * away and whose edge counter is 32-bit — the registers of a hand-written
+ * scalar kernel (FLAT at K = 1 costs 5 to 8 VGPRs more for its 64-bit
+ * counter).
+ *
+ * The strided butterfly is the FLAT one at a span of 1: xor 32..1. */
+__device__ __forceinline__ float heads_lane_sum(float x, uint32_t K) {
+  for (uint32_t w = 32; w >= K; w >>= 1) x += __shfl_xor(x, w, 64);
+  return x;
+}
+__device__ __forceinline__ float heads_lane_max(float x, uint32_t K) {
+  for (uint32_t w = 32; w >= K; w >>= 1) x = fmaxf(x, __shfl_xor(x, w, 64));
+  return x;
+}
+
+/* val.column(slot) once per (item, column), slot = v*K + k; val(e, K, k, m)
+ * per value, m = e*K + k; red.add per value; red.put(acc, span, owner, slot,
+ * shared) per column, span the butterfly's last step */
+template <bool FLAT, int KC, class Value, class Reduce>
+__device__ __forceinline__ void reduce_item(const WaveId &w, const Item &im,
+                                            uint32_t K_run, Value &val,
+                                            const Reduce &red) {
+  const uint32_t K = KC ? (uint32_t)KC : K_run;
+  const uint64_t slot0 = (uint64_t)im.v * K;
+  if constexpr (FLAT) {
+    const uint32_t k = w.lane & (K - 1);
+    const uint32_t lgk = 31u - (uint32_t)__clz(K);
+    const uint64_t m0 = (uint64_t)im.e0 * K;
+    const uint64_t nel = (uint64_t)im.cnt * K;
+    val.column(slot0 + k);
+    typename Reduce::Acc acc = Reduce::empty();
+    for (uint64_t i = w.lane; i < nel; i += 64)
+      red.add(acc, val(im.e0 + (uint32_t)(i >> lgk), K, k, m0 + i), m0 + i,
+              im.shared);
+    red.put(acc, K, w.lane < K, slot0 + w.lane, im.shared);
+  } else {
+    for (uint32_t k = 0; k < K; ++k) {
+      val.column(slot0 + k);
+      typename Reduce::Acc acc = Reduce::empty();
+      for (uint32_t j = w.lane; j < im.cnt; j += 64) {
+        const uint32_t e = im.e0 + j;
+        const uint64_t m = (uint64_t)e * K + k;
+        red.add(acc, val(e, K, k, m), m, im.shared);
       }
-      part = wave_sum(part);
-      if (w.lane == 0) atomicAdd(&sums[(uint64_t)im.v * f + r], part);
+      red.put(acc, 1u, w.lane == 0, slot0 + k, im.shared);
     }
   }
 }
 
-/* Normalize pass.  Optional extras (GAT fusions):
+/* ---- value rules ---- */
+/* in[m]: a softmax score, or a weight to sum */
+struct EdgeIn {
+  const float *__restrict__ in;
+  __device__ void column(uint64_t) {}
+  __device__ float operator()(uint32_t, uint32_t, uint32_t, uint64_t m) const {
+    return in[m];
+  }
+};
+/* softmax backward: g * s */
+struct EdgeInCached {
+  const float *__restrict__ in, *__restrict__ cached;
+  __device__ void column(uint64_t) {}
+  __device__ float operator()(uint32_t, uint32_t, uint32_t, uint64_t m) const {
+    return in[m] * cached[m];
+  }
+};
+/* Fused GAT attention score: per edge and head
+ *   t = s_src[mirror_index[src], k] + s_dst[dst, k],
+ * stashes t (the leaky-relu input the backward mask needs) and applies the
+ * activation — replacing the separate scatter_src_mirror_to_msg +
+ * scatter_dst_to_msg kernels and the torch add/leaky elementwise passes (5
+ * full E-sized passes, with the exp and the sums of the reduce rule) by one. */
+struct EdgeScore {
+  float *__restrict__ m_sum_out;
+  const float *__restrict__ s_src, *__restrict__ s_dst;
+  const uint32_t *__restrict__ row_indices, *__restrict__ mirror_index;
+  float slope;
+  float sd;
+  __device__ void column(uint64_t slot) { sd = s_dst[slot]; }
+  __device__ float operator()(uint32_t e, uint32_t K, uint32_t k,
+                              uint64_t m) const {
+    const uint32_t src = row_indices[e];
+    const uint64_t row = mirror_index ? mirror_index[src] : src;
+    const float t = s_src[row * K + k] + sd;
+    m_sum_out[m] = t;
+    return lrelu(t, slope);
+  }
+};
+
+/* ---------------- stable (max-subtracted) edge softmax ---------------- */
+/* nts_edge_softmax_stable: the same two item-driven passes over the same
+ * bytes as the default.  Pass 1 stashes the activation a (not exp a) in out
+ * and leaves, per (destination, column or head), the pair (M, S) = (max a,
+ * sum exp(a - M)) in a stream-owned scratch; pass 2 writes exp(a - M) / S.
+ *
+ * A pair is one 64-bit word: reduce_key's ordered-uint map of M in the low
+ * half, S in the high half; the all-zero word of the memset is below every
+ * real key and is a sum of 0.
+ * An unsplit destination (one item): a lane keeps a running pair over the
+ * values it strides (one exp per value, nothing re-read at any NTS_SPLIT or
+ * K); M is a butterfly max, every lane rescales its sum to M once, S is the
+ * butterfly sum, and the pair is stored with a plain store, no atomic.
+ * A split destination: its items reduce their maxima in pass 1 and merge
+ * them with a u32 atomicMax on the key; the split-sum pass, which skips
+ * every unsplit item, then re-reads the split items' stash and adds
+ * sum exp(a - M) with the default's fp32 atomicAdd.  (A 64-bit
+ * compare-and-swap merge of whole pairs in pass 1 was measured and removed:
+ * DESIGN section 3.)  A score of -inf adds nothing anywhere, and an item of
+ * nothing but -inf leaves the slot alone (no exp(-inf + inf)). */
+struct MaxSum { float m, s; }; /* s = sum of exp(a - m); (-inf, 0) = nothing */
+
+__device__ __forceinline__ void ms_add(MaxSum &p, float a) {
+  if (a > p.m) {
+    p.s = p.s * __expf(p.m - a) + 1.f; /* first value: 0 * exp(-inf) + 1 */
+    p.m = a;
+  } else if (a > -INFINITY) {
+    p.s += __expf(a - p.m);
+  }
+}
+/* a lane's sum rescaled to the item's maximum (0 from a lane or an item that
+ * saw nothing but -inf) */
+__device__ __forceinline__ float ms_rescaled(const MaxSum &p, float Mi) {
+  return (p.m > -INFINITY) ? p.s * __expf(p.m - Mi) : 0.f;
+}
+
+/* reduce_key's monotone float -> uint map (never 0 for a non-NaN) */
+__device__ __forceinline__ uint32_t ms_key(float x) {
+  const uint32_t u = __float_as_uint(x);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float ms_unkey(uint32_t u) {
+  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
+}
+__device__ __forceinline__ unsigned long long ms_pack(float M, float S) {
+  return ((unsigned long long)__float_as_uint(S) << 32) | ms_key(M);
+}
+__device__ __forceinline__ MaxSum ms_unpack(unsigned long long x) {
+  return MaxSum{ms_unkey((uint32_t)x), __uint_as_float((uint32_t)(x >> 32))};
+}
+
+/* a value into a lane's pair; an item of a split destination needs the
+ * maximum only (its sum is the split-sum pass's) */
+__device__ __forceinline__ void ms_add(MaxSum &p, float a, bool maxonly) {
+  if (maxonly) p.m = fmaxf(p.m, a);
+  else ms_add(p, a);
+}
+
+/* one item's result into its destination's slot: the whole pair of an
+ * unsplit destination, the maximum of a split one's item */
+__device__ __forceinline__ void ms_put(unsigned long long *slot, float Mi,
+                                       float Si, bool shared) {
+  if (!(Mi > -INFINITY)) return;
+  if (shared) atomicMax(reinterpret_cast<uint32_t *>(slot), ms_key(Mi));
+  else *slot = ms_pack(Mi, Si);
+}
+
+/* the split-sum pass's value: exp(stash - M), M the destination's merged
+ * maximum */
+struct EdgeStashExp {
+  const float *out;
+  const unsigned long long *pairs;
+  float M;
+  __device__ void column(uint64_t slot) { M = ms_unkey((uint32_t)pairs[slot]); }
+  __device__ float operator()(uint32_t, uint32_t, uint32_t, uint64_t m) const {
+    return __expf(out[m] - M);
+  }
+};
+
+/* ---- reduce rules ---- */
+/* Default softmax pass 1: stash v = exp(a) (forward) or a (backward) in out
+ * for pass 2, item-partial sums reduced once into sums[slot] by fp32
+ * atomics.  No max subtraction: reference semantics,
+ * ntsCUDADistKernel.cuh:192. */
+template <bool EXP>
+struct SumToSums {
+  float *__restrict__ out, *__restrict__ sums;
+  using Acc = float;
+  __device__ static Acc empty() { return 0.f; }
+  __device__ static bool wants(const Item &) { return true; }
+  __device__ void add(Acc &part, float a, uint64_t m, bool) const {
+    const float v = EXP ? __expf(a) : a;
+    out[m] = v;
+    part += v;
+  }
+  __device__ void put(Acc part, uint32_t span, bool owner, uint64_t slot,
+                      bool) const {
+    part = heads_lane_sum(part, span);
+    if (owner) atomicAdd(&sums[slot], part);
+  }
+};
+/* stable pass 1: stash a, leave the (M, S) pair (the maximum alone from an
+ * item of a split destination) */
+struct MaxSumToPairs {
+  float *__restrict__ out;
+  unsigned long long *__restrict__ pairs;
+  using Acc = MaxSum;
+  __device__ static Acc empty() { return MaxSum{-INFINITY, 0.f}; }
+  __device__ static bool wants(const Item &) { return true; }
+  __device__ void add(Acc &p, float a, uint64_t m, bool shared) const {
+    out[m] = a;
+    ms_add(p, a, shared);
+  }
+  __device__ void put(const Acc &p, uint32_t span, bool owner, uint64_t slot,
+                      bool shared) const {
+    const float Mi = heads_lane_max(p.m, span);
+    const float Si = heads_lane_sum(ms_rescaled(p, Mi), span);
+    if (owner) ms_put(&pairs[slot], Mi, Si, shared);
+  }
+};
+/* between the stable passes: a split destination's items add their sums to
+ * its S */
+struct SplitSumToPairs {
+  unsigned long long *pairs;
+  using Acc = float;
+  __device__ static Acc empty() { return 0.f; }
+  __device__ static bool wants(const Item &im) { return im.shared; }
+  __device__ void add(Acc &part, float v, uint64_t, bool) const { part += v; }
+  __device__ void put(Acc part, uint32_t span, bool owner, uint64_t slot,
+                      bool) const {
+    part = heads_lane_sum(part, span);
+    if (owner && part > 0.f)
+      atomicAdd(reinterpret_cast<float *>(&pairs[slot]) + 1, part);
+  }
+};
+/* out[v*K + k] += the column's sum.  With EdgeIn this is the per-vertex sum
+ * of per-edge weights — the f=1 "aggregate an all-ones input with weights w"
+ * reduction (GAT's attention-scalar source gradient) done natively: lanes
+ * stride the item's edges and wave-reduce, instead of the f-wide gather
+ * kernel where 15/16 lanes idle at f=1 (measured 1.9 ms -> this shape
+ * streams w + offsets only).  Hub items merge by fp32 atomics like the
+ * gather. */
+struct SumToOut {
+  float *__restrict__ out;
+  using Acc = float;
+  __device__ static Acc empty() { return 0.f; }
+  __device__ static bool wants(const Item &) { return true; }
+  __device__ void add(Acc &part, float v, uint64_t, bool) const { part += v; }
+  __device__ void put(Acc part, uint32_t span, bool owner, uint64_t slot,
+                      bool shared) const {
+    part = heads_lane_sum(part, span);
+    if (owner) {
+      if (shared) atomicAdd(&out[slot], part);
+      else out[slot] += part;
+    }
+  }
+};
+
+template <bool FLAT, int KC, class Value, class Reduce>
+__global__ void k_edge_reduce(const uint4 *__restrict__ items,
+                              const uint32_t *__restrict__ n_items_p,
+                              Value val, const Reduce red, uint32_t K) {
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
+    const Item im = load_item(items, it);
+    if (!Reduce::wants(im)) continue;
+    reduce_item<FLAT, KC>(w, im, K, val, red);
+  }
+}
+
+/* Normalize pass (pass 2 of the edge softmax):
+ *   NORM_FWD     out = out / sum                 (out holds exp a)
+ *   NORM_BWD     out = out - sum * cached        (out holds g * s)
+ *   NORM_STABLE  out = exp(out - M) / S          (out holds a)
+ * Optional extras (GAT fusions):
  *  - out2/pos2: ALSO write each value to out2[pos2[m]] — with pos2 = the
  *    CSC->CSR slot map this emits the result in CSR edge order in the same
  *    pass, replacing a separate nts_permute_f32 kernel (2x ~2 ms/step on
  *    the Reddit-scale GAT config).
- *  - lrelu_in/slope (BACKWARD only): multiply by the leaky-relu derivative
+ *  - lrelu_in/slope (NORM_BWD only): multiply by the leaky-relu derivative
  *    (lrelu_in[m] > 0 ? 1 : slope), fusing the attention activation's
  *    backward elementwise pass. */
-template <bool BACKWARD>
+enum NormMode { NORM_FWD, NORM_BWD, NORM_STABLE };
+template <NormMode MODE>
+using NormSlot =
+    std::conditional_t<MODE == NORM_STABLE, unsigned long long, float>;
+
+template <NormMode MODE>
 __global__ void k_edge_softmax_norm(const uint4 *__restrict__ items,
                                     const uint32_t *__restrict__ n_items_p,
                                     float *__restrict__ out,
                                     const float *__restrict__ cached,
-                                    const float *__restrict__ sums,
+                                    const NormSlot<MODE> *__restrict__ slots,
                                     float *__restrict__ out2,
                                     const uint32_t *__restrict__ pos2,
                                     const float *__restrict__ lrelu_in,
@@ -1546,13 +1804,16 @@ __global__ void k_edge_softmax_norm(const uint4 *__restrict__ items,
       const uint32_t e = e0 + (uint32_t)(i / f);
       const uint32_t r = (uint32_t)(i % f);
       const uint64_t m = (uint64_t)e * f + r;
-      const float sum = sums[(uint64_t)d * f + r];
+      const NormSlot<MODE> slot = slots[(uint64_t)d * f + r];
       float v;
-      if (BACKWARD) {
-        v = out[m] - sum * cached[m];
+      if constexpr (MODE == NORM_BWD) {
+        v = out[m] - slot * cached[m];
         if (lrelu_in) v *= (lrelu_in[m] > 0.f) ? 1.f : slope;
+      } else if constexpr (MODE == NORM_STABLE) {
+        const MaxSum q = ms_unpack(slot);
+        v = __expf(out[m] - q.m) / q.s;
       } else {
-        v = out[m] / sum;
+        v = out[m] / slot;
       }
       out[m] = v;
       if (out2) out2[(uint64_t)pos2[e] * f + r] = v; /* pos2: per-edge map */
@@ -1564,69 +1825,6 @@ __global__ void k_edge_softmax_norm(const uint4 *__restrict__ items,
        * so one fp32 atomic per (item, wave), hub-safe */
       gsum = wave_sum(gsum);
       if (w.lane == 0) atomicAdd(&dst_accum[d], gsum);
-    }
-  }
-}
-
-/* Fused GAT attention forward, pass 1 (f==1 attention scalars): computes
- * per edge  m = s_src[mirror_index[src]] + s_dst[dst],  stashes m (the
- * leaky-relu input the backward mask needs), applies the activation and
- * exp, and accumulates the per-destination partial sums — replacing the
- * separate scatter_src_mirror_to_msg + scatter_dst_to_msg kernels and the
- * torch add/leaky elementwise passes (5 full E-sized passes) with one.
- * Pass 2 is the shared normalize kernel (dual-order emission). */
-__global__ void k_edge_att_sum(const uint4 *__restrict__ items,
-                               const uint32_t *__restrict__ n_items_p,
-                               float *__restrict__ out /* exp stash */,
-                               float *__restrict__ m_sum_out,
-                               const float *__restrict__ s_src,
-                               const float *__restrict__ s_dst,
-                               const uint32_t *__restrict__ row_indices,
-                               const uint32_t *__restrict__ mirror_index,
-                               float slope, float *__restrict__ sums) {
-  const uint32_t n_items = *n_items_p;
-  const WaveId w = wave_id();
-  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
-    const Item im = load_item(items, it);
-    const uint32_t d = im.v;
-    const float sd = s_dst[d];
-    float part = 0.f;
-    for (uint32_t k = w.lane; k < im.cnt; k += 64) {
-      const uint32_t e = im.e0 + k;
-      const uint32_t src = row_indices[e];
-      const float m = s_src[mirror_index ? mirror_index[src] : src] + sd;
-      m_sum_out[e] = m;
-      const float a = (m > 0.f) ? m : slope * m;
-      const float v = __expf(a); /* no max subtraction: reference semantics,
-                                    ntsCUDADistKernel.cuh:192 */
-      out[e] = v;
-      part += v;
-    }
-    part = wave_sum(part);
-    if (w.lane == 0) atomicAdd(&sums[d], part);
-  }
-}
-
-/* per-vertex sum of per-edge scalars: out[v] = sum_{e in item(v)} w[e] —
- * the f=1 "aggregate an all-ones input with weights w" reduction (GAT's
- * attention-scalar source gradient) done natively: lanes stride the item's
- * edges and wave-reduce, instead of the f-wide gather kernel where 15/16
- * lanes idle at f=1 (measured 1.9 ms -> this shape streams w + offsets
- * only).  Hub items merge by fp32 atomics like the gather. */
-__global__ void k_weight_sum(const uint4 *__restrict__ items,
-                             const uint32_t *__restrict__ n_items_p,
-                             float *__restrict__ out,
-                             const float *__restrict__ weights) {
-  const uint32_t n_items = *n_items_p;
-  const WaveId w = wave_id();
-  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
-    const Item im = load_item(items, it);
-    float part = 0.f;
-    for (uint32_t k = w.lane; k < im.cnt; k += 64) part += weights[im.e0 + k];
-    part = wave_sum(part);
-    if (w.lane == 0) {
-      if (im.shared) atomicAdd(&out[im.v], part);
-      else out[im.v] += part;
     }
   }
 }
@@ -1680,404 +1878,65 @@ __global__ void k_edge_dot(const uint4 *__restrict__ items,
   }
 }
 
-/* ---------------- multi-head edge kernels ---------------- */
-/* Per-edge values are [E, K] row-major, per-vertex scalars [rows, K].  Each
- * kernel comes in two forms.  The general one, for any K, is the loop order
- * of k_edge_softmax_sum: for each head, lanes stride the item's edges,
- * wave_sum, one atomic per (item, head).  FLAT, for K a power of two <= 64:
- * lanes stride the item's cnt*K values in memory order (coalesced); 64 % K
- * == 0, so a lane stays on head lane % K, and the butterfly steps xor 32..K
- * leave head k's sum on lanes == k mod K. */
-__device__ __forceinline__ float heads_lane_sum(float x, uint32_t K) {
-  for (uint32_t w = 32; w >= K; w >>= 1) x += __shfl_xor(x, w, 64);
-  return x;
+/* ---- per-edge reductions over a row pair, K heads of C columns ---- */
+/* out[e*K + k] = sum over head k's C columns j of term(own[d, j], nbr[src, j]).
+ * The term is a rule struct: the per-head dot, or the GATv2 score, which
+ * brings a third operand per column. */
+template <int R>
+__device__ __forceinline__ void load_cols(const float *p, float (&x)[R]) {
+  if constexpr (R == 1) x[0] = p[0];
+  else load_lane<R>(p, x);
 }
-
-/* attention forward, pass 1, K heads (k_edge_att_sum's twin) */
-template <bool FLAT>
-__global__ void k_edge_att_sum_heads(const uint4 *__restrict__ items,
-                                     const uint32_t *__restrict__ n_items_p,
-                                     float *__restrict__ out /* exp stash */,
-                                     float *__restrict__ m_sum_out,
-                                     const float *__restrict__ s_src,
-                                     const float *__restrict__ s_dst,
-                                     const uint32_t *__restrict__ row_indices,
-                                     const uint32_t *__restrict__ mirror_index,
-                                     float slope, float *__restrict__ sums,
-                                     uint32_t K) {
-  const uint32_t n_items = *n_items_p;
-  const WaveId w = wave_id();
-  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
-    const Item im = load_item(items, it);
-    const uint32_t d = im.v;
-    if constexpr (FLAT) {
-      const uint32_t k = w.lane & (K - 1);
-      const uint32_t lgk = 31u - (uint32_t)__clz(K);
-      const float sd = s_dst[(uint64_t)d * K + k];
-      const uint64_t m0 = (uint64_t)im.e0 * K;
-      const uint64_t nel = (uint64_t)im.cnt * K;
-      float part = 0.f;
-      for (uint64_t i = w.lane; i < nel; i += 64) {
-        const uint32_t src = row_indices[im.e0 + (uint32_t)(i >> lgk)];
-        const uint64_t row = mirror_index ? mirror_index[src] : src;
-        const float m = s_src[row * K + k] + sd;
-        m_sum_out[m0 + i] = m;
-        const float a = (m > 0.f) ? m : slope * m;
-        const float v = __expf(a); /* no max subtraction, as k_edge_att_sum */
-        out[m0 + i] = v;
-        part += v;
-      }
-      part = heads_lane_sum(part, K);
-      if (w.lane < K) atomicAdd(&sums[(uint64_t)d * K + w.lane], part);
-    } else {
-      for (uint32_t k = 0; k < K; ++k) {
-        const float sd = s_dst[(uint64_t)d * K + k];
-        float part = 0.f;
-        for (uint32_t j = w.lane; j < im.cnt; j += 64) {
-          const uint32_t e = im.e0 + j;
-          const uint32_t src = row_indices[e];
-          const uint64_t row = mirror_index ? mirror_index[src] : src;
-          const float m = s_src[row * K + k] + sd;
-          m_sum_out[(uint64_t)e * K + k] = m;
-          const float a = (m > 0.f) ? m : slope * m;
-          const float v = __expf(a);
-          out[(uint64_t)e * K + k] = v;
-          part += v;
-        }
-        part = wave_sum(part);
-        if (w.lane == 0) atomicAdd(&sums[(uint64_t)d * K + k], part);
-      }
-    }
-  }
-}
-
-/* out[v*K + k] += sum over v's edges of weights[e*K + k] (k_weight_sum's
- * twin; split vertices merge by atomics) */
-template <bool FLAT>
-__global__ void k_weight_sum_heads(const uint4 *__restrict__ items,
-                                   const uint32_t *__restrict__ n_items_p,
-                                   float *__restrict__ out,
-                                   const float *__restrict__ weights,
-                                   uint32_t K) {
-  const uint32_t n_items = *n_items_p;
-  const WaveId w = wave_id();
-  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
-    const Item im = load_item(items, it);
-    const float *wp = weights + (uint64_t)im.e0 * K;
-    float *o = out + (uint64_t)im.v * K;
-    if constexpr (FLAT) {
-      const uint64_t nel = (uint64_t)im.cnt * K;
-      float part = 0.f;
-      for (uint64_t i = w.lane; i < nel; i += 64) part += wp[i];
-      part = heads_lane_sum(part, K);
-      if (w.lane < K) {
-        if (im.shared) atomicAdd(&o[w.lane], part);
-        else o[w.lane] += part;
-      }
-    } else {
-      for (uint32_t k = 0; k < K; ++k) {
-        float part = 0.f;
-        for (uint32_t j = w.lane; j < im.cnt; j += 64)
-          part += wp[(uint64_t)j * K + k];
-        part = wave_sum(part);
-        if (w.lane == 0) {
-          if (im.shared) atomicAdd(&o[k], part);
-          else o[k] += part;
-        }
-      }
-    }
-  }
-}
-
-/* ---------------- stable (max-subtracted) edge softmax ---------------- */
-/* nts_edge_softmax_stable: the twins of k_edge_softmax_sum<false>,
- * k_edge_att_sum, both forms of k_edge_att_sum_heads and
- * k_edge_softmax_norm<false>, same two item-driven passes over the same
- * bytes.  Pass 1 stashes the activation a (not exp a) in out and leaves, per
- * (destination, column or head), the pair (M, S) = (max a, sum exp(a - M))
- * in a stream-owned scratch; pass 2 writes exp(a - M) / S.
- *
- * A pair is one 64-bit word: reduce_key's ordered-uint map of M in the low
- * half, S in the high half; the all-zero word of the memset is below every
- * real key and is a sum of 0.
- * An unsplit destination (one item): a lane keeps a running pair over the
- * values it strides (one exp per value, nothing re-read at any NTS_SPLIT or
- * K); M is a butterfly max, every lane rescales its sum to M once, S is the
- * butterfly sum, and the pair is stored with a plain store, no atomic.
- * A split destination: its items reduce their maxima in pass 1 and merge
- * them with a u32 atomicMax on the key; k_edge_softmax_splitsum, which skips
- * every unsplit item, then re-reads the split items' stash and adds
- * sum exp(a - M) with the default's fp32 atomicAdd.  (A 64-bit
- * compare-and-swap merge of whole pairs in pass 1 was measured and removed:
- * DESIGN section 3.)  A score of -inf adds nothing anywhere, and an item of
- * nothing but -inf leaves the slot alone (no exp(-inf + inf)). */
-struct MaxSum { float m, s; }; /* s = sum of exp(a - m); (-inf, 0) = nothing */
-
-__device__ __forceinline__ void ms_add(MaxSum &p, float a) {
-  if (a > p.m) {
-    p.s = p.s * __expf(p.m - a) + 1.f; /* first value: 0 * exp(-inf) + 1 */
-    p.m = a;
-  } else if (a > -INFINITY) {
-    p.s += __expf(a - p.m);
-  }
-}
-
-__device__ __forceinline__ float wave_max(float x) {
+/* a * b */
+struct DotTerm {
+  template <int R>
+  __device__ void load(float (&x)[R], uint32_t) const {
 #pragma unroll
-  for (int w = 32; w >= 1; w >>= 1) x = fmaxf(x, __shfl_xor(x, w, 64));
-  return x;
-}
-/* heads_lane_sum's steps: head k's max on lanes == k mod K */
-__device__ __forceinline__ float heads_lane_max(float x, uint32_t K) {
-  for (uint32_t w = 32; w >= K; w >>= 1) x = fmaxf(x, __shfl_xor(x, w, 64));
-  return x;
-}
-/* a lane's sum rescaled to the item's maximum (0 from a lane or an item that
- * saw nothing but -inf) */
-__device__ __forceinline__ float ms_rescaled(const MaxSum &p, float Mi) {
-  return (p.m > -INFINITY) ? p.s * __expf(p.m - Mi) : 0.f;
-}
-
-/* reduce_key's monotone float -> uint map (never 0 for a non-NaN) */
-__device__ __forceinline__ uint32_t ms_key(float x) {
-  const uint32_t u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ms_unkey(uint32_t u) {
-  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-__device__ __forceinline__ unsigned long long ms_pack(float M, float S) {
-  return ((unsigned long long)__float_as_uint(S) << 32) | ms_key(M);
-}
-__device__ __forceinline__ MaxSum ms_unpack(unsigned long long x) {
-  return MaxSum{ms_unkey((uint32_t)x), __uint_as_float((uint32_t)(x >> 32))};
-}
-
-/* a value into a lane's pair; an item of a split destination needs the
- * maximum only (its sum is k_edge_softmax_splitsum's) */
-__device__ __forceinline__ void ms_add(MaxSum &p, float a, bool maxonly) {
-  if (maxonly) p.m = fmaxf(p.m, a);
-  else ms_add(p, a);
-}
-
-/* one item's result into its destination's slot: the whole pair of an
- * unsplit destination, the maximum of a split one's item */
-__device__ __forceinline__ void ms_put(unsigned long long *slot, float Mi,
-                                       float Si, bool shared) {
-  if (!(Mi > -INFINITY)) return;
-  if (shared) atomicMax(reinterpret_cast<uint32_t *>(slot), ms_key(Mi));
-  else *slot = ms_pack(Mi, Si);
-}
-
-/* Between the passes: an item of a split destination re-reads its stash and adds
- * sum exp(a - M) to its destination's S with the default's fp32 atomicAdd.
- * FLAT (f a power of two <= 64) as k_edge_att_sum_heads. */
-template <bool FLAT>
-__global__ void k_edge_softmax_splitsum(const uint4 *__restrict__ items,
-                                        const uint32_t *__restrict__ n_items_p,
-                                        const float *__restrict__ out,
-                                        unsigned long long *__restrict__ pairs,
-                                        uint32_t f) {
-  const uint32_t n_items = *n_items_p;
-  const WaveId w = wave_id();
-  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
-    const Item im = load_item(items, it);
-    if (!im.shared) continue;
-    unsigned long long *slots = pairs + (uint64_t)im.v * f;
-    if constexpr (FLAT) {
-      const uint32_t k = w.lane & (f - 1);
-      const float M = ms_unkey((uint32_t)slots[k]);
-      const float *o = out + (uint64_t)im.e0 * f;
-      const uint64_t nel = (uint64_t)im.cnt * f;
-      float part = 0.f;
-      for (uint64_t i = w.lane; i < nel; i += 64) part += __expf(o[i] - M);
-      part = heads_lane_sum(part, f);
-      if (w.lane < f && part > 0.f)
-        atomicAdd(reinterpret_cast<float *>(&slots[w.lane]) + 1, part);
-    } else {
-      for (uint32_t r = 0; r < f; ++r) {
-        const float M = ms_unkey((uint32_t)slots[r]);
-        float part = 0.f;
-        for (uint32_t k = w.lane; k < im.cnt; k += 64)
-          part += __expf(out[(uint64_t)(im.e0 + k) * f + r] - M);
-        part = wave_sum(part);
-        if (w.lane == 0 && part > 0.f)
-          atomicAdd(reinterpret_cast<float *>(&slots[r]) + 1, part);
-      }
-    }
+    for (int j = 0; j < R; ++j) x[j] = 0.f; /* no third operand */
   }
-}
-
-/* softmax forward, pass 1 (k_edge_softmax_sum<false>'s twin) */
-__global__ void k_edge_softmax_maxsum(const uint4 *__restrict__ items,
-                                      const uint32_t *__restrict__ n_items_p,
-                                      float *__restrict__ out,
-                                      const float *__restrict__ in,
-                                      unsigned long long *__restrict__ pairs,
-                                      uint32_t f) {
-  const uint32_t n_items = *n_items_p;
-  const WaveId w = wave_id();
-  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
-    const Item im = load_item(items, it);
-    const bool maxonly = im.shared;
-    for (uint32_t r = 0; r < f; ++r) {
-      MaxSum p{-INFINITY, 0.f};
-      for (uint32_t k = w.lane; k < im.cnt; k += 64) {
-        const uint64_t m = (uint64_t)(im.e0 + k) * f + r;
-        const float a = in[m];
-        out[m] = a;          /* stash the score; normalized in pass 2 */
-        ms_add(p, a, maxonly);
-      }
-      const float Mi = wave_max(p.m);
-      const float Si = wave_sum(ms_rescaled(p, Mi));
-      if (w.lane == 0)
-        ms_put(&pairs[(uint64_t)im.v * f + r], Mi, Si, im.shared);
-    }
+  __device__ float operator()(float, float a, float b, float acc) const {
+    return fmaf(a, b, acc);
   }
-}
-
-/* pass 2 (k_edge_softmax_norm<false>'s twin): out = exp(out - M) / S, also
- * emitted at out2[pos2[e]] */
-__global__ void k_edge_softmax_norm_stable(
-    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    float *__restrict__ out, const unsigned long long *__restrict__ pairs,
-    float *__restrict__ out2, const uint32_t *__restrict__ pos2, uint32_t f) {
-  const uint32_t n_items = *n_items_p;
-  const WaveId w = wave_id();
-  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
-    const Item im = load_item(items, it);
-    const uint32_t d = im.v, e0 = im.e0;
-    const uint64_t nel = (uint64_t)im.cnt * f;
-    for (uint64_t i = w.lane; i < nel; i += 64) {
-      const uint32_t e = e0 + (uint32_t)(i / f);
-      const uint32_t r = (uint32_t)(i % f);
-      const uint64_t m = (uint64_t)e * f + r;
-      const MaxSum q = ms_unpack(pairs[(uint64_t)d * f + r]);
-      const float v = __expf(out[m] - q.m) / q.s;
-      out[m] = v;
-      if (out2) out2[(uint64_t)pos2[e] * f + r] = v;
-    }
+};
+/* att[j] * lrelu(a + b): a + b is ONE fp32 add of the two loaded values */
+struct Gatv2Term {
+  const float *__restrict__ att;
+  float slope;
+  template <int R>
+  __device__ void load(float (&x)[R], uint32_t col) const {
+    load_cols<R>(att + col, x);
   }
-}
-
-/* attention forward, pass 1 (k_edge_att_sum's twin) */
-__global__ void k_edge_att_maxsum(const uint4 *__restrict__ items,
-                                  const uint32_t *__restrict__ n_items_p,
-                                  float *__restrict__ out /* a stash */,
-                                  float *__restrict__ m_sum_out,
-                                  const float *__restrict__ s_src,
-                                  const float *__restrict__ s_dst,
-                                  const uint32_t *__restrict__ row_indices,
-                                  const uint32_t *__restrict__ mirror_index,
-                                  float slope,
-                                  unsigned long long *__restrict__ pairs) {
-  const uint32_t n_items = *n_items_p;
-  const WaveId w = wave_id();
-  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
-    const Item im = load_item(items, it);
-    const bool maxonly = im.shared;
-    const uint32_t d = im.v;
-    const float sd = s_dst[d];
-    MaxSum p{-INFINITY, 0.f};
-    for (uint32_t k = w.lane; k < im.cnt; k += 64) {
-      const uint32_t e = im.e0 + k;
-      const uint32_t src = row_indices[e];
-      const float m = s_src[mirror_index ? mirror_index[src] : src] + sd;
-      m_sum_out[e] = m;
-      const float a = (m > 0.f) ? m : slope * m;
-      out[e] = a;
-      ms_add(p, a, maxonly);
-    }
-    const float Mi = wave_max(p.m);
-    const float Si = wave_sum(ms_rescaled(p, Mi));
-    if (w.lane == 0) ms_put(&pairs[d], Mi, Si, im.shared);
+  __device__ float operator()(float x, float a, float b, float acc) const {
+    return fmaf(x, lrelu(a + b, slope), acc);
   }
-}
+};
 
-/* attention forward, pass 1, K heads (k_edge_att_sum_heads' twin) */
-template <bool FLAT>
-__global__ void k_edge_att_maxsum_heads(
-    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    float *__restrict__ out /* a stash */, float *__restrict__ m_sum_out,
-    const float *__restrict__ s_src, const float *__restrict__ s_dst,
-    const uint32_t *__restrict__ row_indices,
-    const uint32_t *__restrict__ mirror_index, float slope,
-    unsigned long long *__restrict__ pairs, uint32_t K) {
-  const uint32_t n_items = *n_items_p;
-  const WaveId w = wave_id();
-  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
-    const Item im = load_item(items, it);
-    const bool maxonly = im.shared;
-    const uint32_t d = im.v;
-    if constexpr (FLAT) {
-      const uint32_t k = w.lane & (K - 1);
-      const uint32_t lgk = 31u - (uint32_t)__clz(K);
-      const float sd = s_dst[(uint64_t)d * K + k];
-      const uint64_t m0 = (uint64_t)im.e0 * K;
-      const uint64_t nel = (uint64_t)im.cnt * K;
-      MaxSum p{-INFINITY, 0.f};
-      for (uint64_t i = w.lane; i < nel; i += 64) {
-        const uint32_t src = row_indices[im.e0 + (uint32_t)(i >> lgk)];
-        const uint64_t row = mirror_index ? mirror_index[src] : src;
-        const float m = s_src[row * K + k] + sd;
-        m_sum_out[m0 + i] = m;
-        const float a = (m > 0.f) ? m : slope * m;
-        out[m0 + i] = a;
-        ms_add(p, a, maxonly);
-      }
-      const float Mi = heads_lane_max(p.m, K);
-      const float Si = heads_lane_sum(ms_rescaled(p, Mi), K);
-      if (w.lane < K)
-        ms_put(&pairs[(uint64_t)d * K + w.lane], Mi, Si, im.shared);
-    } else {
-      for (uint32_t k = 0; k < K; ++k) {
-        const float sd = s_dst[(uint64_t)d * K + k];
-        MaxSum p{-INFINITY, 0.f};
-        for (uint32_t j = w.lane; j < im.cnt; j += 64) {
-          const uint32_t e = im.e0 + j;
-          const uint32_t src = row_indices[e];
-          const uint64_t row = mirror_index ? mirror_index[src] : src;
-          const float m = s_src[row * K + k] + sd;
-          m_sum_out[(uint64_t)e * K + k] = m;
-          const float a = (m > 0.f) ? m : slope * m;
-          out[(uint64_t)e * K + k] = a;
-          ms_add(p, a, maxonly);
-        }
-        const float Mi = wave_max(p.m);
-        const float Si = wave_sum(ms_rescaled(p, Mi));
-        if (w.lane == 0)
-          ms_put(&pairs[(uint64_t)d * K + k], Mi, Si, im.shared);
-      }
-    }
-  }
-}
-
-/* per-head edge dot: out[e*K + k] = dot over head k's C columns.
- * The general form runs a wave per (edge, head): lanes stride the head's C
+/* The general form runs a wave per (edge, head): lanes stride the head's C
  * columns, wave_sum (64 - C lanes idle when C < 64).
- * k_edge_dot_heads_seg, for C a power of two <= 64*R: a lane holds R
- * consecutive columns (one dwordxR load: 4, 2 or 1 by C and the pointers'
- * alignment), so a head is an aligned segment of L = C/R lanes and a row is
- * G = f/R lanes (at most 64 per step); 64/G edges share a wave.  The lane
- * multiplies its R columns, a log2(L)-step butterfly sums each segment, and
- * the segment's first lane writes.  Lanes past the row's end and edge slots
- * past the item's end load a clamped (valid) address and are never written:
- * segments lie inside one head and one lane group, so what such lanes hold
- * never meets a live sum. */
+ * k_edge_pair_seg, for C a power of two <= 64*R: a lane holds R consecutive
+ * columns (one dwordxR load: 4, 2 or 1 by C and the pointers' alignment),
+ * so a head is an aligned segment of L = C/R lanes and a row is G = f/R
+ * lanes (at most 64 per step); 64/G edges share a wave.  The lane reduces
+ * its R columns (the term's own operand is loaded once per (item, slab)
+ * beside the own-row columns), a log2(L)-step butterfly sums each segment,
+ * and the segment's first lane writes.  Lanes past the row's end and edge
+ * slots past the item's end load a clamped (valid) address and are never
+ * written: segments lie inside one head and one lane group, so what such
+ * lanes hold never meets a live sum. */
 __device__ __forceinline__ float seg_sum(float x, uint32_t L) {
   for (uint32_t w = L >> 1; w >= 1; w >>= 1) x += __shfl_xor(x, w, 64);
   return x;
 }
 
-template <int R>
-__global__ void k_edge_dot_heads_seg(const uint4 *__restrict__ items,
-                                     const uint32_t *__restrict__ n_items_p,
-                                     float *__restrict__ out,
-                                     const float *__restrict__ dst_rows,
-                                     const float *__restrict__ src_rows,
-                                     const uint32_t *__restrict__ row_indices,
-                                     uint32_t src_start, uint32_t f,
-                                     uint32_t K, uint32_t C, uint32_t G) {
+template <int R, class Term>
+__global__ void k_edge_pair_seg(const uint4 *__restrict__ items,
+                                const uint32_t *__restrict__ n_items_p,
+                                float *__restrict__ out,
+                                const float *__restrict__ dst_rows,
+                                const float *__restrict__ src_rows,
+                                const uint32_t *__restrict__ row_indices,
+                                uint32_t src_start, uint32_t f, uint32_t K,
+                                uint32_t C, uint32_t G, const Term term) {
   const uint32_t n_items = *n_items_p;
   const WaveId w = wave_id();
   const uint32_t L = C / R;          /* lanes per head */
@@ -2093,23 +1952,22 @@ __global__ void k_edge_dot_heads_seg(const uint4 *__restrict__ items,
       const uint32_t cc = live ? col : 0u;
       const bool writer = live && (gl & (L - 1)) == 0;
       const uint32_t head = cc / C;
-      float av[R];
-      if constexpr (R == 1) av[0] = dst_rows[(uint64_t)im.v * f + cc];
-      else load_lane<R>(dst_rows + (uint64_t)im.v * f + cc, av);
+      float av[R], xv[R];
+      load_cols<R>(dst_rows + (uint64_t)im.v * f + cc, av);
+      term.template load<R>(xv, cc);
       /* 4 edge slots per lane group in flight */
       for (uint32_t k0 = 0; k0 < cnt; k0 += 4 * ng) {
         float pr[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const uint32_t k = min(k0 + q * ng + gi, cnt - 1);
-          const float *b = src_rows +
-              (uint64_t)(row_indices[e0 + k] - src_start) * f + cc;
           float bv[R];
-          if constexpr (R == 1) bv[0] = b[0];
-          else load_lane<R>(b, bv);
+          load_cols<R>(src_rows +
+                           (uint64_t)(row_indices[e0 + k] - src_start) * f + cc,
+                       bv);
           pr[q] = 0.f;
 #pragma unroll
-          for (int j = 0; j < R; ++j) pr[q] = fmaf(av[j], bv[j], pr[q]);
+          for (int j = 0; j < R; ++j) pr[q] = term(xv[j], av[j], bv[j], pr[q]);
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -2122,14 +1980,16 @@ __global__ void k_edge_dot_heads_seg(const uint4 *__restrict__ items,
   }
 }
 
-__global__ void k_edge_dot_heads(const uint4 *__restrict__ items,
-                                 const uint32_t *__restrict__ n_items_p,
-                                 float *__restrict__ out,
-                                 const float *__restrict__ dst_rows,
-                                 const float *__restrict__ src_rows,
-                                 const uint32_t *__restrict__ row_indices,
-                                 uint32_t src_start, uint32_t f, uint32_t K,
-                                 uint32_t C) {
+/* general form, any K and C */
+template <class Term>
+__global__ void k_edge_pair(const uint4 *__restrict__ items,
+                            const uint32_t *__restrict__ n_items_p,
+                            float *__restrict__ out,
+                            const float *__restrict__ dst_rows,
+                            const float *__restrict__ src_rows,
+                            const uint32_t *__restrict__ row_indices,
+                            uint32_t src_start, uint32_t f, uint32_t K,
+                            uint32_t C, const Term term) {
   const uint32_t n_items = *n_items_p;
   const WaveId w = wave_id();
   const uint32_t lane = w.lane;
@@ -2142,8 +2002,11 @@ __global__ void k_edge_dot_heads(const uint4 *__restrict__ items,
       const float *b = src_rows + (uint64_t)(row_indices[e] - src_start) * f;
       for (uint32_t h = 0; h < K; ++h) {
         float sum = 0.f;
-        for (uint32_t j = h * C + lane; j < (h + 1) * C; j += 64)
-          sum = fmaf(a[j], b[j], sum);
+        for (uint32_t j = h * C + lane; j < (h + 1) * C; j += 64) {
+          float x[1];
+          term.template load<1>(x, j);
+          sum = term(x[0], a[j], b[j], sum);
+        }
         sum = wave_sum(sum);
         if (lane == 0) out[(uint64_t)e * K + h] = sum;
       }
@@ -2151,107 +2014,7 @@ __global__ void k_edge_dot_heads(const uint4 *__restrict__ items,
   }
 }
 
-/* ---- GATv2 attention: the f-wide per-edge score and its backward ---- */
-/* t is ONE fp32 add of the two loaded values; lrelu(t) = t > 0 ? t : slope*t,
- * lrelu'(t) = t > 0 ? 1 : slope (slope at t == 0, as k_edge_softmax_norm). */
-__device__ __forceinline__ float lrelu(float t, float slope) {
-  return t > 0.f ? t : slope * t;
-}
-
-/* score[e*K + k] = sum_{j<C} att[k*C+j] * lrelu(own[d, k*C+j] + nbr[src, k*C+j]):
- * k_edge_dot_heads_seg with the product a*b replaced by att*lrelu(a+b); the
- * lane's R att columns are loaded once per (item, slab) beside its own-row
- * columns.  Same lane layout, clamping and writer rule as the dot. */
-template <int R>
-__global__ void k_gatv2_score_seg(const uint4 *__restrict__ items,
-                                  const uint32_t *__restrict__ n_items_p,
-                                  float *__restrict__ out,
-                                  const float *__restrict__ dst_rows,
-                                  const float *__restrict__ src_rows,
-                                  const float *__restrict__ att, float slope,
-                                  const uint32_t *__restrict__ row_indices,
-                                  uint32_t src_start, uint32_t f, uint32_t K,
-                                  uint32_t C, uint32_t G) {
-  const uint32_t n_items = *n_items_p;
-  const WaveId w = wave_id();
-  const uint32_t L = C / R;          /* lanes per head */
-  const uint32_t gl = w.lane & (G - 1);
-  const uint32_t gi = w.lane / G;    /* which of the wave's edge slots */
-  const uint32_t ng = 64 / G;
-  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
-    const Item im = load_item(items, it);
-    const uint32_t e0 = im.e0, cnt = im.cnt;
-    for (uint32_t base = 0; base < f; base += G * R) {
-      const uint32_t col = base + gl * R;
-      const bool live = col < f;     /* f % R == 0: a live lane is full */
-      const uint32_t cc = live ? col : 0u;
-      const bool writer = live && (gl & (L - 1)) == 0;
-      const uint32_t head = cc / C;
-      float av[R], at[R];
-      if constexpr (R == 1) {
-        av[0] = dst_rows[(uint64_t)im.v * f + cc];
-        at[0] = att[cc];
-      } else {
-        load_lane<R>(dst_rows + (uint64_t)im.v * f + cc, av);
-        load_lane<R>(att + cc, at);
-      }
-      /* 4 edge slots per lane group in flight */
-      for (uint32_t k0 = 0; k0 < cnt; k0 += 4 * ng) {
-        float pr[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const uint32_t k = min(k0 + q * ng + gi, cnt - 1);
-          const float *b = src_rows +
-              (uint64_t)(row_indices[e0 + k] - src_start) * f + cc;
-          float bv[R];
-          if constexpr (R == 1) bv[0] = b[0];
-          else load_lane<R>(b, bv);
-          pr[q] = 0.f;
-#pragma unroll
-          for (int j = 0; j < R; ++j)
-            pr[q] = fmaf(at[j], lrelu(av[j] + bv[j], slope), pr[q]);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const uint32_t k = k0 + q * ng + gi;
-          const float sum = seg_sum(pr[q], L);
-          if (writer && k < cnt) out[(uint64_t)(e0 + k) * K + head] = sum;
-        }
-      }
-    }
-  }
-}
-
-/* general form, any K and C: a wave per (edge, head), lanes stride the head */
-__global__ void k_gatv2_score(const uint4 *__restrict__ items,
-                              const uint32_t *__restrict__ n_items_p,
-                              float *__restrict__ out,
-                              const float *__restrict__ dst_rows,
-                              const float *__restrict__ src_rows,
-                              const float *__restrict__ att, float slope,
-                              const uint32_t *__restrict__ row_indices,
-                              uint32_t src_start, uint32_t f, uint32_t K,
-                              uint32_t C) {
-  const uint32_t n_items = *n_items_p;
-  const WaveId w = wave_id();
-  const uint32_t lane = w.lane;
-  for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
-    const Item im = load_item(items, it);
-    const uint32_t e0 = im.e0, cnt = im.cnt;
-    const float *a = dst_rows + (uint64_t)im.v * f;
-    for (uint32_t k = 0; k < cnt; ++k) {
-      const uint32_t e = e0 + k;
-      const float *b = src_rows + (uint64_t)(row_indices[e] - src_start) * f;
-      for (uint32_t h = 0; h < K; ++h) {
-        float sum = 0.f;
-        for (uint32_t j = h * C + lane; j < (h + 1) * C; j += 64)
-          sum = fmaf(att[j], lrelu(a[j] + b[j], slope), sum);
-        sum = wave_sum(sum);
-        if (lane == 0) out[(uint64_t)e * K + h] = sum;
-      }
-    }
-  }
-}
+/* ---- GATv2 attention: the backward of the f-wide per-edge score ---- */
 
 /* One walk over an offset array, the shape of k_gather_spmm_heads: a group of
  * G lanes per work item, a lane owning R consecutive columns of one head
@@ -3604,19 +3367,68 @@ void nts_edge_softmax_stable_last(nts_stream *s, int *stable) {
   if (stable) *stable = s->softmax_stable_last ? 1 : 0;
 }
 
-/* what follows pass 1 of the stable forward entries: the split items' sum
- * pass, then pass 2 */
-static void launch_norm_stable(nts_stream *s, const EdgeItems &p, float *out,
-                               unsigned long long *pairs, float *out2,
-                               const nts_vid *pos2, nts_vid f) {
-  const bool flat = !s->heads_general && f <= 64 && (f & (f - 1)) == 0;
-  hipLaunchKernelGGL(flat ? k_edge_softmax_splitsum<true>
-                          : k_edge_softmax_splitsum<false>,
-                     dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-                     p.ib->counter, out, pairs, f);
-  hipLaunchKernelGGL(k_edge_softmax_norm_stable, dim3(p.grid),
+/* the FLAT layout takes K a power of two <= 64 */
+static bool heads_flat(const nts_stream *s, uint32_t K) {
+  return !s->heads_general && K <= 64 && (K & (K - 1)) == 0;
+}
+
+extern "C++" { /* a template cannot have the C linkage of this block */
+/* one k_edge_reduce pass in a given lane layout ... */
+template <bool FLAT, int KC, class Value, class Reduce>
+static void launch_reduce_as(nts_stream *s, const EdgeItems &p, uint32_t K,
+                             const Value &val, const Reduce &red) {
+  hipLaunchKernelGGL((k_edge_reduce<FLAT, KC, Value, Reduce>), dim3(p.grid),
                      dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-                     p.ib->counter, out, pairs, out2, pos2, f);
+                     p.ib->counter, val, red, K);
+}
+/* ... and in the layout heads_flat() picks; one column has one layout */
+template <class Value, class Reduce>
+static void launch_reduce(nts_stream *s, const EdgeItems &p, uint32_t K,
+                          const Value &val, const Reduce &red) {
+  if (K == 1) launch_reduce_as<false, 1>(s, p, K, val, red);
+  else if (heads_flat(s, K)) launch_reduce_as<true, 0>(s, p, K, val, red);
+  else launch_reduce_as<false, 0>(s, p, K, val, red);
+}
+}  // extern "C++"
+
+/* the per-destination scratch of a softmax forward: sums (default) or pairs
+ * (stable), the other null */
+struct SoftmaxScratch {
+  float *sums = nullptr;
+  unsigned long long *pairs = nullptr;
+};
+static SoftmaxScratch softmax_scratch(nts_stream *s, uint64_t n) {
+  SoftmaxScratch ws;
+  if (s->softmax_stable) ws.pairs = get_pairs(s, n);
+  else ws.sums = get_sums(s, n);
+  return ws;
+}
+
+extern "C++" {
+template <NormMode MODE>
+static void launch_norm(nts_stream *s, const EdgeItems &p, float *out,
+                        const float *cached, const NormSlot<MODE> *slots,
+                        float *out2, const nts_vid *pos2, nts_vid f,
+                        const float *lrelu_in = nullptr, float slope = 0.f,
+                        float *dst_accum = nullptr) {
+  hipLaunchKernelGGL(k_edge_softmax_norm<MODE>, dim3(p.grid), dim3(NTS_BLOCK),
+                     0, s->stream, p.ib->items, p.ib->counter, out, cached,
+                     slots, out2, pos2, lrelu_in, slope, dst_accum, f);
+}
+}  // extern "C++"
+
+/* what follows pass 1 of a softmax or attention forward: the split items'
+ * sum pass (stable only), then the normalize pass */
+static void launch_softmax_tail(nts_stream *s, const EdgeItems &p, float *out,
+                                const SoftmaxScratch &ws, float *out2,
+                                const nts_vid *pos2, nts_vid f) {
+  if (ws.pairs) {
+    launch_reduce(s, p, f, EdgeStashExp{out, ws.pairs, 0.f},
+                  SplitSumToPairs{ws.pairs});
+    launch_norm<NORM_STABLE>(s, p, out, nullptr, ws.pairs, out2, pos2, f);
+  } else {
+    launch_norm<NORM_FWD>(s, p, out, nullptr, ws.sums, out2, pos2, f);
+  }
 }
 
 static void launch_edge_op(nts_stream *s, EdgeOp op, float *message,
@@ -3638,7 +3450,10 @@ static void launch_edge_op(nts_stream *s, EdgeOp op, float *message,
   dbg_sync(s, "k_edge_items");
 }
 
-/* returns the edge count it read (0: nothing ran) */
+/* Edge softmax, two item-parallel passes: pass 1 stashes exp(in) (forward)
+ * or g*s (backward) in out and reduces per-destination sums, pass 2
+ * normalizes.  Strided walk at every f.  Returns the edge count it read
+ * (0: nothing ran). */
 static uint32_t launch_edge_softmax(nts_stream *s, bool backward, float *out,
                                     const float *in, const float *cached,
                                     const nts_vid *column_offset,
@@ -3653,27 +3468,26 @@ static uint32_t launch_edge_softmax(nts_stream *s, bool backward, float *out,
   if (!f) return 0;
   const EdgeItems p = edge_items(s, column_offset, batch);
   if (!p.ib) return 0;
-  if (!backward && s->softmax_stable) {
-    unsigned long long *pairs = get_pairs(s, (uint64_t)batch * f);
+  const uint64_t n = (uint64_t)batch * f;
+  if (backward) {
+    float *sums = get_sums(s, n);
     Tic t(s, NTS_KTAG_EDGE);
-    hipLaunchKernelGGL(k_edge_softmax_maxsum, dim3(p.grid), dim3(NTS_BLOCK),
-                       0, s->stream, p.ib->items, p.ib->counter, out, in,
-                       pairs, f);
-    launch_norm_stable(s, p, out, pairs, out2, pos2, f);
-    dbg_sync(s, "k_edge_softmax_stable");
+    launch_reduce_as<false, 0>(s, p, f, EdgeInCached{in, cached},
+                               SumToSums<false>{out, sums});
+    launch_norm<NORM_BWD>(s, p, out, cached, sums, out2, pos2, f, lrelu_in,
+                          slope, dst_accum);
+    dbg_sync(s, "k_edge_softmax_backward");
     return p.edges;
   }
-  float *sums = get_sums(s, (uint64_t)batch * f);
+  const SoftmaxScratch ws = softmax_scratch(s, n);
   Tic t(s, NTS_KTAG_EDGE);
-  hipLaunchKernelGGL(
-      backward ? k_edge_softmax_sum<true> : k_edge_softmax_sum<false>,
-      dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-      p.ib->counter, out, in, cached, sums, f);
-  hipLaunchKernelGGL(
-      backward ? k_edge_softmax_norm<true> : k_edge_softmax_norm<false>,
-      dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-      p.ib->counter, out, cached, sums, out2, pos2, lrelu_in, slope,
-      dst_accum, f);
+  if (ws.pairs)
+    launch_reduce_as<false, 0>(s, p, f, EdgeIn{in},
+                               MaxSumToPairs{out, ws.pairs});
+  else
+    launch_reduce_as<false, 0>(s, p, f, EdgeIn{in},
+                               SumToSums<true>{out, ws.sums});
+  launch_softmax_tail(s, p, out, ws, out2, pos2, f);
   dbg_sync(s, "k_edge_softmax");
   return p.edges;
 }
@@ -3799,55 +3613,8 @@ void nts_edge_softmax_backward_fused(nts_stream *s, float *msg_input_grad,
                       dst_sum);
 }
 
-void nts_weight_sum(nts_stream *s, float *out, const float *weights,
-                    const nts_vid *offset, nts_vid batch_size) {
-  const EdgeItems p = edge_items(s, offset, batch_size);
-  if (!p.ib) return;
-  Tic t(s, NTS_KTAG_EDGE);
-  hipLaunchKernelGGL(k_weight_sum, dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream,
-                     p.ib->items, p.ib->counter, out, weights);
-  dbg_sync(s, "k_weight_sum");
-}
-
-void nts_edge_attention_forward(nts_stream *s, float *softmax_out,
-                                float *softmax_out_perm,
-                                const nts_vid *perm_pos, float *m_sum_out,
-                                const float *s_src_mirror, const float *s_dst,
-                                const nts_vid *row_indices,
-                                const nts_vid *mirror_index, float slope,
-                                const nts_vid *column_offset,
-                                nts_vid batch_size) {
-  s->softmax_stable_last = s->softmax_stable;
-  const EdgeItems p = edge_items(s, column_offset, batch_size);
-  if (!p.ib) return;
-  const ItemsBuf &ib = *p.ib;
-  const uint32_t grid = p.grid;
-  if (s->softmax_stable) {
-    unsigned long long *pairs = get_pairs(s, batch_size);
-    Tic t(s, NTS_KTAG_EDGE);
-    hipLaunchKernelGGL(k_edge_att_maxsum, dim3(grid), dim3(NTS_BLOCK), 0,
-                       s->stream, ib.items, ib.counter, softmax_out, m_sum_out,
-                       s_src_mirror, s_dst, row_indices, mirror_index, slope,
-                       pairs);
-    launch_norm_stable(s, p, softmax_out, pairs, softmax_out_perm, perm_pos,
-                       1u);
-    dbg_sync(s, "k_edge_att_stable");
-    return;
-  }
-  float *sums = get_sums(s, batch_size);
-  Tic t(s, NTS_KTAG_EDGE);
-  hipLaunchKernelGGL(k_edge_att_sum, dim3(grid), dim3(NTS_BLOCK), 0,
-                     s->stream, ib.items, ib.counter, softmax_out, m_sum_out,
-                     s_src_mirror, s_dst, row_indices, mirror_index, slope,
-                     sums);
-  hipLaunchKernelGGL((k_edge_softmax_norm<false>), dim3(grid),
-                     dim3(NTS_BLOCK), 0, s->stream, ib.items, ib.counter,
-                     softmax_out, nullptr, sums, softmax_out_perm, perm_pos,
-                     nullptr, 0.f, nullptr, 1u);
-  dbg_sync(s, "k_edge_att");
-}
-
-/* ---- multi-head entries (additive; see include/nts_hip.h) ---- */
+/* ---- attention and multi-head entries (additive; see include/nts_hip.h) ----
+ * A one-column entry is its heads entry at K = 1 behind the other prologue. */
 
 /* Prologue of the heads edge entries: as edge_items, with the edge count
  * from the caller — no device-to-host copy, no stream synchronize. */
@@ -3861,13 +3628,40 @@ static EdgeItems edge_items_known(nts_stream *s, const nts_vid *offset,
   return p;
 }
 
-/* the FLAT kernel forms take K a power of two <= 64 */
-static bool heads_flat(const nts_stream *s, uint32_t K) {
-  return !s->heads_general && K <= 64 && (K & (K - 1)) == 0;
-}
-
 void nts_heads_dbg_general(nts_stream *s, int enable) {
   s->heads_general = enable != 0;
+}
+
+/* Pass 1 fuses the score, the activation, the exp and the per-destination
+ * sums; pass 2 is the softmax's normalize (dual-order emission). */
+static void attention_forward(nts_stream *s, const EdgeItems &p, nts_vid K,
+                              nts_vid batch, float *softmax_out,
+                              float *softmax_out_perm, const nts_vid *perm_pos,
+                              const EdgeScore &score) {
+  s->softmax_stable_last = s->softmax_stable;
+  if (!p.ib) return;
+  const SoftmaxScratch ws = softmax_scratch(s, (uint64_t)batch * K);
+  Tic t(s, NTS_KTAG_EDGE);
+  if (ws.pairs)
+    launch_reduce(s, p, K, score, MaxSumToPairs{softmax_out, ws.pairs});
+  else
+    launch_reduce(s, p, K, score, SumToSums<true>{softmax_out, ws.sums});
+  launch_softmax_tail(s, p, softmax_out, ws, softmax_out_perm, perm_pos, K);
+  dbg_sync(s, "k_edge_att");
+}
+
+void nts_edge_attention_forward(nts_stream *s, float *softmax_out,
+                                float *softmax_out_perm,
+                                const nts_vid *perm_pos, float *m_sum_out,
+                                const float *s_src_mirror, const float *s_dst,
+                                const nts_vid *row_indices,
+                                const nts_vid *mirror_index, float slope,
+                                const nts_vid *column_offset,
+                                nts_vid batch_size) {
+  attention_forward(s, edge_items(s, column_offset, batch_size), 1, batch_size,
+                    softmax_out, softmax_out_perm, perm_pos,
+                    EdgeScore{m_sum_out, s_src_mirror, s_dst, row_indices,
+                              mirror_index, slope, 0.f});
 }
 
 void nts_edge_attention_forward_heads(
@@ -3877,48 +3671,64 @@ void nts_edge_attention_forward_heads(
     const nts_vid *mirror_index, float slope, const nts_vid *column_offset,
     nts_vid batch_size, nts_vid edges, nts_vid heads) {
   check_heads("nts_edge_attention_forward_heads", heads, heads);
-  s->softmax_stable_last = s->softmax_stable;
-  const EdgeItems p = edge_items_known(s, column_offset, batch_size, edges);
-  if (!p.ib) return;
-  const ItemsBuf &ib = *p.ib;
-  if (s->softmax_stable) {
-    unsigned long long *pairs = get_pairs(s, (uint64_t)batch_size * heads);
-    Tic t(s, NTS_KTAG_EDGE);
-    if (heads == 1)
-      hipLaunchKernelGGL(k_edge_att_maxsum, dim3(p.grid), dim3(NTS_BLOCK), 0,
-                         s->stream, ib.items, ib.counter, softmax_out,
-                         m_sum_out, s_src_mirror, s_dst, row_indices,
-                         mirror_index, slope, pairs);
-    else
-      hipLaunchKernelGGL(heads_flat(s, heads) ? k_edge_att_maxsum_heads<true>
-                                              : k_edge_att_maxsum_heads<false>,
-                         dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream, ib.items,
-                         ib.counter, softmax_out, m_sum_out, s_src_mirror,
-                         s_dst, row_indices, mirror_index, slope, pairs, heads);
-    launch_norm_stable(s, p, softmax_out, pairs, softmax_out_perm, perm_pos,
-                       heads);
-    dbg_sync(s, "k_edge_att_heads_stable");
-    return;
-  }
-  float *sums = get_sums(s, (uint64_t)batch_size * heads);
-  Tic t(s, NTS_KTAG_EDGE);
-  if (heads == 1)
-    hipLaunchKernelGGL(k_edge_att_sum, dim3(p.grid), dim3(NTS_BLOCK), 0,
-                       s->stream, ib.items, ib.counter, softmax_out, m_sum_out,
-                       s_src_mirror, s_dst, row_indices, mirror_index, slope,
-                       sums);
-  else
-    hipLaunchKernelGGL(heads_flat(s, heads) ? k_edge_att_sum_heads<true>
-                                            : k_edge_att_sum_heads<false>,
-                       dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream, ib.items,
-                       ib.counter, softmax_out, m_sum_out, s_src_mirror, s_dst,
-                       row_indices, mirror_index, slope, sums, heads);
-  hipLaunchKernelGGL((k_edge_softmax_norm<false>), dim3(p.grid),
-                     dim3(NTS_BLOCK), 0, s->stream, ib.items, ib.counter,
-                     softmax_out, nullptr, sums, softmax_out_perm, perm_pos,
-                     nullptr, 0.f, nullptr, heads);
-  dbg_sync(s, "k_edge_att_heads");
+  attention_forward(s, edge_items_known(s, column_offset, batch_size, edges),
+                    heads, batch_size, softmax_out, softmax_out_perm, perm_pos,
+                    EdgeScore{m_sum_out, s_src_mirror, s_dst, row_indices,
+                              mirror_index, slope, 0.f});
 }
+
+static void weight_sum(nts_stream *s, const EdgeItems &p, nts_vid K,
+                       float *out, const float *weights) {
+  if (!p.ib) return;
+  Tic t(s, NTS_KTAG_EDGE);
+  launch_reduce(s, p, K, EdgeIn{weights}, SumToOut{out});
+  dbg_sync(s, "k_weight_sum");
+}
+
+void nts_weight_sum(nts_stream *s, float *out, const float *weights,
+                    const nts_vid *offset, nts_vid batch_size) {
+  weight_sum(s, edge_items(s, offset, batch_size), 1, out, weights);
+}
+
+void nts_weight_sum_heads(nts_stream *s, float *out, const float *weights,
+                          const nts_vid *offset, nts_vid batch_size,
+                          nts_vid edges, nts_vid heads) {
+  check_heads("nts_weight_sum_heads", heads, heads);
+  weight_sum(s, edge_items_known(s, offset, batch_size, edges), heads, out,
+             weights);
+}
+
+/* The row-pair passes' lane geometry.  R, columns per lane: the widest of
+ * 4 / 2 / 1 dwords that divides C and that every pointer's alignment
+ * permits; L = C / R lanes per head.  seg: L a power of two <= 64.  G, the
+ * lane group of one row: f / R lanes rounded up to a power of two, <= 64. */
+extern "C++" {
+template <class Term>
+static void launch_edge_pair(nts_stream *s, const EdgeItems &p, float *out,
+                             const float *dst_rows, const float *src_rows,
+                             const nts_vid *row_indices, nts_vid src_start,
+                             nts_vid f, nts_vid K, uintptr_t alignment,
+                             const Term &term) {
+  const uint32_t C = f / K;
+  const uint32_t R =
+      (uint32_t)gather_geometry(C, alignment, sizeof(float)).elem;
+  const uint32_t L = C / R;
+  if (!s->heads_general && (L & (L - 1)) == 0 && L <= 64) {
+    uint32_t G = 64;
+    while (G / 2 >= f / R) G /= 2;
+    hipLaunchKernelGGL((R == 4   ? k_edge_pair_seg<4, Term>
+                        : R == 2 ? k_edge_pair_seg<2, Term>
+                                 : k_edge_pair_seg<1, Term>),
+                       dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream,
+                       p.ib->items, p.ib->counter, out, dst_rows, src_rows,
+                       row_indices, src_start, f, K, C, G, term);
+  } else {
+    hipLaunchKernelGGL(k_edge_pair<Term>, dim3(p.grid), dim3(NTS_BLOCK), 0,
+                       s->stream, p.ib->items, p.ib->counter, out, dst_rows,
+                       src_rows, row_indices, src_start, f, K, C, term);
+  }
+}
+}  // extern "C++"
 
 void nts_edge_dot_heads(nts_stream *s, float *out, const float *dst_rows,
                         const float *src_rows, const nts_vid *row_indices,
@@ -3928,35 +3738,15 @@ void nts_edge_dot_heads(nts_stream *s, float *out, const float *dst_rows,
   check_heads("nts_edge_dot_heads", feature_size, heads);
   const EdgeItems p = edge_items_known(s, column_offset, batch_size, edges);
   if (!p.ib) return;
-  const uint32_t C = feature_size / heads;
   Tic t(s, NTS_KTAG_EDGE);
-  if (heads == 1)
+  if (heads == 1) /* k_edge_dot: another shape, measured */
     hipLaunchKernelGGL(k_edge_dot, dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream,
                        p.ib->items, p.ib->counter, out, dst_rows, src_rows,
                        row_indices, src_start, feature_size);
-  else {
-    /* columns per lane: the widest of 4 / 2 / 1 dwords that divides C and
-     * that both row pointers' alignment permits; lanes per head C / R */
-    const GatherGeom geo = gather_geometry(
-        C, (uintptr_t)dst_rows | (uintptr_t)src_rows, sizeof(float));
-    const uint32_t R = (uint32_t)geo.elem, L = C / R;
-    if (!s->heads_general && (L & (L - 1)) == 0 && L <= 64) {
-      /* lane group of one row: f / R lanes, a power of two up to 64 */
-      uint32_t G = 64;
-      while (G / 2 >= feature_size / R) G /= 2;
-      hipLaunchKernelGGL(R == 4   ? k_edge_dot_heads_seg<4>
-                         : R == 2 ? k_edge_dot_heads_seg<2>
-                                  : k_edge_dot_heads_seg<1>,
-                         dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream,
-                         p.ib->items, p.ib->counter, out, dst_rows, src_rows,
-                         row_indices, src_start, feature_size, heads, C, G);
-    } else {
-      hipLaunchKernelGGL(k_edge_dot_heads, dim3(p.grid), dim3(NTS_BLOCK), 0,
-                         s->stream, p.ib->items, p.ib->counter, out, dst_rows,
-                         src_rows, row_indices, src_start, feature_size, heads,
-                         C);
-    }
-  }
+  else
+    launch_edge_pair(s, p, out, dst_rows, src_rows, row_indices, src_start,
+                     feature_size, heads,
+                     (uintptr_t)dst_rows | (uintptr_t)src_rows, DotTerm{});
   dbg_sync(s, "k_edge_dot_heads");
 }
 
@@ -3969,29 +3759,11 @@ void nts_edge_gatv2_score(nts_stream *s, float *score, const float *dst_rows,
   check_heads("nts_edge_gatv2_score", feature_size, heads);
   const EdgeItems p = edge_items_known(s, column_offset, batch_size, edges);
   if (!p.ib) return;
-  const uint32_t C = feature_size / heads;
-  /* columns per lane as for nts_edge_dot_heads, att's alignment included */
-  const GatherGeom geo = gather_geometry(
-      C, (uintptr_t)dst_rows | (uintptr_t)src_rows | (uintptr_t)att,
-      sizeof(float));
-  const uint32_t R = (uint32_t)geo.elem, L = C / R;
   Tic t(s, NTS_KTAG_EDGE);
-  if (!s->heads_general && (L & (L - 1)) == 0 && L <= 64) {
-    uint32_t G = 64;
-    while (G / 2 >= feature_size / R) G /= 2;
-    hipLaunchKernelGGL(R == 4   ? k_gatv2_score_seg<4>
-                       : R == 2 ? k_gatv2_score_seg<2>
-                                : k_gatv2_score_seg<1>,
-                       dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream,
-                       p.ib->items, p.ib->counter, score, dst_rows, src_rows,
-                       att, slope, row_indices, src_start, feature_size, heads,
-                       C, G);
-  } else {
-    hipLaunchKernelGGL(k_gatv2_score, dim3(p.grid), dim3(NTS_BLOCK), 0,
-                       s->stream, p.ib->items, p.ib->counter, score, dst_rows,
-                       src_rows, att, slope, row_indices, src_start,
-                       feature_size, heads, C);
-  }
+  launch_edge_pair(s, p, score, dst_rows, src_rows, row_indices, src_start,
+                   feature_size, heads,
+                   (uintptr_t)dst_rows | (uintptr_t)src_rows | (uintptr_t)att,
+                   Gatv2Term{att, slope});
   dbg_sync(s, "k_gatv2_score");
 }
 
@@ -4029,24 +3801,6 @@ void nts_edge_gatv2_backward(nts_stream *s, float *grad_own, float *grad_att,
                      G);
 #undef NTS_K
   dbg_sync(s, "k_gatv2_backward");
-}
-
-void nts_weight_sum_heads(nts_stream *s, float *out, const float *weights,
-                          const nts_vid *offset, nts_vid batch_size,
-                          nts_vid edges, nts_vid heads) {
-  check_heads("nts_weight_sum_heads", heads, heads);
-  const EdgeItems p = edge_items_known(s, offset, batch_size, edges);
-  if (!p.ib) return;
-  Tic t(s, NTS_KTAG_EDGE);
-  if (heads == 1)
-    hipLaunchKernelGGL(k_weight_sum, dim3(p.grid), dim3(NTS_BLOCK), 0,
-                       s->stream, p.ib->items, p.ib->counter, out, weights);
-  else
-    hipLaunchKernelGGL(heads_flat(s, heads) ? k_weight_sum_heads<true>
-                                            : k_weight_sum_heads<false>,
-                       dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream,
-                       p.ib->items, p.ib->counter, out, weights, heads);
-  dbg_sync(s, "k_weight_sum_heads");
 }
 
 int nts_gather_by_src_from_dst_dot(nts_stream *s, const float *input,

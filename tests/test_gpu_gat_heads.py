@@ -318,7 +318,8 @@ def _attention_case(heads, with_mirror):
 @pytest.mark.parametrize("with_perm", [True, False])
 @pytest.mark.parametrize("with_mirror", [True, False])
 @pytest.mark.parametrize("heads,form", [(2, "auto"), (3, "auto"), (8, "auto"),
-                                        (2, "general"), (8, "general")])
+                                        (2, "general"), (8, "general"),
+                                        (1, "auto"), (1, "general")])
 def test_attention_forward_heads(gpu, heads, form, with_mirror, with_perm):
     """Per head the inputs of test_attention_forward (seed = head), m exactly
     0 on some edges.  m_sum_out is one fp32 add: bit-equal to numpy float32.
@@ -380,6 +381,7 @@ def _dot_case(heads, c_per):
     (8, 16, "auto", 1),
     (4, 6, "auto", 0), (3, 7, "auto", 0),  # general loop
     (1, 33, "auto", 0),                    # the single-head kernel
+    (1, 33, "general", 0),
     (8, 16, "general", 0), (2, 64, "general", 0), (2, 128, "general", 0)])
 def test_edge_dot_heads(gpu, heads, c_per, form, shift):
     """out[e, k] = dst_rows[dst, head k] . src_rows[src - src_start, head k].
@@ -404,7 +406,8 @@ def test_edge_dot_heads(gpu, heads, c_per, form, shift):
 # --------------------------------------------------------------------------
 @pytest.mark.parametrize("order", ["csc", "csr"])
 @pytest.mark.parametrize("heads,form", [(2, "auto"), (3, "auto"), (8, "auto"),
-                                        (2, "general"), (8, "general")])
+                                        (2, "general"), (8, "general"),
+                                        (1, "auto"), (1, "general")])
 def test_weight_sum_heads(gpu, heads, form, order):
     """out[v, k] += sum of signed weights[e, k] over v's edge range, onto a
     non-zero prefill; over the CSC offsets (split destinations) and the CSR
@@ -428,6 +431,72 @@ def test_weight_sum_heads(gpu, heads, form, order):
     zero = np.diff(off.astype(np.int64)) == 0
     assert zero.any()
     _assert_bits(got[zero], pre[zero], name + " at degree 0")
+
+
+# --------------------------------------------------------------------------
+# one head against the scalar entries
+# --------------------------------------------------------------------------
+@pytest.mark.parametrize("form", ["auto", "general"])
+def test_one_head_is_the_scalar_entries(gpu, form):
+    """At K = 1 the three heads edge entries compute what
+    nts_edge_attention_forward, nts_weight_sum and nts_edge_dot compute, bit
+    for bit wherever no atomic merge is involved: m_sum and the dot on every
+    edge, the softmax on the edges of destinations of at most 256 edges, the
+    weight sum on those destinations.  Split destinations merge by fp32
+    atomics in an order that varies from launch to launch and stay under the
+    bounds of test_attention_forward_heads and test_weight_sum_heads."""
+    g = R.edge_case_graph()
+    dev, st = gpu["dev"], _stream(gpu, form)
+    one = g.deg <= R.SPLIT
+    one_e = one[g.dst_of_edge]
+    assert one.any() and not one.all()
+    name = f"K=1 {form} against the scalar entry: "
+
+    s_src, s_dst, m_ref, s_ref = _attention_case(1, True)
+    d_src, d_dst = Inp(dev, s_src), Inp(dev, s_dst)
+    got = []
+    for heads_entry in (True, False):
+        out, msum, out2 = (Buf(dev, (g.edges, 1)) for _ in range(3))
+        args = (out.ptr, out2.ptr, gpu["pos"].data_ptr(), msum.ptr, d_src.ptr,
+                d_dst.ptr, gpu["rows"].data_ptr(), gpu["mi"].data_ptr(), SLOPE,
+                gpu["coff"].data_ptr(), g.batch)
+        if heads_entry:
+            st.edge_attention_forward_heads(*args, g.edges, 1)
+        else:
+            st.edge_attention_forward(*args)
+        got.append([b.read(name + "attention") for b in (out, msum, out2)])
+    (out_h, msum_h, out2_h), (out_s, msum_s, out2_s) = got
+    _assert_bits(msum_h, msum_s, name + "m_sum")
+    _assert_bits(out_h[one_e], out_s[one_e], name + "softmax, unsplit")
+    pos = R.csc_to_csr(g.row_indices)[1]
+    _assert_bits(out2_h[pos][one_e], out2_s[pos][one_e],
+                 name + "permuted softmax, unsplit")
+    _assert_bound(out_h, s_ref, 1e-4 * np.abs(s_ref), name + "softmax")
+
+    rng = np.random.default_rng(9100)
+    w = rng.normal(size=(g.edges, 1)).astype(np.float32)
+    pre = (rng.normal(size=(g.batch, 1)) + 2).astype(np.float32)
+    ref, mag = H.weight_sum(g.column_offset, w, pre)
+    d_w = Inp(dev, w)
+    out_h, out_s = Buf(dev, (g.batch, 1), pre), Buf(dev, (g.batch, 1), pre)
+    st.weight_sum_heads(out_h.ptr, d_w.ptr, gpu["coff"].data_ptr(), g.batch,
+                        g.edges, 1)
+    st.weight_sum(out_s.ptr, d_w.ptr, gpu["coff"].data_ptr(), g.batch)
+    got_h, got_s = out_h.read(name + "weight_sum"), out_s.read(name)
+    _assert_bits(got_h[one], got_s[one], name + "weight_sum, unsplit")
+    _assert_bound(got_h, ref, 1e-4 * np.abs(ref) + 1e-4 * mag,
+                  name + "weight_sum")
+
+    a, b, ref, mag = _dot_case(1, 33)
+    d_a, d_b = Inp(dev, a), Inp(dev, b)
+    out_h, out_s = Buf(dev, (g.edges, 1)), Buf(dev, (g.edges, 1))
+    st.edge_dot_heads(out_h.ptr, d_a.ptr, d_b.ptr, gpu["rows"].data_ptr(),
+                      gpu["coff"].data_ptr(), g.src_start, g.batch, g.edges,
+                      33, 1)
+    st.edge_dot(out_s.ptr, d_a.ptr, d_b.ptr, gpu["rows"].data_ptr(),
+                gpu["coff"].data_ptr(), g.src_start, g.batch, 33)
+    _assert_bits(out_h.read(name + "edge_dot"), out_s.read(name),
+                 name + "edge_dot")
 
 
 # --------------------------------------------------------------------------

@@ -675,6 +675,74 @@ void nts_edge_softmax_stable(nts_stream *s, int enable);   /* default 0 */
  * that had no edge to work on counts, with the mode it was made in). */
 void nts_edge_softmax_stable_last(nts_stream *s, int *stable);
 
+/* ---- attention dropout, fused into the edge softmax (additive) ----
+ * Training-time dropout of attention coefficients, per edge and head
+ * (GATConv(dropout=), attn_drop): the gathers weigh with
+ *   w[e, k] = keep[e, k] ? alpha[e, k] * scale : +0.0f
+ * instead of the softmax alpha.  The mask is a function of (seed, e, k)
+ * alone and is regenerated wherever it is needed; none is stored.
+ *   fmix64(z): z = (z ^ (z >> 33)) * 0xff51afd7ed558ccd;
+ *              z = (z ^ (z >> 33)) * 0xc4ceb9fe1a85ec53;  return z ^ (z >> 33);
+ *   i     = e*K + k, 64-bit; e the chunk-local CSC edge position, k the head
+ *           (or softmax column), K = heads or feature_size
+ *   base  = fmix64(seed)                     (once, on the host)
+ *   u     = fmix64(base + i) >> 40           (24 bits)
+ *   T     = (uint32) lrintf(p * 16777216.0f) (p as fp32, 0 <= p < 1)
+ *   keep  = u >= T                           (drops with probability T / 2^24)
+ *   scale = 1.0f / (1.0f - p)                (fp32; one fp32 multiply per w)
+ * The seed is mixed before the position is added, so seeds s and s + 1 do not
+ * give shifted copies of one mask.  p == 0 keeps everything and w equals alpha
+ * bit for bit.  The mask does not depend on work-item boundaries, the split,
+ * the grid, the lane layout or the softmax mode, and the permuted emission
+ * carries the value of the CSC one.  A destination all of whose in-edges drop
+ * has only zero weights: its aggregated row is zero.
+ * The three stream entries take the host-known edge count (no device-to-host
+ * copy, no synchronize), honour nts_edge_softmax_stable (both modes; the
+ * forward ones are reported by nts_edge_softmax_stable_last) and launch the
+ * kernels of their twins under NTS_KTAG_EDGE: pass 1, the split-sum pass when
+ * stable, normalize — no mask pass and no apply pass.  batch_size == 0 or
+ * edges == 0 launches nothing.  p outside [0, 1) aborts, as invalid heads do. */
+
+/* The device's own keep decision on the host (touches no device):
+ * keep[j] = 1/0 for position first + j, j < count. */
+void nts_edge_dropout_keep(unsigned long long seed, float p,
+    unsigned long long first, unsigned long long count, uint8_t *keep);
+
+/* nts_edge_attention_forward_heads under dropout.  alpha_out[e*K + k] gets
+ * the undropped softmax (what the backward caches: pass 1 stashes into it
+ * and the normalize pass finishes it), softmax_out[e*K + k] and, with
+ * perm_pos, softmax_out_perm[perm_pos[e]*K + k] get w.  alpha_out must not
+ * alias the two weight outputs.  heads == 1 is the one-column layout with
+ * the caller-known edge count.  m_sum_out, mirror_index NULL,
+ * nts_heads_dbg_general and item reuse as for the heads entry. */
+void nts_edge_attention_forward_drop(nts_stream *s, float *softmax_out,
+    float *softmax_out_perm, const nts_vid *perm_pos, float *m_sum_out,
+    const float *s_src_mirror, const float *s_dst,
+    const nts_vid *row_indices, const nts_vid *mirror_index, float slope,
+    const nts_vid *column_offset, nts_vid batch_size, nts_vid edges,
+    nts_vid heads, float *alpha_out, float p, unsigned long long seed);
+
+/* nts_edge_softmax_forward_dual under dropout, K = feature_size (the GATv2
+ * path): msg_cached gets alpha and must be distinct from msg_output;
+ * msg_output and, with perm_pos, msg_output_perm get w. */
+void nts_edge_softmax_forward_drop(nts_stream *s, float *msg_output,
+    float *msg_output_perm, const nts_vid *perm_pos, const float *msg_input,
+    float *msg_cached, const nts_vid *column_offset, nts_vid batch_size,
+    nts_vid edges, nts_vid feature_size, float p, unsigned long long seed);
+
+/* nts_edge_softmax_backward_fused under dropout: msg_output_grad is the
+ * gradient with respect to w in CSC order, and pass 1 uses
+ * g = msg_output_grad * (keep ? scale : 0) where the fused entry uses
+ * msg_output_grad, the mask regenerated from (seed, e, k).  msg_cached is
+ * alpha; lrelu_input / slope, the dual emission and dst_sum (feature_size ==
+ * 1 only) as for the fused entry. */
+void nts_edge_softmax_backward_drop(nts_stream *s, float *msg_input_grad,
+    float *msg_input_grad_perm, const nts_vid *perm_pos,
+    const float *msg_output_grad, const float *msg_cached,
+    const float *lrelu_input, float slope, float *dst_sum,
+    const nts_vid *column_offset, nts_vid batch_size, nts_vid edges,
+    nts_vid feature_size, float p, unsigned long long seed);
+
 /* Opt-in work-item reuse: with enable=1 the stream caches its two most
  * recent item decompositions keyed on (offset pointer, batch, edges) and
  * skips identical rebuilds.  ONLY safe while the caller keeps those

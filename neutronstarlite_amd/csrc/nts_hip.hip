@@ -1490,6 +1490,29 @@ __device__ __forceinline__ float lrelu(float t, float slope) {
   return t > 0.f ? t : slope * t;
 }
 
+/* ---- attention dropout: the keep decision of one (edge, head) ---- */
+/* Position i = e*K + k, e the chunk-local CSC edge, as a 64-bit value; the
+ * finalizer is k_hash_u32's.  keep = (fmix64(base + i) >> 40) >= T with
+ * base = fmix64(seed) mixed once on the host (seeds s and s + 1 give no
+ * shifted copies of one mask) and T = lrintf(p * 2^24): a position drops with
+ * probability T / 2^24.  A function of (seed, e, k) alone, so every pass and
+ * the host (nts_edge_dropout_keep) regenerate the mask and none stores it. */
+__host__ __device__ inline unsigned long long drop_fmix64(
+    unsigned long long z) {
+  z = (z ^ (z >> 33)) * 0xff51afd7ed558ccdULL;
+  z = (z ^ (z >> 33)) * 0xc4ceb9fe1a85ec53ULL;
+  return z ^ (z >> 33);
+}
+struct DropMask {
+  unsigned long long base; /* fmix64(seed) */
+  uint32_t T;              /* keep iff the 24-bit draw >= T */
+  float scale;             /* 1 / (1 - p) */
+};
+__host__ __device__ inline bool drop_keep(const DropMask &dm,
+                                          unsigned long long i) {
+  return (uint32_t)(drop_fmix64(dm.base + i) >> 40) >= dm.T;
+}
+
 /* ---- per-destination reductions over an item's [cnt, K] values ---- */
 /* Per-edge values are [E, K] row-major, per-vertex ones [rows, K]: K is the
  * softmax's f, the attention's heads, 1 for one scalar per edge.  A wave
@@ -1568,6 +1591,20 @@ struct EdgeInCached {
   __device__ void column(uint64_t) {}
   __device__ float operator()(uint32_t, uint32_t, uint32_t, uint64_t m) const {
     return in[m] * cached[m];
+  }
+};
+/* softmax backward under attention dropout: in is the gradient of the
+ * dropped weights w = keep ? s * scale : 0, so the gradient of s is
+ * in * (keep ? scale : 0), the mask regenerated from m (never loaded).
+ * Both loads stand before the hash: its two 64-bit multiplies (four 32-bit
+ * multiplies each, quarter rate) run under the loads' latency. */
+struct EdgeInCachedDrop {
+  const float *__restrict__ in, *__restrict__ cached;
+  DropMask dm;
+  __device__ void column(uint64_t) {}
+  __device__ float operator()(uint32_t, uint32_t, uint32_t, uint64_t m) const {
+    const float g = in[m], c = cached[m];
+    return g * (drop_keep(dm, m) ? dm.scale : 0.f) * c;
   }
 };
 /* Fused GAT attention score: per edge and head
@@ -1781,7 +1818,24 @@ template <NormMode MODE>
 using NormSlot =
     std::conditional_t<MODE == NORM_STABLE, unsigned long long, float>;
 
-template <NormMode MODE>
+/* Attention dropout's emission rule for the forward modes: out keeps the
+ * undropped softmax for the backward, and the dropped weight
+ * w = keep ? v * scale : +0 goes to w_out[m] and, in place of v, to out2 —
+ * one more [E, K] write in this pass instead of a mask tensor and an apply
+ * pass.  The rule is an optional trailing argument (a pack that is empty or
+ * one NormEmitDropped): without it the kernel has the arguments and the body
+ * it had before the rule existed. */
+struct NormEmitDropped {
+  float *__restrict__ w_out;
+  DropMask dm;
+  __device__ float operator()(float v, uint64_t m) const {
+    const float w = drop_keep(dm, m) ? v * dm.scale : 0.f;
+    w_out[m] = w;
+    return w;
+  }
+};
+
+template <NormMode MODE, class... Emit>
 __global__ void k_edge_softmax_norm(const uint4 *__restrict__ items,
                                     const uint32_t *__restrict__ n_items_p,
                                     float *__restrict__ out,
@@ -1792,7 +1846,8 @@ __global__ void k_edge_softmax_norm(const uint4 *__restrict__ items,
                                     const float *__restrict__ lrelu_in,
                                     float slope,
                                     float *__restrict__ dst_accum,
-                                    uint32_t f) {
+                                    uint32_t f, const Emit... emit) {
+  static_assert(sizeof...(Emit) <= 1, "at most one emission rule");
   const uint32_t n_items = *n_items_p;
   const WaveId w = wave_id();
   for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
@@ -1816,7 +1871,9 @@ __global__ void k_edge_softmax_norm(const uint4 *__restrict__ items,
         v = out[m] / slot;
       }
       out[m] = v;
-      if (out2) out2[(uint64_t)pos2[e] * f + r] = v; /* pos2: per-edge map */
+      float v2 = v;
+      ((v2 = emit(v, m)), ...);
+      if (out2) out2[(uint64_t)pos2[e] * f + r] = v2; /* pos2: per-edge map */
       if (dst_accum) gsum += v;
     }
     if (dst_accum) {
@@ -3415,17 +3472,37 @@ static void launch_norm(nts_stream *s, const EdgeItems &p, float *out,
                      0, s->stream, p.ib->items, p.ib->counter, out, cached,
                      slots, out2, pos2, lrelu_in, slope, dst_accum, f);
 }
+/* the forward modes under attention dropout: out = the softmax, emit.w_out
+ * and out2 = the dropped weights */
+template <NormMode MODE>
+static void launch_norm_drop(nts_stream *s, const EdgeItems &p, float *out,
+                             const NormSlot<MODE> *slots, float *out2,
+                             const nts_vid *pos2, nts_vid f,
+                             const NormEmitDropped &emit) {
+  hipLaunchKernelGGL((k_edge_softmax_norm<MODE, NormEmitDropped>),
+                     dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                     p.ib->counter, out, (const float *)nullptr, slots, out2,
+                     pos2, (const float *)nullptr, 0.f, (float *)nullptr, f,
+                     emit);
+}
 }  // extern "C++"
 
 /* what follows pass 1 of a softmax or attention forward: the split items'
- * sum pass (stable only), then the normalize pass */
+ * sum pass (stable only), then the normalize pass.  drop: out keeps the
+ * softmax, drop->w_out and out2 get the dropped weights. */
 static void launch_softmax_tail(nts_stream *s, const EdgeItems &p, float *out,
                                 const SoftmaxScratch &ws, float *out2,
-                                const nts_vid *pos2, nts_vid f) {
+                                const nts_vid *pos2, nts_vid f,
+                                const NormEmitDropped *drop = nullptr) {
   if (ws.pairs) {
     launch_reduce(s, p, f, EdgeStashExp{out, ws.pairs, 0.f},
                   SplitSumToPairs{ws.pairs});
-    launch_norm<NORM_STABLE>(s, p, out, nullptr, ws.pairs, out2, pos2, f);
+    if (drop)
+      launch_norm_drop<NORM_STABLE>(s, p, out, ws.pairs, out2, pos2, f, *drop);
+    else
+      launch_norm<NORM_STABLE>(s, p, out, nullptr, ws.pairs, out2, pos2, f);
+  } else if (drop) {
+    launch_norm_drop<NORM_FWD>(s, p, out, ws.sums, out2, pos2, f, *drop);
   } else {
     launch_norm<NORM_FWD>(s, p, out, nullptr, ws.sums, out2, pos2, f);
   }
@@ -3450,9 +3527,47 @@ static void launch_edge_op(nts_stream *s, EdgeOp op, float *message,
   dbg_sync(s, "k_edge_items");
 }
 
-/* Edge softmax, two item-parallel passes: pass 1 stashes exp(in) (forward)
- * or g*s (backward) in out and reduces per-destination sums, pass 2
- * normalizes.  Strided walk at every f.  Returns the edge count it read
+/* Edge softmax, two item-parallel passes over the items of p (p.ib set):
+ * pass 1 stashes exp(in) (forward) or g*s (backward) in out and reduces
+ * per-destination sums, pass 2 normalizes.  Strided walk at every f. */
+static void softmax_forward_passes(nts_stream *s, const EdgeItems &p,
+                                   float *out, const float *in, nts_vid batch,
+                                   nts_vid f, float *out2, const nts_vid *pos2,
+                                   const NormEmitDropped *drop = nullptr) {
+  const SoftmaxScratch ws = softmax_scratch(s, (uint64_t)batch * f);
+  Tic t(s, NTS_KTAG_EDGE);
+  if (ws.pairs)
+    launch_reduce_as<false, 0>(s, p, f, EdgeIn{in},
+                               MaxSumToPairs{out, ws.pairs});
+  else
+    launch_reduce_as<false, 0>(s, p, f, EdgeIn{in},
+                               SumToSums<true>{out, ws.sums});
+  launch_softmax_tail(s, p, out, ws, out2, pos2, f, drop);
+  dbg_sync(s, "k_edge_softmax");
+}
+
+/* drop: in is the gradient of the dropped weights (EdgeInCachedDrop) */
+static void softmax_backward_passes(nts_stream *s, const EdgeItems &p,
+                                    float *out, const float *in,
+                                    const float *cached, nts_vid batch,
+                                    nts_vid f, float *out2,
+                                    const nts_vid *pos2, const float *lrelu_in,
+                                    float slope, float *dst_accum,
+                                    const DropMask *drop = nullptr) {
+  float *sums = get_sums(s, (uint64_t)batch * f);
+  Tic t(s, NTS_KTAG_EDGE);
+  if (drop)
+    launch_reduce_as<false, 0>(s, p, f, EdgeInCachedDrop{in, cached, *drop},
+                               SumToSums<false>{out, sums});
+  else
+    launch_reduce_as<false, 0>(s, p, f, EdgeInCached{in, cached},
+                               SumToSums<false>{out, sums});
+  launch_norm<NORM_BWD>(s, p, out, cached, sums, out2, pos2, f, lrelu_in,
+                        slope, dst_accum);
+  dbg_sync(s, "k_edge_softmax_backward");
+}
+
+/* The entries that read the edge count from the device.  Returns that count
  * (0: nothing ran). */
 static uint32_t launch_edge_softmax(nts_stream *s, bool backward, float *out,
                                     const float *in, const float *cached,
@@ -3468,27 +3583,11 @@ static uint32_t launch_edge_softmax(nts_stream *s, bool backward, float *out,
   if (!f) return 0;
   const EdgeItems p = edge_items(s, column_offset, batch);
   if (!p.ib) return 0;
-  const uint64_t n = (uint64_t)batch * f;
-  if (backward) {
-    float *sums = get_sums(s, n);
-    Tic t(s, NTS_KTAG_EDGE);
-    launch_reduce_as<false, 0>(s, p, f, EdgeInCached{in, cached},
-                               SumToSums<false>{out, sums});
-    launch_norm<NORM_BWD>(s, p, out, cached, sums, out2, pos2, f, lrelu_in,
-                          slope, dst_accum);
-    dbg_sync(s, "k_edge_softmax_backward");
-    return p.edges;
-  }
-  const SoftmaxScratch ws = softmax_scratch(s, n);
-  Tic t(s, NTS_KTAG_EDGE);
-  if (ws.pairs)
-    launch_reduce_as<false, 0>(s, p, f, EdgeIn{in},
-                               MaxSumToPairs{out, ws.pairs});
+  if (backward)
+    softmax_backward_passes(s, p, out, in, cached, batch, f, out2, pos2,
+                            lrelu_in, slope, dst_accum);
   else
-    launch_reduce_as<false, 0>(s, p, f, EdgeIn{in},
-                               SumToSums<true>{out, ws.sums});
-  launch_softmax_tail(s, p, out, ws, out2, pos2, f);
-  dbg_sync(s, "k_edge_softmax");
+    softmax_forward_passes(s, p, out, in, batch, f, out2, pos2);
   return p.edges;
 }
 
@@ -3637,7 +3736,8 @@ void nts_heads_dbg_general(nts_stream *s, int enable) {
 static void attention_forward(nts_stream *s, const EdgeItems &p, nts_vid K,
                               nts_vid batch, float *softmax_out,
                               float *softmax_out_perm, const nts_vid *perm_pos,
-                              const EdgeScore &score) {
+                              const EdgeScore &score,
+                              const NormEmitDropped *drop = nullptr) {
   s->softmax_stable_last = s->softmax_stable;
   if (!p.ib) return;
   const SoftmaxScratch ws = softmax_scratch(s, (uint64_t)batch * K);
@@ -3646,7 +3746,8 @@ static void attention_forward(nts_stream *s, const EdgeItems &p, nts_vid K,
     launch_reduce(s, p, K, score, MaxSumToPairs{softmax_out, ws.pairs});
   else
     launch_reduce(s, p, K, score, SumToSums<true>{softmax_out, ws.sums});
-  launch_softmax_tail(s, p, softmax_out, ws, softmax_out_perm, perm_pos, K);
+  launch_softmax_tail(s, p, softmax_out, ws, softmax_out_perm, perm_pos, K,
+                      drop);
   dbg_sync(s, "k_edge_att");
 }
 
@@ -3675,6 +3776,82 @@ void nts_edge_attention_forward_heads(
                     heads, batch_size, softmax_out, softmax_out_perm, perm_pos,
                     EdgeScore{m_sum_out, s_src_mirror, s_dst, row_indices,
                               mirror_index, slope, 0.f});
+}
+
+/* ---- attention dropout entries (additive; see include/nts_hip.h) ---- */
+
+/* the mask constants of (p, seed); p outside [0, 1) aborts (error culture of
+ * the header: the bindings check first) */
+static DropMask drop_mask(const char *entry, float p,
+                          unsigned long long seed) {
+  if (!(p >= 0.f && p < 1.f)) {
+    fprintf(stderr, "%s: dropout probability %g is not in [0, 1)\n", entry,
+            (double)p);
+    abort();
+  }
+  return DropMask{drop_fmix64(seed), (uint32_t)lrintf(p * 16777216.0f),
+                  1.0f / (1.0f - p)};
+}
+
+void nts_edge_dropout_keep(unsigned long long seed, float p,
+                           unsigned long long first, unsigned long long count,
+                           uint8_t *keep) {
+  const DropMask dm = drop_mask("nts_edge_dropout_keep", p, seed);
+  for (unsigned long long j = 0; j < count; ++j)
+    keep[j] = drop_keep(dm, first + j) ? 1 : 0;
+}
+
+void nts_edge_attention_forward_drop(
+    nts_stream *s, float *softmax_out, float *softmax_out_perm,
+    const nts_vid *perm_pos, float *m_sum_out, const float *s_src_mirror,
+    const float *s_dst, const nts_vid *row_indices,
+    const nts_vid *mirror_index, float slope, const nts_vid *column_offset,
+    nts_vid batch_size, nts_vid edges, nts_vid heads, float *alpha_out,
+    float p, unsigned long long seed) {
+  check_heads("nts_edge_attention_forward_drop", heads, heads);
+  const NormEmitDropped drop{
+      softmax_out, drop_mask("nts_edge_attention_forward_drop", p, seed)};
+  /* pass 1 stashes into alpha_out, which the normalize pass turns into the
+   * softmax while it writes the dropped weights to the two weight outputs */
+  attention_forward(s, edge_items_known(s, column_offset, batch_size, edges),
+                    heads, batch_size, alpha_out, softmax_out_perm, perm_pos,
+                    EdgeScore{m_sum_out, s_src_mirror, s_dst, row_indices,
+                              mirror_index, slope, 0.f},
+                    &drop);
+}
+
+void nts_edge_softmax_forward_drop(nts_stream *s, float *msg_output,
+                                   float *msg_output_perm,
+                                   const nts_vid *perm_pos,
+                                   const float *msg_input, float *msg_cached,
+                                   const nts_vid *column_offset,
+                                   nts_vid batch_size, nts_vid edges,
+                                   nts_vid feature_size, float p,
+                                   unsigned long long seed) {
+  const NormEmitDropped drop{
+      msg_output, drop_mask("nts_edge_softmax_forward_drop", p, seed)};
+  s->softmax_stable_last = s->softmax_stable;
+  if (!feature_size) return;
+  const EdgeItems it = edge_items_known(s, column_offset, batch_size, edges);
+  if (!it.ib) return;
+  softmax_forward_passes(s, it, msg_cached, msg_input, batch_size,
+                         feature_size, msg_output_perm, perm_pos, &drop);
+}
+
+void nts_edge_softmax_backward_drop(
+    nts_stream *s, float *msg_input_grad, float *msg_input_grad_perm,
+    const nts_vid *perm_pos, const float *msg_output_grad,
+    const float *msg_cached, const float *lrelu_input, float slope,
+    float *dst_sum, const nts_vid *column_offset, nts_vid batch_size,
+    nts_vid edges, nts_vid feature_size, float p, unsigned long long seed) {
+  const DropMask dm = drop_mask("nts_edge_softmax_backward_drop", p, seed);
+  if (dst_sum && feature_size != 1) abort(); /* as for the fused entry */
+  if (!feature_size) return;
+  const EdgeItems it = edge_items_known(s, column_offset, batch_size, edges);
+  if (!it.ib) return;
+  softmax_backward_passes(s, it, msg_input_grad, msg_output_grad, msg_cached,
+                          batch_size, feature_size, msg_input_grad_perm,
+                          perm_pos, lrelu_input, slope, dst_sum, &dm);
 }
 
 static void weight_sum(nts_stream *s, const EdgeItems &p, nts_vid K,

@@ -34,6 +34,13 @@ GATv2 (GATv2Layer, `attend_v2`): the score is att . leaky_relu(x_l[src] +
 x_r[dst]) per head, one f-wide edge pass and two backward walks of their own
 (nts_edge_gatv2_score, nts_edge_gatv2_backward); softmax, aggregation and the
 gradient with respect to the softmax are the heads entries above.
+
+Attention dropout (`dropout=p, seed=s` of both layers' forward, of `attend`
+and `attend_v2`): the gathers weigh with w = keep ? alpha / (1 - p) : 0, the
+keep mask a counter hash of (seed, CSC edge position, head) that the softmax's
+normalize pass applies while it writes and the softmax backward regenerates
+(nts_edge_attention_forward_drop, nts_edge_softmax_forward_drop,
+nts_edge_softmax_backward_drop); no mask tensor, no extra launch.
 """
 import numpy as np
 import torch
@@ -98,6 +105,14 @@ class _EdgeLayer:
         return self._soe
 
     @staticmethod
+    def _drop(dropout, seed):
+        """(p, seed) of a forward with attention dropout, None at
+        dropout == 0 (today's calls); an invalid pair raises ValueError
+        before any launch."""
+        shim.check_dropout(dropout, seed)
+        return (float(dropout), seed) if dropout > 0 else None
+
+    @staticmethod
     def _check_rows(name, t, rows, cols):
         """The kernels take raw pointers: anything but a contiguous float32
         device matrix of the expected shape raises before a launch."""
@@ -131,11 +146,28 @@ class GATLayer(_EdgeLayer):
         self._heads_path = heads > 1 or _heads_path
 
     def forward(self, h: torch.Tensor, s_src: torch.Tensor,
-                s_dst: torch.Tensor, negative_slope: float = 0.2):
+                s_dst: torch.Tensor, negative_slope: float = 0.2,
+                dropout: float = 0.0, seed: int = 0):
         """h: [V,f] projected features; s_src/s_dst: [V] attention scalars
-        ([V, heads] for a multi-head layer)."""
+        ([V, heads] for a multi-head layer).
+
+        dropout = p in [0, 1): attention dropout for training.  Each softmax
+        coefficient alpha[e, k] is dropped with probability p (exactly
+        round(p * 2^24) / 2^24) and the kept ones are scaled by 1 / (1 - p);
+        the mask is a function of (seed, CSC edge position, head) alone
+        (include/nts_hip.h, shim.edge_dropout_keep), regenerated in the
+        backward and never stored.  The aggregation and the backward's CSR
+        gather weigh with the dropped weights w, `saved` carries alpha (the
+        softmax backward's cache), w in CSC and CSR order, p and seed, so the
+        layer retains 4*E*K more bytes than without dropout.  A destination
+        all of whose in-edges drop gets a zero row.  dropout == 0.0 (the
+        default, and what evaluation passes: there is no train/eval flag)
+        makes exactly the calls of a layer without the argument.  seed is an
+        int in [0, 2**64); an invalid dropout or seed raises ValueError before
+        any launch."""
+        drop = self._drop(dropout, seed)
         if self._heads_path:
-            return self._forward_heads(h, s_src, s_dst, negative_slope)
+            return self._forward_heads(h, s_src, s_dst, negative_slope, drop)
         ch, st, E = self.ch, self.stream, self.E
         dev = h.device
         h = h.contiguous()
@@ -149,23 +181,30 @@ class GATLayer(_EdgeLayer):
         # the normalize pass dual-emits the softmax in CSC (s) and CSR
         # (s_csr) edge order.  cache = output (reference convention), so
         # `s` doubles as the backward's cached tensor.
-        st.edge_attention_forward(s.data_ptr(), s_csr.data_ptr(),
-                                  self._inv_perm_u32.data_ptr(),
-                                  m_sum.data_ptr(),
-                                  s_src.contiguous().data_ptr(),
-                                  s_dst.contiguous().data_ptr(),
-                                  ch.row_indices.data_ptr(),
-                                  self.mirror_index.data_ptr(),
-                                  negative_slope,
-                                  ch.column_offset.data_ptr(), ch.dst_n)
+        args = (s.data_ptr(), s_csr.data_ptr(), self._inv_perm_u32.data_ptr(),
+                m_sum.data_ptr(), s_src.contiguous().data_ptr(),
+                s_dst.contiguous().data_ptr(), ch.row_indices.data_ptr(),
+                self.mirror_index.data_ptr(), negative_slope,
+                ch.column_offset.data_ptr(), ch.dst_n)
+        if drop:
+            # the same two passes (one column, host-known edge count): the
+            # normalize pass leaves the softmax in alpha, for the backward,
+            # and dual-emits the dropped weights into s and s_csr
+            alpha = torch.empty(E, 1, device=dev)
+            st.edge_attention_forward_drop(*args, E, 1, alpha.data_ptr(),
+                                           *drop)
+            saved = {"h": h, "alpha": alpha, "w": s, "w_csr": s_csr,
+                     "m_sum": m_sum, "p": drop[0], "seed": drop[1]}
+        else:
+            st.edge_attention_forward(*args)
+            saved = {"h": h, "s": s, "s_csr": s_csr, "cached": s,
+                     "m_sum": m_sum}
         y = torch.zeros(ch.dst_n, h.shape[1], device=dev)
         st.gather_by_dst_from_src(h.data_ptr(), y.data_ptr(), s.data_ptr(),
                                   ch.row_indices.data_ptr(),
                                   ch.column_offset.data_ptr(),
                                   ch.src_s, ch.src_e, ch.dst_s, ch.dst_e,
                                   E, ch.dst_n, h.shape[1], with_weight=True)
-        saved = {"h": h, "s": s, "s_csr": s_csr, "cached": s,
-                 "m_sum": m_sum}
         return y, saved
 
     def backward(self, grad_y: torch.Tensor, saved,
@@ -187,10 +226,14 @@ class GATLayer(_EdgeLayer):
         # (round-1: ~9 ms/step at f=128) and the s permute (dual-order
         # softmax output from forward).  rc=0 -> width not fused (ragged /
         # multi-slab f): the plain gather ran; do the dot separately.
+        # after a forward with dropout the gather's weights are the dropped
+        # ones (w_csr) and gs is the gradient with respect to them
+        dropped = "p" in saved
+        s_csr = saved["w_csr"] if dropped else saved["s_csr"]
         gs = torch.empty(E, 1, device=dev)
         grad_h = torch.zeros(ch.src_n, f, device=dev)
         rc = st.gather_by_src_from_dst_dot(
-            grad_y.data_ptr(), grad_h.data_ptr(), saved["s_csr"].data_ptr(),
+            grad_y.data_ptr(), grad_h.data_ptr(), s_csr.data_ptr(),
             ch.row_offset.data_ptr(), ch.column_indices.data_ptr(),
             ch.dst_s, ch.src_n, E, f, saved["h"].data_ptr(), gs.data_ptr(),
             self._perm_u32.data_ptr())
@@ -204,12 +247,21 @@ class GATLayer(_EdgeLayer):
         ge = torch.empty(E, 1, device=dev)
         ge_csr = torch.empty(E, 1, device=dev)
         g_dst = torch.zeros(ch.dst_n, 1, device=dev)
-        st.edge_softmax_backward_fused(
-            ge.data_ptr(), ge_csr.data_ptr(), self._inv_perm_u32.data_ptr(),
-            gs.data_ptr(), saved["cached"].data_ptr(),
-            saved["m_sum"].contiguous().data_ptr(), negative_slope,
-            ch.column_offset.data_ptr(), ch.dst_n, 1,
-            dst_sum=g_dst.data_ptr())
+        if dropped:
+            st.edge_softmax_backward_drop(
+                ge.data_ptr(), ge_csr.data_ptr(),
+                self._inv_perm_u32.data_ptr(), gs.data_ptr(),
+                saved["alpha"].data_ptr(), saved["m_sum"].data_ptr(),
+                negative_slope, ch.column_offset.data_ptr(), ch.dst_n, E, 1,
+                saved["p"], saved["seed"], dst_sum=g_dst.data_ptr())
+        else:
+            st.edge_softmax_backward_fused(
+                ge.data_ptr(), ge_csr.data_ptr(),
+                self._inv_perm_u32.data_ptr(), gs.data_ptr(),
+                saved["cached"].data_ptr(),
+                saved["m_sum"].contiguous().data_ptr(), negative_slope,
+                ch.column_offset.data_ptr(), ch.dst_n, 1,
+                dst_sum=g_dst.data_ptr())
         # edge-scalar -> vertex reductions through the load-balanced gather
         # kernel (per-edge values as WEIGHTS over an all-ones input): the
         # direct msg->vertex atomics serialize on power-law hub sources
@@ -238,8 +290,9 @@ class GATLayer(_EdgeLayer):
                 f"{name} has {f} columns, not a multiple of heads={self.heads}")
         return f
 
-    def _forward_heads(self, h, s_src, s_dst, negative_slope):
-        """h: [V, K*C]; s_src/s_dst: [V, K].  Returns (y[V, K*C], saved)."""
+    def _forward_heads(self, h, s_src, s_dst, negative_slope, drop=None):
+        """h: [V, K*C]; s_src/s_dst: [V, K].  Returns (y[V, K*C], saved).
+        drop: None or the (p, seed) of forward's dropout."""
         ch, st, E, K = self.ch, self.stream, self.E, self.heads
         f = self._width("h", h)
         self._check_rows("h", h, ch.src_n, f)
@@ -250,17 +303,25 @@ class GATLayer(_EdgeLayer):
         s = torch.empty(E, K, device=dev)
         s_csr = torch.empty(E, K, device=dev)
         m_sum = torch.empty(E, K, device=dev)
-        st.edge_attention_forward_heads(
-            s.data_ptr(), s_csr.data_ptr(), self._inv_perm_u32.data_ptr(),
-            m_sum.data_ptr(), s_src.data_ptr(), s_dst.data_ptr(),
-            ch.row_indices.data_ptr(), self.mirror_index.data_ptr(),
-            negative_slope, ch.column_offset.data_ptr(), ch.dst_n, E, K)
+        args = (s.data_ptr(), s_csr.data_ptr(), self._inv_perm_u32.data_ptr(),
+                m_sum.data_ptr(), s_src.data_ptr(), s_dst.data_ptr(),
+                ch.row_indices.data_ptr(), self.mirror_index.data_ptr(),
+                negative_slope, ch.column_offset.data_ptr(), ch.dst_n, E, K)
+        if drop:
+            # s, s_csr: the dropped weights; alpha: the softmax, for backward
+            alpha = torch.empty(E, K, device=dev)
+            st.edge_attention_forward_drop(*args, alpha.data_ptr(), *drop)
+            saved = {"h": h, "alpha": alpha, "w": s, "w_csr": s_csr,
+                     "m_sum": m_sum, "p": drop[0], "seed": drop[1]}
+        else:
+            st.edge_attention_forward_heads(*args)
+            saved = {"h": h, "s": s, "s_csr": s_csr, "cached": s,
+                     "m_sum": m_sum}
         y = torch.zeros(ch.dst_n, f, device=dev)
         st.gather_by_dst_from_src_heads(
             h.data_ptr(), y.data_ptr(), s.data_ptr(),
             ch.row_indices.data_ptr(), ch.column_offset.data_ptr(),
             ch.src_s, ch.src_e, ch.dst_s, ch.dst_e, E, ch.dst_n, f, K)
-        saved = {"h": h, "s": s, "s_csr": s_csr, "cached": s, "m_sum": m_sum}
         return y, saved
 
     def _backward_heads(self, grad_y, saved, negative_slope):
@@ -276,9 +337,11 @@ class GATLayer(_EdgeLayer):
         # the fused gather-dot is single-head: the CSR gather (weights in CSR
         # order from the forward's dual emission) and the per-head dot
         # gs[e, k] = grad_y[dst(e), head k] . h[src(e), head k] run apart
+        dropped = "p" in saved   # then the weights are w and gs is dL/dw
+        s_csr = saved["w_csr"] if dropped else saved["s_csr"]
         grad_h = torch.zeros(ch.src_n, f, device=dev)
         st.gather_by_src_from_dst_heads(
-            grad_y.data_ptr(), grad_h.data_ptr(), saved["s_csr"].data_ptr(),
+            grad_y.data_ptr(), grad_h.data_ptr(), s_csr.data_ptr(),
             ch.row_offset.data_ptr(), ch.column_indices.data_ptr(),
             ch.src_s, ch.src_e, ch.dst_s, ch.dst_e, E, ch.src_n, f, K)
         gs = torch.empty(E, K, device=dev)
@@ -288,11 +351,20 @@ class GATLayer(_EdgeLayer):
                           f, K)
         ge = torch.empty(E, K, device=dev)
         ge_csr = torch.empty(E, K, device=dev)
-        st.edge_softmax_backward_fused(
-            ge.data_ptr(), ge_csr.data_ptr(), self._inv_perm_u32.data_ptr(),
-            gs.data_ptr(), saved["cached"].data_ptr(),
-            saved["m_sum"].data_ptr(), negative_slope,
-            ch.column_offset.data_ptr(), ch.dst_n, K, dst_sum=None)
+        if dropped:
+            st.edge_softmax_backward_drop(
+                ge.data_ptr(), ge_csr.data_ptr(),
+                self._inv_perm_u32.data_ptr(), gs.data_ptr(),
+                saved["alpha"].data_ptr(), saved["m_sum"].data_ptr(),
+                negative_slope, ch.column_offset.data_ptr(), ch.dst_n, E, K,
+                saved["p"], saved["seed"], dst_sum=None)
+        else:
+            st.edge_softmax_backward_fused(
+                ge.data_ptr(), ge_csr.data_ptr(),
+                self._inv_perm_u32.data_ptr(), gs.data_ptr(),
+                saved["cached"].data_ptr(), saved["m_sum"].data_ptr(),
+                negative_slope, ch.column_offset.data_ptr(), ch.dst_n, K,
+                dst_sum=None)
         # per-(vertex, head) sums of the edge gradient: by source over the
         # CSR order, by destination over the CSC order (the softmax
         # backward's own dst_sum emission is single-column)
@@ -311,10 +383,12 @@ class _AttendFn(torch.autograd.Function):
     ops._AggregateFn): gradients flow to h, s_src and s_dst."""
 
     @staticmethod
-    def forward(ctx, h, s_src, s_dst, layer, negative_slope):
+    def forward(ctx, h, s_src, s_dst, layer, negative_slope, dropout=0.0,
+                seed=0):
         y, saved = layer.forward(h.detach().contiguous(),
                                  s_src.detach().contiguous(),
-                                 s_dst.detach().contiguous(), negative_slope)
+                                 s_dst.detach().contiguous(), negative_slope,
+                                 dropout, seed)
         ctx.layer, ctx.saved, ctx.slope = layer, saved, negative_slope
         ctx.scalar_shapes = (s_src.shape, s_dst.shape)
         return y
@@ -324,16 +398,33 @@ class _AttendFn(torch.autograd.Function):
         grad_h, g_src, g_dst = ctx.layer.backward(grad_y.contiguous(),
                                                   ctx.saved, ctx.slope)
         return (grad_h, g_src.reshape(ctx.scalar_shapes[0]),
-                g_dst.reshape(ctx.scalar_shapes[1]), None, None)
+                g_dst.reshape(ctx.scalar_shapes[1]), None, None, None, None)
+
+
+def _draw_seed(dropout, seed):
+    """The seed of an attend call: the caller's, or for seed=None a draw from
+    torch's default CPU generator (reproducible under torch.manual_seed, no
+    device synchronize).  Checked here, so nothing is drawn or launched for
+    an invalid pair."""
+    shim.check_dropout(dropout, 0 if seed is None else seed)
+    if seed is not None:
+        return seed
+    if dropout == 0:   # nothing to mask: the generator is left alone
+        return 0
+    return int(torch.randint(0, 2**63 - 1, (1,), dtype=torch.int64))
 
 
 def attend(h: torch.Tensor, s_src: torch.Tensor, s_dst: torch.Tensor,
-           layer: GATLayer, negative_slope: float = 0.2) -> torch.Tensor:
+           layer: GATLayer, negative_slope: float = 0.2,
+           dropout: float = 0.0, seed=None) -> torch.Tensor:
     """Autograd-aware attention-weighted aggregation on `layer`'s graph:
     y = layer.forward(h, s_src, s_dst), differentiable in all three.  The
     projections stay in torch, e.g. for K heads of C columns
-    s_src = (h.view(V, K, C) * a_src).sum(-1) with a_src of shape [K, C]."""
-    return _AttendFn.apply(h, s_src, s_dst, layer, negative_slope)
+    s_src = (h.view(V, K, C) * a_src).sum(-1) with a_src of shape [K, C].
+    dropout, seed: attention dropout as for GATLayer.forward (pass 0.0 for
+    evaluation); seed=None draws one from torch's default CPU generator."""
+    return _AttendFn.apply(h, s_src, s_dst, layer, negative_slope, dropout,
+                           _draw_seed(dropout, seed))
 
 
 class GATv2Layer(_EdgeLayer):
@@ -371,9 +462,14 @@ class GATv2Layer(_EdgeLayer):
         return f
 
     def forward(self, x_l: torch.Tensor, x_r: torch.Tensor, att: torch.Tensor,
-                negative_slope: float = 0.2):
+                negative_slope: float = 0.2, dropout: float = 0.0,
+                seed: int = 0):
         """x_l: [src_n, K*C], x_r: [dst_n, K*C], att: [K, C].  Returns
-        (y[dst_n, K*C], saved)."""
+        (y[dst_n, K*C], saved).  dropout, seed: attention dropout exactly as
+        for GATLayer.forward — `saved` then carries alpha (the cache), w and
+        w_csr (the dropped gather weights), p and seed, 4*E*K more bytes
+        than without; dropout == 0.0 makes today's calls."""
+        drop = self._drop(dropout, seed)
         ch, st, E, K = self.ch, self.stream, self.E, self.heads
         f = self._check_inputs(x_l, x_r, att)
         dev = x_l.device
@@ -386,18 +482,29 @@ class GATv2Layer(_EdgeLayer):
         # per-(destination, head) softmax, dual-emitted in CSC (alpha) and
         # CSR (alpha_csr) edge order; cache = output
         alpha = torch.empty(E, K, device=dev)
-        alpha_csr = torch.empty(E, K, device=dev)
-        st.edge_softmax_forward_dual(
-            alpha.data_ptr(), alpha_csr.data_ptr(),
-            self._inv_perm_u32.data_ptr(), score.data_ptr(), alpha.data_ptr(),
-            ch.column_offset.data_ptr(), ch.dst_n, K)
+        saved = {"x_l": x_l, "x_r": x_r, "att": att, "alpha": alpha}
+        if drop:
+            # alpha stays the softmax; w, w_csr are the dropped weights
+            w = torch.empty(E, K, device=dev)
+            w_csr = torch.empty(E, K, device=dev)
+            st.edge_softmax_forward_drop(
+                w.data_ptr(), w_csr.data_ptr(), self._inv_perm_u32.data_ptr(),
+                score.data_ptr(), alpha.data_ptr(),
+                ch.column_offset.data_ptr(), ch.dst_n, E, K, *drop)
+            saved.update(w=w, w_csr=w_csr, p=drop[0], seed=drop[1])
+        else:
+            w = alpha
+            alpha_csr = torch.empty(E, K, device=dev)
+            st.edge_softmax_forward_dual(
+                alpha.data_ptr(), alpha_csr.data_ptr(),
+                self._inv_perm_u32.data_ptr(), score.data_ptr(),
+                alpha.data_ptr(), ch.column_offset.data_ptr(), ch.dst_n, K)
+            saved["alpha_csr"] = alpha_csr
         y = torch.zeros(ch.dst_n, f, device=dev)
         st.gather_by_dst_from_src_heads(
-            x_l.data_ptr(), y.data_ptr(), alpha.data_ptr(),
+            x_l.data_ptr(), y.data_ptr(), w.data_ptr(),
             ch.row_indices.data_ptr(), ch.column_offset.data_ptr(),
             ch.src_s, ch.src_e, ch.dst_s, ch.dst_e, E, ch.dst_n, f, K)
-        saved = {"x_l": x_l, "x_r": x_r, "att": att, "alpha": alpha,
-                 "alpha_csr": alpha_csr}
         return y, saved
 
     def backward(self, grad_y: torch.Tensor, saved,
@@ -415,10 +522,12 @@ class GATv2Layer(_EdgeLayer):
         st.items_reuse(1)
         # through alpha: the aggregation's own gradient to x_l, and the
         # per-head dot that is the gradient with respect to alpha
+        dropped = "p" in saved   # then the weights are w and galpha is dL/dw
+        w_csr = saved["w_csr"] if dropped else saved["alpha_csr"]
         grad_xl = torch.zeros(ch.src_n, f, device=dev)
         st.gather_by_src_from_dst_heads(
             grad_y.data_ptr(), grad_xl.data_ptr(),
-            saved["alpha_csr"].data_ptr(), ch.row_offset.data_ptr(),
+            w_csr.data_ptr(), ch.row_offset.data_ptr(),
             ch.column_indices.data_ptr(), ch.src_s, ch.src_e, ch.dst_s,
             ch.dst_e, E, ch.src_n, f, K)
         galpha = torch.empty(E, K, device=dev)
@@ -430,11 +539,19 @@ class GATv2Layer(_EdgeLayer):
         # per column, inside the two walks below), dual-emitted
         gscore = torch.empty(E, K, device=dev)
         gscore_csr = torch.empty(E, K, device=dev)
-        st.edge_softmax_backward_fused(
-            gscore.data_ptr(), gscore_csr.data_ptr(),
-            self._inv_perm_u32.data_ptr(), galpha.data_ptr(),
-            saved["alpha"].data_ptr(), None, negative_slope,
-            ch.column_offset.data_ptr(), ch.dst_n, K, dst_sum=None)
+        if dropped:
+            st.edge_softmax_backward_drop(
+                gscore.data_ptr(), gscore_csr.data_ptr(),
+                self._inv_perm_u32.data_ptr(), galpha.data_ptr(),
+                saved["alpha"].data_ptr(), None, negative_slope,
+                ch.column_offset.data_ptr(), ch.dst_n, E, K, saved["p"],
+                saved["seed"], dst_sum=None)
+        else:
+            st.edge_softmax_backward_fused(
+                gscore.data_ptr(), gscore_csr.data_ptr(),
+                self._inv_perm_u32.data_ptr(), galpha.data_ptr(),
+                saved["alpha"].data_ptr(), None, negative_slope,
+                ch.column_offset.data_ptr(), ch.dst_n, K, dst_sum=None)
         # CSC walk: own = x_r, nbr = x_l -> grad_x_r and grad_att
         grad_xr = torch.zeros(ch.dst_n, f, device=dev)
         grad_att = torch.zeros(K, f // K, device=dev)
@@ -456,9 +573,10 @@ class _AttendV2Fn(torch.autograd.Function):
     """torch.autograd bridge over GATv2Layer.forward/backward."""
 
     @staticmethod
-    def forward(ctx, x_l, x_r, att, layer, negative_slope):
+    def forward(ctx, x_l, x_r, att, layer, negative_slope, dropout=0.0,
+                seed=0):
         y, saved = layer.forward(x_l.detach(), x_r.detach(), att.detach(),
-                                 negative_slope)
+                                 negative_slope, dropout, seed)
         ctx.layer, ctx.saved, ctx.slope = layer, saved, negative_slope
         return y
 
@@ -466,14 +584,17 @@ class _AttendV2Fn(torch.autograd.Function):
     def backward(ctx, grad_y):
         grad_xl, grad_xr, grad_att = ctx.layer.backward(
             grad_y.contiguous(), ctx.saved, ctx.slope)
-        return grad_xl, grad_xr, grad_att, None, None
+        return grad_xl, grad_xr, grad_att, None, None, None, None
 
 
 def attend_v2(x_l: torch.Tensor, x_r: torch.Tensor, att: torch.Tensor,
-              layer: GATv2Layer, negative_slope: float = 0.2) -> torch.Tensor:
+              layer: GATv2Layer, negative_slope: float = 0.2,
+              dropout: float = 0.0, seed=None) -> torch.Tensor:
     """Autograd-aware GATv2 aggregation on `layer`'s graph, differentiable in
     x_l [src_n, K*C], x_r [dst_n, K*C] and att [K, C] (all float32,
     contiguous, on the device; anything else raises before a launch).  The
     projections stay in torch: x_l = x @ W_l, x_r = x @ W_r.  Weight sharing
-    (x_l is x_r) needs no special case: autograd adds the two gradients."""
-    return _AttendV2Fn.apply(x_l, x_r, att, layer, negative_slope)
+    (x_l is x_r) needs no special case: autograd adds the two gradients.
+    dropout, seed: attention dropout as for `attend`."""
+    return _AttendV2Fn.apply(x_l, x_r, att, layer, negative_slope, dropout,
+                             _draw_seed(dropout, seed))

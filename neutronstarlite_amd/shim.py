@@ -131,6 +131,17 @@ def lib():
         [_vp] + [_vp] * 6 + [_c.c_float] + [_vp] * 2 + [_u32] * 5)
     l.nts_edge_softmax_stable.argtypes = [_vp, _i32]
     l.nts_edge_softmax_stable_last.argtypes = [_vp, _vp]
+    # attention dropout
+    l.nts_edge_dropout_keep.argtypes = (
+        [_c.c_ulonglong, _c.c_float] + [_c.c_ulonglong] * 2 + [_vp])
+    l.nts_edge_attention_forward_drop.argtypes = (
+        l.nts_edge_attention_forward_heads.argtypes
+        + [_vp, _c.c_float, _c.c_ulonglong])
+    l.nts_edge_softmax_forward_drop.argtypes = (
+        [_vp] + [_vp] * 6 + [_u32] * 3 + [_c.c_float, _c.c_ulonglong])
+    l.nts_edge_softmax_backward_drop.argtypes = (
+        [_vp] + [_vp] * 6 + [_c.c_float] + [_vp] * 2 + [_u32] * 3
+        + [_c.c_float, _c.c_ulonglong])
     # max / min aggregation
     l.nts_reduce_by_dst_from_src.argtypes = (
         [_vp, _i32] + [_vp] * 5 + [_u32] * 7)
@@ -250,6 +261,34 @@ def gather_plan_heads(f, heads, alignment, batch, edges):
     lib().nts_gather_plan_heads(f, heads, alignment, batch, edges,
                                 *[_c.byref(o) for o in out])
     return {n: o.value for n, o in zip(names, out)}
+
+
+def check_dropout(p, seed):
+    """p a float (or int) that is in [0, 1) as a float32, seed an int in
+    [0, 2**64), else ValueError — the library aborts on such a p, so every
+    dropout binding checks before it calls."""
+    if (isinstance(p, bool) or not isinstance(p, (float, int))
+            or not 0 <= p < 1 or _c.c_float(p).value >= 1.0):
+        raise ValueError(
+            f"dropout={p!r} must be a float in [0, 1) (as a float32)")
+    if (isinstance(seed, bool) or not isinstance(seed, int)
+            or not 0 <= seed < 2 ** 64):
+        raise ValueError(f"seed={seed!r} must be an int in [0, 2**64)")
+
+
+def edge_dropout_keep(seed, p, first, count):
+    """The attention-dropout keep mask as the kernels compute it (no device
+    access; the mask is defined in include/nts_hip.h): a numpy bool array,
+    element j for position first + j, position = edge * K + head with the
+    edge's chunk-local CSC position."""
+    import numpy as np
+    check_dropout(p, seed)
+    if (not isinstance(first, int) or not isinstance(count, int)
+            or first < 0 or count < 0 or first + count > 2 ** 64):
+        raise ValueError("first, count must be ints with first + count <= 2**64")
+    keep = np.zeros(count, dtype=np.uint8)
+    lib().nts_edge_dropout_keep(seed, p, first, count, keep.ctypes.data)
+    return keep.astype(bool)
 
 
 # enum nts_reduce_op and NTS_NO_EDGE in include/nts_hip.h
@@ -640,9 +679,10 @@ class Stream:
 
     def edge_softmax_stable(self, enable):
         """Max-subtracted softmax in the following edge_softmax_forward,
-        edge_softmax_forward_dual, edge_attention_forward and
-        edge_attention_forward_heads calls of this wrapper (default off: the
-        reference's exp / sum exp, NaN past a score of about 88)."""
+        edge_softmax_forward_dual, edge_attention_forward,
+        edge_attention_forward_heads and *_forward_drop calls of this wrapper
+        (default off: the reference's exp / sum exp, NaN past a score of
+        about 88)."""
         self._lib.nts_edge_softmax_stable(self.h, 1 if enable else 0)
 
     def edge_softmax_stable_last(self):
@@ -650,6 +690,46 @@ class Stream:
         stable = _i32(0)
         self._lib.nts_edge_softmax_stable_last(self.h, _c.byref(stable))
         return stable.value
+
+    # ---- attention dropout; (p, seed) is checked here, the library aborts
+    # on an invalid p ----
+    def edge_attention_forward_drop(self, softmax_out, softmax_out_perm,
+                                    perm_pos, m_sum_out, s_src_mirror, s_dst,
+                                    row_indices, mirror_index, slope,
+                                    column_offset, batch, edges, heads,
+                                    alpha_out, p, seed):
+        """edge_attention_forward_heads under dropout: alpha_out gets the
+        softmax, softmax_out / softmax_out_perm the dropped weights
+        keep ? alpha / (1 - p) : 0.  alpha_out must not alias them."""
+        check_heads(heads, heads)
+        check_dropout(p, seed)
+        self._lib.nts_edge_attention_forward_drop(
+            self.h, _vp(softmax_out), _vp(softmax_out_perm), _vp(perm_pos),
+            _vp(m_sum_out), _vp(s_src_mirror), _vp(s_dst), _vp(row_indices),
+            _vp(mirror_index), slope, _vp(column_offset), batch, edges, heads,
+            _vp(alpha_out), p, seed)
+
+    def edge_softmax_forward_drop(self, out, out_perm, perm_pos, inp, cached,
+                                  column_offset, batch, edges, f, p, seed):
+        """edge_softmax_forward_dual under dropout with a caller-known edge
+        count: cached gets the softmax (distinct from out), out / out_perm
+        the dropped weights."""
+        check_dropout(p, seed)
+        self._lib.nts_edge_softmax_forward_drop(
+            self.h, _vp(out), _vp(out_perm), _vp(perm_pos), _vp(inp),
+            _vp(cached), _vp(column_offset), batch, edges, f, p, seed)
+
+    def edge_softmax_backward_drop(self, in_grad, in_grad_perm, perm_pos,
+                                   out_grad, cached, lrelu_input, slope,
+                                   column_offset, batch, edges, f, p, seed,
+                                   dst_sum=None):
+        """edge_softmax_backward_fused where out_grad is the gradient of the
+        dropped weights of (p, seed) and cached the undropped softmax."""
+        check_dropout(p, seed)
+        self._lib.nts_edge_softmax_backward_drop(
+            self.h, _vp(in_grad), _vp(in_grad_perm), _vp(perm_pos),
+            _vp(out_grad), _vp(cached), _vp(lrelu_input), slope,
+            _vp(dst_sum), _vp(column_offset), batch, edges, f, p, seed)
 
     def destroy(self):
         if self.h:

@@ -154,7 +154,7 @@ void nts_gather_by_src_from_dst_bf16(nts_stream *s,
  * the sizes at which the column schedules engage.  heads == 1 IS the scalar
  * entry with with_weight = 1 (same launch); heads == feature_size is the
  * reference's tensor_weight form.  heads == 0, heads > feature_size or
- * feature_size % heads != 0 aborts.  fp32 rows only. */
+ * feature_size % heads != 0 aborts.  fp32 rows; the bf16 pair follows. */
 void nts_gather_by_dst_from_src_heads(nts_stream *s,
     const float *input, float *output, const float *weight_forward,
     const nts_vid *row_indices, const nts_vid *column_offset,
@@ -170,6 +170,40 @@ void nts_gather_by_src_from_dst_heads(nts_stream *s,
  * nts_gather_plan): lane group, dwords per lane (4, 2 or 1) and grid.  With
  * heads == 1 these are nts_gather_plan's for the request (0, -1). */
 void nts_gather_plan_heads(nts_vid feature_size, nts_vid heads,
+    unsigned alignment_bytes, nts_vid batch_size, nts_vid edges,
+    int *lane_group, int *vector_width, int *grid);
+
+/* The heads gathers over bfloat16 rows (additive): `input` as for the scalar
+ * bf16 gathers (raw uint16_t, row pitch 2*feature_size bytes, any 2-byte
+ * alignment), weights [edges, K], accumulation and `output` fp32, every other
+ * part of the contract that of the fp32 heads pair.  A bf16 value is widened
+ * exactly, and each output element is one fp32 fmaf chain over the item's
+ * edges in edge order whatever the lane width, so for a vertex that is not
+ * split the result is bit-identical to the fp32 heads entry run on the
+ * widened rows.  Elements per lane: the widest of 8 / 4 / 2 that divides C as
+ * well as feature_size and that the pointers' alignment permits — the input
+ * load is 16 / 8 / 4 bytes, and the output is accessed in vectors of half as
+ * many floats, so it needs the same 16 / 8 / 4 bytes, the rule of
+ * nts_gather_plan_bf16 — else 4 strided 2-byte loads per lane with the head
+ * of each element.  Lane group: the smallest power of two in [16, 64] that
+ * covers feature_size / (elements per lane); grid: (batch_size + edges /
+ * NTS_SPLIT + 1) * slabs * lane group threads in workgroups of 256, under
+ * the block cap.  heads == 1 IS the scalar bf16 entry with with_weight = 1. */
+void nts_gather_by_dst_from_src_heads_bf16(nts_stream *s,
+    const uint16_t *input, float *output, const float *weight_forward,
+    const nts_vid *row_indices, const nts_vid *column_offset,
+    nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
+    nts_vid edges, nts_vid batch_size, nts_vid feature_size, nts_vid heads);
+void nts_gather_by_src_from_dst_heads_bf16(nts_stream *s,
+    const uint16_t *input, float *output, const float *weight_backward,
+    const nts_vid *row_offset, const nts_vid *column_indices,
+    nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
+    nts_vid edges, nts_vid batch_size, nts_vid feature_size, nts_vid heads);
+
+/* nts_gather_plan_heads for bf16 rows: vector_width is in elements per lane
+ * (8, 4, 2 or 1), alignment_bytes the common alignment of input and output.
+ * With heads == 1 these are nts_gather_plan_bf16's for the request (0, -1). */
+void nts_gather_plan_heads_bf16(nts_vid feature_size, nts_vid heads,
     unsigned alignment_bytes, nts_vid batch_size, nts_vid edges,
     int *lane_group, int *vector_width, int *grid);
 
@@ -640,6 +674,44 @@ void nts_edge_gatv2_backward(nts_stream *s, float *grad_own, float *grad_att,
     const float *att, float slope, const nts_vid *offset,
     const nts_vid *nbr_indices, nts_vid nbr_start, nts_vid batch_size,
     nts_vid edges, nts_vid feature_size, nts_vid heads);
+
+/* ---- bfloat16 feature rows for the attention passes (additive) ----
+ * nts_edge_dot_heads, nts_edge_gatv2_score and nts_edge_gatv2_backward with
+ * feature rows stored as bfloat16 (raw uint16_t, row pitch 2*feature_size
+ * bytes, any 2-byte alignment).  Only the operands typed uint16_t below are
+ * bf16; att, grad_score, every [edges, K] value, every accumulator and every
+ * output stay fp32.  A bf16 value is widened exactly in registers, so each
+ * entry computes what its fp32 twin computes on the widened rows; for the
+ * GATv2 pair t is ONE fp32 add of the two widened values.  Error culture,
+ * NTS_KTAG_EDGE, the item cache, NTS_SPLIT and nts_heads_dbg_general are the
+ * fp32 entries'; batch_size == 0 or edges == 0 launches nothing and writes
+ * nothing.
+ *   Columns per lane: R = the widest of 4 / 2 / 1 that divides C and that
+ * every pointer permits by its own element size: R*4 bytes of alignment for
+ * an fp32 operand (and for grad_own), R*2 bytes for a bf16 one.  R = 1 and
+ * the general forms take 2-byte loads and run at any element offset.  With
+ * the R of the fp32 twin (the same form, and pointers that give the twin the
+ * same R, e.g. all 16-byte aligned) a lane sums the same columns in the same
+ * order and the segment butterfly is the same: the score entries are then
+ * bit-identical to the fp32 entries on the widened rows, and so is grad_own
+ * on a vertex that is not split.
+ *   nts_edge_dot_heads_bf16: dst_rows fp32 (the attention layers pass
+ * grad_y), src_rows bf16.  heads == 1 runs the row-pair forms with K = 1;
+ * the wave-per-edge kernel of nts_edge_dot stays fp32 only. */
+void nts_edge_dot_heads_bf16(nts_stream *s, float *out, const float *dst_rows,
+    const uint16_t *src_rows, const nts_vid *row_indices,
+    const nts_vid *column_offset, nts_vid src_start, nts_vid batch_size,
+    nts_vid edges, nts_vid feature_size, nts_vid heads);
+void nts_edge_gatv2_score_bf16(nts_stream *s, float *score,
+    const uint16_t *dst_rows, const uint16_t *src_rows, const float *att,
+    float slope, const nts_vid *row_indices, const nts_vid *column_offset,
+    nts_vid src_start, nts_vid batch_size, nts_vid edges,
+    nts_vid feature_size, nts_vid heads);
+void nts_edge_gatv2_backward_bf16(nts_stream *s, float *grad_own,
+    float *grad_att, const float *grad_score, const uint16_t *own_rows,
+    const uint16_t *nbr_rows, const float *att, float slope,
+    const nts_vid *offset, const nts_vid *nbr_indices, nts_vid nbr_start,
+    nts_vid batch_size, nts_vid edges, nts_vid feature_size, nts_vid heads);
 
 /* ---- numerically stable edge softmax (additive) ----
  * A request on the stream, as nts_gather_staging is; it reads no environment.

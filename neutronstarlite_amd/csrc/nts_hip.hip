@@ -786,13 +786,19 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm_stripe(
  * ew[e*K + c/C].  ELEM = 4 or 2 is chosen to divide C as well as f, so a
  * lane's vector never straddles two heads and the lane loads ONE weight per
  * edge (f % ELEM == 0: every live lane is full, there is no ragged lane);
- * ELEM = 1 runs 4 strided dwords per lane with the head of each element. */
-template <int ELEM, int NE>
+ * ELEM = 1 runs 4 strided dwords per lane with the head of each element.
+ * T = row element type of `in`, as for k_gather_spmm: with uint16_t (bf16)
+ * rows ELEM is 8, 4 or 2 (one 16-, 8- or 4-byte load; `out` is accessed in
+ * vectors of ELEM/2 floats), or 1 with 4 strided 2-byte loads, which is the
+ * form for any 2-byte alignment of `in`.  Weights, accumulators and `out` are
+ * fp32, and each output element is the fp32 instantiation's fmaf chain on
+ * the widened values whatever the lane width. */
+template <int ELEM, int NE, typename T>
 __device__ __forceinline__ void heads_edges_vec(float (&acc)[ELEM],
-                                                const GatherSrc<float> &g,
+                                                const GatherSrc<T> &g,
                                                 uint32_t e, uint32_t col,
                                                 uint32_t K, uint32_t head) {
-  const float *p[NE];
+  const T *p[NE];
   float wv[NE];
 #pragma unroll
   for (int k = 0; k < NE; ++k) {
@@ -803,11 +809,11 @@ __device__ __forceinline__ void heads_edges_vec(float (&acc)[ELEM],
 }
 /* strided twin: element j at column col + j*G, head hd[j], live while
  * col + j*G < f */
-template <int NSTR, int NE>
+template <int NSTR, int NE, typename T>
 __device__ __forceinline__ void heads_edges_strided(
-    float (&acc)[NSTR], const GatherSrc<float> &g, uint32_t e, uint32_t col,
+    float (&acc)[NSTR], const GatherSrc<T> &g, uint32_t e, uint32_t col,
     uint32_t G, uint32_t K, const uint32_t (&hd)[NSTR]) {
-  const float *p[NE];
+  const T *p[NE];
   const float *wrow[NE];
 #pragma unroll
   for (int k = 0; k < NE; ++k) {
@@ -819,20 +825,20 @@ __device__ __forceinline__ void heads_edges_strided(
 #pragma unroll
     for (int j = 0; j < NSTR; ++j)
       if (col + j * G < g.f)
-        acc[j] = fmaf(wrow[k][hd[j]], p[k][j * G], acc[j]);
+        acc[j] = fmaf(wrow[k][hd[j]], to_f32(p[k][j * G]), acc[j]);
 }
 
-template <int ELEM>
+template <int ELEM, typename T = float>
 __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm_heads(
     const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
     const uint32_t *__restrict__ nbr, const float *__restrict__ ew,
-    const float *__restrict__ in, float *__restrict__ out, uint32_t nbr_start,
+    const T *__restrict__ in, float *__restrict__ out, uint32_t nbr_start,
     uint32_t f, uint32_t G, uint32_t n_slabs, uint32_t K, uint32_t C) {
   constexpr int NSTR = (ELEM == 1) ? 4 : 1;
   const uint32_t n_items = *n_items_p;
   const uint32_t glane = threadIdx.x & (G - 1);
   const uint32_t tilef = G * ELEM * NSTR;
-  const GatherSrc<float> g{nbr, ew, in, nbr_start, f, f};
+  const GatherSrc<T> g{nbr, ew, in, nbr_start, f, f};
   const GatherPlan pl{NTS_SCHED_ITEM, tilef, n_slabs, 1u};
   const XcdClass xc;
   const uint64_t total = (uint64_t)n_items * n_slabs;
@@ -862,7 +868,8 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm_heads(
       for (; e + 4 <= e_end; e += 4)
         heads_edges_vec<ELEM, 4>(acc, g, e, col, K, head);
       for (; e < e_end; ++e) heads_edges_vec<ELEM, 1>(acc, g, e, col, K, head);
-      store_acc<ELEM>(o, acc, ELEM, im.shared);
+      store_acc<ELEM, common_ov(ELEM, (int)sizeof(T))>(o, acc, ELEM,
+                                                       im.shared);
     }
   }
 }
@@ -1939,9 +1946,9 @@ __global__ void k_edge_dot(const uint4 *__restrict__ items,
 /* out[e*K + k] = sum over head k's C columns j of term(own[d, j], nbr[src, j]).
  * The term is a rule struct: the per-head dot, or the GATv2 score, which
  * brings a third operand per column. */
-template <int R>
-__device__ __forceinline__ void load_cols(const float *p, float (&x)[R]) {
-  if constexpr (R == 1) x[0] = p[0];
+template <int R, typename T>
+__device__ __forceinline__ void load_cols(const T *p, float (&x)[R]) {
+  if constexpr (R == 1) x[0] = to_f32(p[0]);
   else load_lane<R>(p, x);
 }
 /* a * b */
@@ -1979,18 +1986,25 @@ struct Gatv2Term {
  * and the segment's first lane writes.  Lanes past the row's end and edge
  * slots past the item's end load a clamped (valid) address and are never
  * written: segments lie inside one head and one lane group, so what such
- * lanes hold never meets a live sum. */
+ * lanes hold never meets a live sum.
+ * TD / TS = element types of dst_rows / src_rows (float, or uint16_t for
+ * bfloat16 rows, widened exactly on load): a lane's R columns are then one
+ * R*2-byte load (R = 1: a 2-byte load, any 2-byte alignment).  R follows C
+ * and, per pointer, R * element size bytes of alignment; at the same R a
+ * lane sums the same columns in the same order as the fp32 instantiation
+ * and the butterfly is the same, so the result is bit-identical to the fp32
+ * kernel's on the widened rows. */
 __device__ __forceinline__ float seg_sum(float x, uint32_t L) {
   for (uint32_t w = L >> 1; w >= 1; w >>= 1) x += __shfl_xor(x, w, 64);
   return x;
 }
 
-template <int R, class Term>
+template <int R, class Term, typename TD = float, typename TS = float>
 __global__ void k_edge_pair_seg(const uint4 *__restrict__ items,
                                 const uint32_t *__restrict__ n_items_p,
                                 float *__restrict__ out,
-                                const float *__restrict__ dst_rows,
-                                const float *__restrict__ src_rows,
+                                const TD *__restrict__ dst_rows,
+                                const TS *__restrict__ src_rows,
                                 const uint32_t *__restrict__ row_indices,
                                 uint32_t src_start, uint32_t f, uint32_t K,
                                 uint32_t C, uint32_t G, const Term term) {
@@ -2038,12 +2052,12 @@ __global__ void k_edge_pair_seg(const uint4 *__restrict__ items,
 }
 
 /* general form, any K and C */
-template <class Term>
+template <class Term, typename TD = float, typename TS = float>
 __global__ void k_edge_pair(const uint4 *__restrict__ items,
                             const uint32_t *__restrict__ n_items_p,
                             float *__restrict__ out,
-                            const float *__restrict__ dst_rows,
-                            const float *__restrict__ src_rows,
+                            const TD *__restrict__ dst_rows,
+                            const TS *__restrict__ src_rows,
                             const uint32_t *__restrict__ row_indices,
                             uint32_t src_start, uint32_t f, uint32_t K,
                             uint32_t C, const Term term) {
@@ -2053,16 +2067,16 @@ __global__ void k_edge_pair(const uint4 *__restrict__ items,
   for (uint32_t it = w.wave; it < n_items; it += w.n_waves) {
     const Item im = load_item(items, it);
     const uint32_t e0 = im.e0, cnt = im.cnt;
-    const float *a = dst_rows + (uint64_t)im.v * f;
+    const TD *a = dst_rows + (uint64_t)im.v * f;
     for (uint32_t k = 0; k < cnt; ++k) {
       const uint32_t e = e0 + k;
-      const float *b = src_rows + (uint64_t)(row_indices[e] - src_start) * f;
+      const TS *b = src_rows + (uint64_t)(row_indices[e] - src_start) * f;
       for (uint32_t h = 0; h < K; ++h) {
         float sum = 0.f;
         for (uint32_t j = h * C + lane; j < (h + 1) * C; j += 64) {
           float x[1];
           term.template load<1>(x, j);
-          sum = term(x[0], a[j], b[j], sum);
+          sum = term(x[0], to_f32(a[j]), to_f32(b[j]), sum);
         }
         sum = wave_sum(sum);
         if (lane == 0) out[(uint64_t)e * K + h] = sum;
@@ -2081,20 +2095,23 @@ __global__ void k_edge_pair(const uint4 *__restrict__ items,
  *   dAtt[j] += gs * lrelu (t)      (WITH_ATT)
  * The column slab is the outer loop and the group's items the inner one, so
  * dAtt is R registers at any f; after the items the workgroup's 256/G groups
- * meet in LDS and ONE atomicAdd per (workgroup, column) reaches grad_att. */
-template <int R, int NE>
+ * meet in LDS and ONE atomicAdd per (workgroup, column) reaches grad_att.
+ * T = element type of own_rows and nbr_rows (float, or uint16_t for bfloat16
+ * rows, widened exactly on load; R columns are one R*2-byte load, R = 1 a
+ * 2-byte load); grad_score, att and both outputs are fp32.  At the same R a
+ * lane runs the fp32 instantiation's chains on the widened values. */
+template <int R, int NE, typename T>
 __device__ __forceinline__ void gatv2_bwd_edges(
     float (&down)[R], float (&datt)[R], const float (&ov)[R],
-    const float *__restrict__ nbr_rows, const uint32_t *__restrict__ nbr,
+    const T *__restrict__ nbr_rows, const uint32_t *__restrict__ nbr,
     const float *__restrict__ gscore, uint32_t nbr_start, uint32_t f,
     uint32_t K, uint32_t e, uint32_t col, uint32_t head, float slope,
     bool with_att) {
   float x[NE][R], gs[NE];
 #pragma unroll
   for (int k = 0; k < NE; ++k) {
-    const float *p = nbr_rows + (uint64_t)(nbr[e + k] - nbr_start) * f + col;
-    if constexpr (R == 1) x[k][0] = p[0];
-    else load_lane<R>(p, x[k]);
+    load_cols<R>(nbr_rows + (uint64_t)(nbr[e + k] - nbr_start) * f + col,
+                 x[k]);
     gs[k] = gscore[(uint64_t)(e + k) * K + head];
   }
 #pragma unroll
@@ -2107,12 +2124,12 @@ __device__ __forceinline__ void gatv2_bwd_edges(
     }
 }
 
-template <int R, bool WITH_ATT>
+template <int R, bool WITH_ATT, typename T = float>
 __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_backward(
     const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
     float *__restrict__ grad_own, float *__restrict__ grad_att,
-    const float *__restrict__ gscore, const float *__restrict__ own_rows,
-    const float *__restrict__ nbr_rows, const float *__restrict__ att,
+    const float *__restrict__ gscore, const T *__restrict__ own_rows,
+    const T *__restrict__ nbr_rows, const float *__restrict__ att,
     float slope, const uint32_t *__restrict__ nbr, uint32_t nbr_start,
     uint32_t f, uint32_t K, uint32_t C, uint32_t G) {
   __shared__ float part[WITH_ATT ? NTS_BLOCK * R : 1];
@@ -2134,8 +2151,7 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_backward(
         const uint32_t e_end = im.e0 + im.cnt;
         uint32_t e = im.e0;
         float ov[R], down[R] = {};
-        if constexpr (R == 1) ov[0] = own_rows[(uint64_t)im.v * f + col];
-        else load_lane<R>(own_rows + (uint64_t)im.v * f + col, ov);
+        load_cols<R>(own_rows + (uint64_t)im.v * f + col, ov);
         for (; e + 4 <= e_end; e += 4)
           gatv2_bwd_edges<R, 4>(down, datt, ov, nbr_rows, nbr, gscore,
                                 nbr_start, f, K, e, col, head, slope, WITH_ATT);
@@ -2759,12 +2775,18 @@ void check_heads(const char *entry, uint32_t f, uint32_t heads) {
 
 /* Launch decision of a heads gather: always the native launch (one tile per
  * slab, item-major), lanes narrowed until they divide the columns per head.
- * Pure, like plan_gather; at K = 1 it is plan_gather's native launch. */
+ * Pure, like plan_gather; at K = 1 it is plan_gather's native launch.
+ * elem_bytes = 2 (bf16 rows): elements per lane are the widest of 8 / 4 / 2
+ * that divides C as well as f and whose load (16 / 8 / 4 bytes) the common
+ * alignment of `in` and `out` permits — `out` is then accessed in vectors of
+ * half as many floats, the rule of the scalar bf16 gather — else 4 strided
+ * single elements; the lane group is the smallest power of two in [16, 64]
+ * covering f, the grid bound_items * slabs * lanes under the block cap. */
 GatherLaunch plan_gather_heads(uint32_t f, uint32_t heads, uintptr_t alignment,
                                uint32_t batch, uint32_t edges,
-                               const GatherEnv &env) {
-  const GatherGeom geo =
-      gather_geometry(f, alignment, sizeof(float), f / heads);
+                               const GatherEnv &env,
+                               uint32_t elem_bytes = sizeof(float)) {
+  const GatherGeom geo = gather_geometry(f, alignment, elem_bytes, f / heads);
   const uint32_t slabf = geo.G * geo.elem * geo.nstr;
   const uint32_t n_slabs = (f + slabf - 1) / slabf;
   const uint64_t bound_items = (uint64_t)batch + edges / env.split + 1;
@@ -2774,7 +2796,8 @@ GatherLaunch plan_gather_heads(uint32_t f, uint32_t heads, uintptr_t alignment,
       GatherPlan{NTS_SCHED_ITEM, slabf, n_slabs, 1u}};
 }
 
-void launch_gather_heads(nts_stream *s, const char *entry, const float *in,
+template <typename T>
+void launch_gather_heads(nts_stream *s, const char *entry, const T *in,
                          float *out, const float *ew, const uint32_t *nbr,
                          const uint32_t *offset, uint32_t nbr_start,
                          uint32_t batch, uint32_t edges, uint32_t f,
@@ -2788,14 +2811,19 @@ void launch_gather_heads(nts_stream *s, const char *entry, const float *in,
   if (!batch || !edges) return;
   ItemsBuf &ib = get_items(s, offset, batch, edges);
   const GatherLaunch L = plan_gather_heads(
-      f, heads, (uintptr_t)in | (uintptr_t)out, batch, edges, gather_env());
+      f, heads, (uintptr_t)in | (uintptr_t)out, batch, edges, gather_env(),
+      sizeof(T));
   s->sched_last = (int)L.pl.sched;
   s->window_last = (int)L.pl.wf;
   s->stripe_last = s->stripe_run_last = 0;
+  /* indexed by log2(elements per lane); the last entry is the widest lane:
+   * 4 dwords, or 8 bf16 */
+  constexpr int WIDEST = 16 / (int)sizeof(T);
+  static const decltype(&k_gather_spmm_heads<1, T>) kernels[4] = {
+      k_gather_spmm_heads<1, T>, k_gather_spmm_heads<2, T>,
+      k_gather_spmm_heads<4, T>, k_gather_spmm_heads<WIDEST, T>};
   Tic t(s, tag);
-  hipLaunchKernelGGL(L.elem == 4   ? k_gather_spmm_heads<4>
-                     : L.elem == 2 ? k_gather_spmm_heads<2>
-                                   : k_gather_spmm_heads<1>,
+  hipLaunchKernelGGL(kernels[__builtin_ctz((unsigned)L.elem)],
                      dim3(L.grid), dim3(NTS_BLOCK), 0, s->stream, ib.items,
                      ib.counter, nbr, ew, in, out, nbr_start, f, L.G,
                      L.pl.n_windows, heads, f / heads);
@@ -3063,18 +3091,65 @@ void nts_gather_by_src_from_dst_heads(
                       dst_end > dst_start ? dst_end - dst_start : 0);
 }
 
+void nts_gather_by_dst_from_src_heads_bf16(
+    nts_stream *s, const uint16_t *input, float *output,
+    const float *weight_forward, const nts_vid *row_indices,
+    const nts_vid *column_offset, nts_vid src_start, nts_vid src_end,
+    nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid batch_size,
+    nts_vid feature_size, nts_vid heads) {
+  (void)dst_start; (void)dst_end;
+  launch_gather_heads(s, "nts_gather_by_dst_from_src_heads_bf16", input,
+                      output, weight_forward, row_indices, column_offset,
+                      src_start, batch_size, edges, feature_size, heads,
+                      NTS_KTAG_FWD,
+                      src_end > src_start ? src_end - src_start : 0);
+}
+
+void nts_gather_by_src_from_dst_heads_bf16(
+    nts_stream *s, const uint16_t *input, float *output,
+    const float *weight_backward, const nts_vid *row_offset,
+    const nts_vid *column_indices, nts_vid src_start, nts_vid src_end,
+    nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid batch_size,
+    nts_vid feature_size, nts_vid heads) {
+  (void)src_start; (void)src_end;
+  launch_gather_heads(s, "nts_gather_by_src_from_dst_heads_bf16", input,
+                      output, weight_backward, column_indices, row_offset,
+                      dst_start, batch_size, edges, feature_size, heads,
+                      NTS_KTAG_BWD,
+                      dst_end > dst_start ? dst_end - dst_start : 0);
+}
+
+static void report_plan_heads(const char *entry, uint32_t elem_bytes,
+                              nts_vid feature_size, nts_vid heads,
+                              unsigned alignment_bytes, nts_vid batch_size,
+                              nts_vid edges, int *lane_group,
+                              int *vector_width, int *grid) {
+  check_heads(entry, feature_size, heads);
+  GatherLaunch L{};
+  if (batch_size && edges) /* else nothing is launched */
+    L = plan_gather_heads(feature_size, heads, alignment_bytes, batch_size,
+                          edges, gather_env(), elem_bytes);
+  if (lane_group) *lane_group = (int)L.G;
+  if (vector_width) *vector_width = L.elem;
+  if (grid) *grid = (int)L.grid;
+}
+
 void nts_gather_plan_heads(nts_vid feature_size, nts_vid heads,
                            unsigned alignment_bytes, nts_vid batch_size,
                            nts_vid edges, int *lane_group, int *vector_width,
                            int *grid) {
-  check_heads("nts_gather_plan_heads", feature_size, heads);
-  GatherLaunch L{};
-  if (batch_size && edges) /* else nothing is launched */
-    L = plan_gather_heads(feature_size, heads, alignment_bytes, batch_size,
-                          edges, gather_env());
-  if (lane_group) *lane_group = (int)L.G;
-  if (vector_width) *vector_width = L.elem;
-  if (grid) *grid = (int)L.grid;
+  report_plan_heads("nts_gather_plan_heads", sizeof(float), feature_size,
+                    heads, alignment_bytes, batch_size, edges, lane_group,
+                    vector_width, grid);
+}
+
+void nts_gather_plan_heads_bf16(nts_vid feature_size, nts_vid heads,
+                                unsigned alignment_bytes, nts_vid batch_size,
+                                nts_vid edges, int *lane_group,
+                                int *vector_width, int *grid) {
+  report_plan_heads("nts_gather_plan_heads_bf16", sizeof(uint16_t),
+                    feature_size, heads, alignment_bytes, batch_size, edges,
+                    lane_group, vector_width, grid);
 }
 
 void nts_reduce_by_dst_from_src(nts_stream *s, int op, const float *input,
@@ -3876,31 +3951,48 @@ void nts_weight_sum_heads(nts_stream *s, float *out, const float *weights,
 }
 
 /* The row-pair passes' lane geometry.  R, columns per lane: the widest of
- * 4 / 2 / 1 dwords that divides C and that every pointer's alignment
- * permits; L = C / R lanes per head.  seg: L a power of two <= 64.  G, the
- * lane group of one row: f / R lanes rounded up to a power of two, <= 64. */
+ * 4 / 2 / 1 that divides C and that every pointer permits, each by its own
+ * element size: R * 4 bytes of alignment for an fp32 operand, R * 2 for a
+ * bf16 one (R = 1 runs at any element alignment).  L = C / R lanes per head.
+ * seg: L a power of two <= 64.  G, the lane group of one row: f / R lanes
+ * rounded up to a power of two, <= 64. */
 extern "C++" {
-template <class Term>
+/* fp32_alignment / bf16_alignment: the OR of the pointers of each kind */
+static uint32_t pair_cols(uint32_t C, uintptr_t fp32_alignment,
+                          uintptr_t bf16_alignment) {
+  for (uint32_t R = 4; R > 1; R /= 2)
+    if (C % R == 0 && fp32_alignment % (R * sizeof(float)) == 0 &&
+        bf16_alignment % (R * sizeof(uint16_t)) == 0)
+      return R;
+  return 1;
+}
+template <typename T>
+static uintptr_t align_as(const T *p, size_t elem_bytes) {
+  return sizeof(T) == elem_bytes ? (uintptr_t)p : 0;
+}
+/* fp32_extra: the term's own fp32 operand (att), 0 if none */
+template <class Term, typename TD, typename TS>
 static void launch_edge_pair(nts_stream *s, const EdgeItems &p, float *out,
-                             const float *dst_rows, const float *src_rows,
+                             const TD *dst_rows, const TS *src_rows,
                              const nts_vid *row_indices, nts_vid src_start,
-                             nts_vid f, nts_vid K, uintptr_t alignment,
+                             nts_vid f, nts_vid K, uintptr_t fp32_extra,
                              const Term &term) {
   const uint32_t C = f / K;
-  const uint32_t R =
-      (uint32_t)gather_geometry(C, alignment, sizeof(float)).elem;
+  const uint32_t R = pair_cols(
+      C, fp32_extra | align_as(dst_rows, 4) | align_as(src_rows, 4),
+      align_as(dst_rows, 2) | align_as(src_rows, 2));
   const uint32_t L = C / R;
   if (!s->heads_general && (L & (L - 1)) == 0 && L <= 64) {
     uint32_t G = 64;
     while (G / 2 >= f / R) G /= 2;
-    hipLaunchKernelGGL((R == 4   ? k_edge_pair_seg<4, Term>
-                        : R == 2 ? k_edge_pair_seg<2, Term>
-                                 : k_edge_pair_seg<1, Term>),
+    hipLaunchKernelGGL((R == 4   ? k_edge_pair_seg<4, Term, TD, TS>
+                        : R == 2 ? k_edge_pair_seg<2, Term, TD, TS>
+                                 : k_edge_pair_seg<1, Term, TD, TS>),
                        dim3(p.grid), dim3(NTS_BLOCK), 0, s->stream,
                        p.ib->items, p.ib->counter, out, dst_rows, src_rows,
                        row_indices, src_start, f, K, C, G, term);
   } else {
-    hipLaunchKernelGGL(k_edge_pair<Term>, dim3(p.grid), dim3(NTS_BLOCK), 0,
+    hipLaunchKernelGGL((k_edge_pair<Term, TD, TS>), dim3(p.grid), dim3(NTS_BLOCK), 0,
                        s->stream, p.ib->items, p.ib->counter, out, dst_rows,
                        src_rows, row_indices, src_start, f, K, C, term);
   }
@@ -3922,9 +4014,24 @@ void nts_edge_dot_heads(nts_stream *s, float *out, const float *dst_rows,
                        row_indices, src_start, feature_size);
   else
     launch_edge_pair(s, p, out, dst_rows, src_rows, row_indices, src_start,
-                     feature_size, heads,
-                     (uintptr_t)dst_rows | (uintptr_t)src_rows, DotTerm{});
+                     feature_size, heads, 0, DotTerm{});
   dbg_sync(s, "k_edge_dot_heads");
+}
+
+void nts_edge_dot_heads_bf16(nts_stream *s, float *out, const float *dst_rows,
+                             const uint16_t *src_rows,
+                             const nts_vid *row_indices,
+                             const nts_vid *column_offset, nts_vid src_start,
+                             nts_vid batch_size, nts_vid edges,
+                             nts_vid feature_size, nts_vid heads) {
+  check_heads("nts_edge_dot_heads_bf16", feature_size, heads);
+  const EdgeItems p = edge_items_known(s, column_offset, batch_size, edges);
+  if (!p.ib) return;
+  Tic t(s, NTS_KTAG_EDGE);
+  /* heads == 1 too: the row-pair forms at K = 1 (k_edge_dot is fp32 only) */
+  launch_edge_pair(s, p, out, dst_rows, src_rows, row_indices, src_start,
+                   feature_size, heads, 0, DotTerm{});
+  dbg_sync(s, "k_edge_dot_heads_bf16");
 }
 
 void nts_edge_gatv2_score(nts_stream *s, float *score, const float *dst_rows,
@@ -3938,11 +4045,67 @@ void nts_edge_gatv2_score(nts_stream *s, float *score, const float *dst_rows,
   if (!p.ib) return;
   Tic t(s, NTS_KTAG_EDGE);
   launch_edge_pair(s, p, score, dst_rows, src_rows, row_indices, src_start,
-                   feature_size, heads,
-                   (uintptr_t)dst_rows | (uintptr_t)src_rows | (uintptr_t)att,
-                   Gatv2Term{att, slope});
+                   feature_size, heads, (uintptr_t)att, Gatv2Term{att, slope});
   dbg_sync(s, "k_gatv2_score");
 }
+
+void nts_edge_gatv2_score_bf16(nts_stream *s, float *score,
+                               const uint16_t *dst_rows,
+                               const uint16_t *src_rows, const float *att,
+                               float slope, const nts_vid *row_indices,
+                               const nts_vid *column_offset, nts_vid src_start,
+                               nts_vid batch_size, nts_vid edges,
+                               nts_vid feature_size, nts_vid heads) {
+  check_heads("nts_edge_gatv2_score_bf16", feature_size, heads);
+  const EdgeItems p = edge_items_known(s, column_offset, batch_size, edges);
+  if (!p.ib) return;
+  Tic t(s, NTS_KTAG_EDGE);
+  launch_edge_pair(s, p, score, dst_rows, src_rows, row_indices, src_start,
+                   feature_size, heads, (uintptr_t)att, Gatv2Term{att, slope});
+  dbg_sync(s, "k_gatv2_score_bf16");
+}
+
+extern "C++" {
+template <typename T>
+static void launch_gatv2_backward(nts_stream *s, const char *entry,
+                                  float *grad_own, float *grad_att,
+                                  const float *grad_score, const T *own_rows,
+                                  const T *nbr_rows, const float *att,
+                                  float slope, const nts_vid *offset,
+                                  const nts_vid *nbr_indices,
+                                  nts_vid nbr_start, nts_vid batch_size,
+                                  nts_vid edges, nts_vid feature_size,
+                                  nts_vid heads) {
+  check_heads(entry, feature_size, heads);
+  const EdgeItems p = edge_items_known(s, offset, batch_size, edges);
+  if (!p.ib) return;
+  const uint32_t f = feature_size, C = f / heads;
+  /* columns per lane: 4 / 2 dividing C (a lane stays inside one head) where
+   * every row pointer, att and grad_own permit the vector access (each by
+   * its own element size, as pair_cols has it), else 1, which is also the
+   * general form nts_heads_dbg_general asks for */
+  uint32_t R = 1;
+  if (!s->heads_general)
+    R = pair_cols(C,
+                  (uintptr_t)grad_own | (uintptr_t)att |
+                      align_as(own_rows, 4) | align_as(nbr_rows, 4),
+                  align_as(own_rows, 2) | align_as(nbr_rows, 2));
+  uint32_t G = 64;
+  while (G / 2 >= f / R && G > 16) G /= 2;
+  const uint64_t bound_items = (uint64_t)batch_size + edges / NTS_SPLIT + 1;
+  const uint32_t grid = grid_for(bound_items * G);
+  Tic t(s, NTS_KTAG_EDGE);
+#define NTS_K(RR)                                                             \
+  (grad_att ? k_gatv2_backward<RR, true, T> : k_gatv2_backward<RR, false, T>)
+  hipLaunchKernelGGL(R == 4 ? NTS_K(4) : R == 2 ? NTS_K(2) : NTS_K(1),
+                     dim3(grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                     p.ib->counter, grad_own, grad_att, grad_score, own_rows,
+                     nbr_rows, att, slope, nbr_indices, nbr_start, f, heads, C,
+                     G);
+#undef NTS_K
+  dbg_sync(s, "k_gatv2_backward");
+}
+}  // extern "C++"
 
 void nts_edge_gatv2_backward(nts_stream *s, float *grad_own, float *grad_att,
                              const float *grad_score, const float *own_rows,
@@ -3951,33 +4114,22 @@ void nts_edge_gatv2_backward(nts_stream *s, float *grad_own, float *grad_att,
                              const nts_vid *nbr_indices, nts_vid nbr_start,
                              nts_vid batch_size, nts_vid edges,
                              nts_vid feature_size, nts_vid heads) {
-  check_heads("nts_edge_gatv2_backward", feature_size, heads);
-  const EdgeItems p = edge_items_known(s, offset, batch_size, edges);
-  if (!p.ib) return;
-  const uint32_t f = feature_size, C = f / heads;
-  /* columns per lane: 4 / 2 dividing C (a lane stays inside one head) where
-   * every row pointer and att permit the vector access, else 1, which is
-   * also the general form nts_heads_dbg_general asks for */
-  uint32_t R = 1;
-  if (!s->heads_general)
-    R = (uint32_t)gather_geometry(
-            C, (uintptr_t)grad_own | (uintptr_t)own_rows |
-                   (uintptr_t)nbr_rows | (uintptr_t)att,
-            sizeof(float)).elem;
-  uint32_t G = 64;
-  while (G / 2 >= f / R && G > 16) G /= 2;
-  const uint64_t bound_items = (uint64_t)batch_size + edges / NTS_SPLIT + 1;
-  const uint32_t grid = grid_for(bound_items * G);
-  Tic t(s, NTS_KTAG_EDGE);
-#define NTS_K(RR)                                                             \
-  (grad_att ? k_gatv2_backward<RR, true> : k_gatv2_backward<RR, false>)
-  hipLaunchKernelGGL(R == 4 ? NTS_K(4) : R == 2 ? NTS_K(2) : NTS_K(1),
-                     dim3(grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-                     p.ib->counter, grad_own, grad_att, grad_score, own_rows,
-                     nbr_rows, att, slope, nbr_indices, nbr_start, f, heads, C,
-                     G);
-#undef NTS_K
-  dbg_sync(s, "k_gatv2_backward");
+  launch_gatv2_backward(s, "nts_edge_gatv2_backward", grad_own, grad_att,
+                        grad_score, own_rows, nbr_rows, att, slope, offset,
+                        nbr_indices, nbr_start, batch_size, edges,
+                        feature_size, heads);
+}
+
+void nts_edge_gatv2_backward_bf16(
+    nts_stream *s, float *grad_own, float *grad_att, const float *grad_score,
+    const uint16_t *own_rows, const uint16_t *nbr_rows, const float *att,
+    float slope, const nts_vid *offset, const nts_vid *nbr_indices,
+    nts_vid nbr_start, nts_vid batch_size, nts_vid edges, nts_vid feature_size,
+    nts_vid heads) {
+  launch_gatv2_backward(s, "nts_edge_gatv2_backward_bf16", grad_own, grad_att,
+                        grad_score, own_rows, nbr_rows, att, slope, offset,
+                        nbr_indices, nbr_start, batch_size, edges,
+                        feature_size, heads);
 }
 
 int nts_gather_by_src_from_dst_dot(nts_stream *s, const float *input,

@@ -41,6 +41,13 @@ keep mask a counter hash of (seed, CSC edge position, head) that the softmax's
 normalize pass applies while it writes and the softmax backward regenerates
 (nts_edge_attention_forward_drop, nts_edge_softmax_forward_drop,
 nts_edge_softmax_backward_drop); no mask tensor, no extra launch.
+
+bfloat16 feature rows: `h` of GATLayer and `x_l` / `x_r` of GATv2Layer may be
+torch.bfloat16.  The f-wide passes then read 2-byte rows through the *_bf16
+entries (widened exactly in registers); attention scalars, `att`, every
+[E, K] value, `y`, `grad_y` and every gradient the layers return stay
+float32, and `attend` / `attend_v2` cast the row gradients to the dtype of
+the input they belong to.
 """
 import numpy as np
 import torch
@@ -113,13 +120,18 @@ class _EdgeLayer:
         return (float(dropout), seed) if dropout > 0 else None
 
     @staticmethod
-    def _check_rows(name, t, rows, cols):
+    def _check_rows(name, t, rows, cols, bf16_ok=False):
         """The kernels take raw pointers: anything but a contiguous float32
-        device matrix of the expected shape raises before a launch."""
+        device matrix of the expected shape raises before a launch.
+        bf16_ok: a feature-row operand, which may be bfloat16 instead."""
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a torch.Tensor")
-        if t.dtype != torch.float32:
-            raise TypeError(f"{name} must be float32, got {t.dtype}")
+        if bf16_ok and t.dtype == torch.bfloat16:
+            pass
+        elif t.dtype != torch.float32:
+            raise TypeError(
+                f"{name} must be float32{' or bfloat16' if bf16_ok else ''}, "
+                f"got {t.dtype}")
         if not t.is_cuda:
             raise TypeError(f"{name} must be a device tensor")
         if tuple(t.shape) != (rows, cols):
@@ -151,6 +163,12 @@ class GATLayer(_EdgeLayer):
         """h: [V,f] projected features; s_src/s_dst: [V] attention scalars
         ([V, heads] for a multi-head layer).
 
+        h may be bfloat16 (s_src, s_dst, y and the backward's grad_y and
+        results stay float32): the forward gather and the backward's edge dot
+        then read bf16 rows.  A single-head layer given a bfloat16 h runs the
+        heads call chain ([V] scalars are taken as [V, 1]): the fused
+        gather-dot of the single-head backward is float32 only.
+
         dropout = p in [0, 1): attention dropout for training.  Each softmax
         coefficient alpha[e, k] is dropped with probability p (exactly
         round(p * 2^24) / 2^24) and the kept ones are scaled by 1 / (1 - p);
@@ -166,7 +184,10 @@ class GATLayer(_EdgeLayer):
         int in [0, 2**64); an invalid dropout or seed raises ValueError before
         any launch."""
         drop = self._drop(dropout, seed)
-        if self._heads_path:
+        # a single-head layer leaves the fused path for any h that is not
+        # float32: the heads chain takes bfloat16 and rejects the rest
+        if self._heads_path or (isinstance(h, torch.Tensor)
+                                and h.dtype != torch.float32):
             return self._forward_heads(h, s_src, s_dst, negative_slope, drop)
         ch, st, E = self.ch, self.stream, self.E
         dev = h.device
@@ -213,6 +234,12 @@ class GATLayer(_EdgeLayer):
         the two scalar gradients are [V, heads] for a multi-head layer."""
         if self._heads_path:
             return self._backward_heads(grad_y, saved, negative_slope)
+        if saved["h"].dtype == torch.bfloat16:
+            # the forward ran the heads chain: so does the backward, and the
+            # scalar gradients come back [V] as from the fused path
+            grad_h, g_src, g_dst = self._backward_heads(grad_y, saved,
+                                                        negative_slope)
+            return grad_h, g_src[:, 0], g_dst[:, 0]
         ch, st, E = self.ch, self.stream, self.E
         dev = grad_y.device
         f = grad_y.shape[1]
@@ -295,9 +322,14 @@ class GATLayer(_EdgeLayer):
         drop: None or the (p, seed) of forward's dropout."""
         ch, st, E, K = self.ch, self.stream, self.E, self.heads
         f = self._width("h", h)
-        self._check_rows("h", h, ch.src_n, f)
+        self._check_rows("h", h, ch.src_n, f, bf16_ok=True)
+        if not self._heads_path:
+            # a single-head layer sent here by a bfloat16 h: [V] as [V, 1]
+            s_src, s_dst = (t[:, None] if isinstance(t, torch.Tensor)
+                            and t.dim() == 1 else t for t in (s_src, s_dst))
         self._check_rows("s_src", s_src, self.v, K)
         self._check_rows("s_dst", s_dst, ch.dst_n, K)
+        bf16 = h.dtype == torch.bfloat16
         dev = h.device
         st.items_reuse(1)
         s = torch.empty(E, K, device=dev)
@@ -318,7 +350,8 @@ class GATLayer(_EdgeLayer):
             saved = {"h": h, "s": s, "s_csr": s_csr, "cached": s,
                      "m_sum": m_sum}
         y = torch.zeros(ch.dst_n, f, device=dev)
-        st.gather_by_dst_from_src_heads(
+        (st.gather_by_dst_from_src_heads_bf16 if bf16
+         else st.gather_by_dst_from_src_heads)(
             h.data_ptr(), y.data_ptr(), s.data_ptr(),
             ch.row_indices.data_ptr(), ch.column_offset.data_ptr(),
             ch.src_s, ch.src_e, ch.dst_s, ch.dst_e, E, ch.dst_n, f, K)
@@ -345,10 +378,11 @@ class GATLayer(_EdgeLayer):
             ch.row_offset.data_ptr(), ch.column_indices.data_ptr(),
             ch.src_s, ch.src_e, ch.dst_s, ch.dst_e, E, ch.src_n, f, K)
         gs = torch.empty(E, K, device=dev)
-        st.edge_dot_heads(gs.data_ptr(), grad_y.data_ptr(),
-                          saved["h"].data_ptr(), ch.row_indices.data_ptr(),
-                          ch.column_offset.data_ptr(), ch.src_s, ch.dst_n, E,
-                          f, K)
+        bf16 = saved["h"].dtype == torch.bfloat16
+        (st.edge_dot_heads_bf16 if bf16 else st.edge_dot_heads)(
+            gs.data_ptr(), grad_y.data_ptr(), saved["h"].data_ptr(),
+            ch.row_indices.data_ptr(), ch.column_offset.data_ptr(), ch.src_s,
+            ch.dst_n, E, f, K)
         ge = torch.empty(E, K, device=dev)
         ge_csr = torch.empty(E, K, device=dev)
         if dropped:
@@ -397,6 +431,8 @@ class _AttendFn(torch.autograd.Function):
     def backward(ctx, grad_y):
         grad_h, g_src, g_dst = ctx.layer.backward(grad_y.contiguous(),
                                                   ctx.saved, ctx.slope)
+        # fp32 out of the kernels; bf16 only if h itself was
+        grad_h = grad_h.to(ctx.saved["h"].dtype)
         return (grad_h, g_src.reshape(ctx.scalar_shapes[0]),
                 g_dst.reshape(ctx.scalar_shapes[1]), None, None, None, None)
 
@@ -421,6 +457,8 @@ def attend(h: torch.Tensor, s_src: torch.Tensor, s_dst: torch.Tensor,
     y = layer.forward(h, s_src, s_dst), differentiable in all three.  The
     projections stay in torch, e.g. for K heads of C columns
     s_src = (h.view(V, K, C) * a_src).sum(-1) with a_src of shape [K, C].
+    h may be bfloat16 (GATLayer.forward); h.grad then is bfloat16, the float32
+    gradient of the kernels rounded once, and s_src / s_dst stay float32.
     dropout, seed: attention dropout as for GATLayer.forward (pass 0.0 for
     evaluation); seed=None draws one from torch's default CPU generator."""
     return _AttendFn.apply(h, s_src, s_dst, layer, negative_slope, dropout,
@@ -456,8 +494,12 @@ class GATv2Layer(_EdgeLayer):
         if f < K or f % K != 0:
             raise ValueError(
                 f"x_l has {f} columns, not a multiple of heads={K}")
-        self._check_rows("x_l", x_l, ch.src_n, f)
-        self._check_rows("x_r", x_r, ch.dst_n, f)
+        self._check_rows("x_l", x_l, ch.src_n, f, bf16_ok=True)
+        self._check_rows("x_r", x_r, ch.dst_n, f, bf16_ok=True)
+        if x_l.dtype != x_r.dtype:
+            raise TypeError(
+                f"x_l and x_r must have one dtype, got {x_l.dtype} and "
+                f"{x_r.dtype}")
         self._check_rows("att", att, K, f // K)
         return f
 
@@ -465,7 +507,10 @@ class GATv2Layer(_EdgeLayer):
                 negative_slope: float = 0.2, dropout: float = 0.0,
                 seed: int = 0):
         """x_l: [src_n, K*C], x_r: [dst_n, K*C], att: [K, C].  Returns
-        (y[dst_n, K*C], saved).  dropout, seed: attention dropout exactly as
+        (y[dst_n, K*C], saved).  x_l and x_r may both be bfloat16 (att, y,
+        grad_y and the backward's results stay float32): the score, the
+        gather, the edge dot and both backward walks then read bf16 rows.
+        dropout, seed: attention dropout exactly as
         for GATLayer.forward — `saved` then carries alpha (the cache), w and
         w_csr (the dropped gather weights), p and seed, 4*E*K more bytes
         than without; dropout == 0.0 makes today's calls."""
@@ -473,9 +518,10 @@ class GATv2Layer(_EdgeLayer):
         ch, st, E, K = self.ch, self.stream, self.E, self.heads
         f = self._check_inputs(x_l, x_r, att)
         dev = x_l.device
+        bf16 = x_l.dtype == torch.bfloat16
         st.items_reuse(1)
         score = torch.empty(E, K, device=dev)
-        st.edge_gatv2_score(
+        (st.edge_gatv2_score_bf16 if bf16 else st.edge_gatv2_score)(
             score.data_ptr(), x_r.data_ptr(), x_l.data_ptr(), att.data_ptr(),
             negative_slope, ch.row_indices.data_ptr(),
             ch.column_offset.data_ptr(), ch.src_s, ch.dst_n, E, f, K)
@@ -501,7 +547,8 @@ class GATv2Layer(_EdgeLayer):
                 alpha.data_ptr(), ch.column_offset.data_ptr(), ch.dst_n, K)
             saved["alpha_csr"] = alpha_csr
         y = torch.zeros(ch.dst_n, f, device=dev)
-        st.gather_by_dst_from_src_heads(
+        (st.gather_by_dst_from_src_heads_bf16 if bf16
+         else st.gather_by_dst_from_src_heads)(
             x_l.data_ptr(), y.data_ptr(), w.data_ptr(),
             ch.row_indices.data_ptr(), ch.column_offset.data_ptr(),
             ch.src_s, ch.src_e, ch.dst_s, ch.dst_e, E, ch.dst_n, f, K)
@@ -519,6 +566,8 @@ class GATv2Layer(_EdgeLayer):
             raise ValueError("grad_y does not match the saved forward input")
         self._check_rows("grad_y", grad_y, ch.dst_n, f)
         dev = grad_y.device
+        bf16 = x_l.dtype == torch.bfloat16
+        walk = st.edge_gatv2_backward_bf16 if bf16 else st.edge_gatv2_backward
         st.items_reuse(1)
         # through alpha: the aggregation's own gradient to x_l, and the
         # per-head dot that is the gradient with respect to alpha
@@ -531,10 +580,10 @@ class GATv2Layer(_EdgeLayer):
             ch.column_indices.data_ptr(), ch.src_s, ch.src_e, ch.dst_s,
             ch.dst_e, E, ch.src_n, f, K)
         galpha = torch.empty(E, K, device=dev)
-        st.edge_dot_heads(galpha.data_ptr(), grad_y.data_ptr(),
-                          x_l.data_ptr(), ch.row_indices.data_ptr(),
-                          ch.column_offset.data_ptr(), ch.src_s, ch.dst_n, E,
-                          f, K)
+        (st.edge_dot_heads_bf16 if bf16 else st.edge_dot_heads)(
+            galpha.data_ptr(), grad_y.data_ptr(), x_l.data_ptr(),
+            ch.row_indices.data_ptr(), ch.column_offset.data_ptr(), ch.src_s,
+            ch.dst_n, E, f, K)
         # softmax backward without a leaky-relu mask (the GATv2 mask is
         # per column, inside the two walks below), dual-emitted
         gscore = torch.empty(E, K, device=dev)
@@ -555,13 +604,13 @@ class GATv2Layer(_EdgeLayer):
         # CSC walk: own = x_r, nbr = x_l -> grad_x_r and grad_att
         grad_xr = torch.zeros(ch.dst_n, f, device=dev)
         grad_att = torch.zeros(K, f // K, device=dev)
-        st.edge_gatv2_backward(
+        walk(
             grad_xr.data_ptr(), grad_att.data_ptr(), gscore.data_ptr(),
             x_r.data_ptr(), x_l.data_ptr(), att.data_ptr(), negative_slope,
             ch.column_offset.data_ptr(), ch.row_indices.data_ptr(), ch.src_s,
             ch.dst_n, E, f, K)
         # CSR walk: own = x_l, nbr = x_r, accumulated into grad_x_l
-        st.edge_gatv2_backward(
+        walk(
             grad_xl.data_ptr(), None, gscore_csr.data_ptr(), x_l.data_ptr(),
             x_r.data_ptr(), att.data_ptr(), negative_slope,
             ch.row_offset.data_ptr(), ch.column_indices.data_ptr(), ch.dst_s,
@@ -584,14 +633,18 @@ class _AttendV2Fn(torch.autograd.Function):
     def backward(ctx, grad_y):
         grad_xl, grad_xr, grad_att = ctx.layer.backward(
             grad_y.contiguous(), ctx.saved, ctx.slope)
-        return grad_xl, grad_xr, grad_att, None, None, None, None
+        # fp32 out of the kernels; bf16 only if the rows themselves were
+        dt = ctx.saved["x_l"].dtype
+        return (grad_xl.to(dt), grad_xr.to(dt), grad_att, None, None, None,
+                None)
 
 
 def attend_v2(x_l: torch.Tensor, x_r: torch.Tensor, att: torch.Tensor,
               layer: GATv2Layer, negative_slope: float = 0.2,
               dropout: float = 0.0, seed=None) -> torch.Tensor:
     """Autograd-aware GATv2 aggregation on `layer`'s graph, differentiable in
-    x_l [src_n, K*C], x_r [dst_n, K*C] and att [K, C] (all float32,
+    x_l [src_n, K*C], x_r [dst_n, K*C] and att [K, C] (att float32, x_l and
+    x_r both float32 or both bfloat16, their gradients in their own dtype;
     contiguous, on the device; anything else raises before a launch).  The
     projections stay in torch: x_l = x @ W_l, x_r = x @ W_r.  Weight sharing
     (x_l is x_r) needs no special case: autograd adds the two gradients.

@@ -129,6 +129,16 @@ def lib():
         [_vp] + [_vp] * 4 + [_c.c_float] + [_vp] * 2 + [_u32] * 5)
     l.nts_edge_gatv2_backward.argtypes = (
         [_vp] + [_vp] * 6 + [_c.c_float] + [_vp] * 2 + [_u32] * 5)
+    # bf16 feature rows of the attention passes
+    l.nts_gather_by_dst_from_src_heads_bf16.argtypes = (
+        l.nts_gather_by_dst_from_src_heads.argtypes)
+    l.nts_gather_by_src_from_dst_heads_bf16.argtypes = (
+        l.nts_gather_by_dst_from_src_heads.argtypes)
+    l.nts_gather_plan_heads_bf16.argtypes = l.nts_gather_plan_heads.argtypes
+    l.nts_edge_dot_heads_bf16.argtypes = l.nts_edge_dot_heads.argtypes
+    l.nts_edge_gatv2_score_bf16.argtypes = l.nts_edge_gatv2_score.argtypes
+    l.nts_edge_gatv2_backward_bf16.argtypes = (
+        l.nts_edge_gatv2_backward.argtypes)
     l.nts_edge_softmax_stable.argtypes = [_vp, _i32]
     l.nts_edge_softmax_stable_last.argtypes = [_vp, _vp]
     # attention dropout
@@ -252,15 +262,27 @@ def check_heads(f, heads):
             f"heads={heads!r} must be a positive divisor of the width {f!r}")
 
 
-def gather_plan_heads(f, heads, alignment, batch, edges):
-    """The launch decision of a heads gather (no device access): dict of
-    lane_group, vector_width (4, 2 or 1 dwords per lane) and grid."""
+def _plan_heads(entry, f, heads, alignment, batch, edges):
     check_heads(f, heads)
     names = ("lane_group", "vector_width", "grid")
     out = [_i32(0) for _ in names]
-    lib().nts_gather_plan_heads(f, heads, alignment, batch, edges,
-                                *[_c.byref(o) for o in out])
+    entry(f, heads, alignment, batch, edges, *[_c.byref(o) for o in out])
     return {n: o.value for n, o in zip(names, out)}
+
+
+def gather_plan_heads(f, heads, alignment, batch, edges):
+    """The launch decision of a heads gather (no device access): dict of
+    lane_group, vector_width (4, 2 or 1 dwords per lane) and grid."""
+    return _plan_heads(lib().nts_gather_plan_heads, f, heads, alignment,
+                       batch, edges)
+
+
+def gather_plan_heads_bf16(f, heads, alignment, batch, edges):
+    """gather_plan_heads for bfloat16 feature rows: vector_width is in
+    elements per lane (8, 4, 2 or 1), alignment the common alignment of the
+    input and the output in bytes."""
+    return _plan_heads(lib().nts_gather_plan_heads_bf16, f, heads, alignment,
+                       batch, edges)
 
 
 def check_dropout(p, seed):
@@ -647,6 +669,62 @@ class Stream:
             self.h, _vp(grad_own), _vp(grad_att), _vp(grad_score),
             _vp(own_rows), _vp(nbr_rows), _vp(att), slope, _vp(offset),
             _vp(nbr_indices), nbr_start, batch, edges, f, heads)
+
+    # ---- bf16 feature rows of the attention passes: the operands named
+    # *_bf16 point at bfloat16 rows, everything else is float32 ----
+    def gather_by_dst_from_src_heads_bf16(self, x_bf16, y_ptr, w_ptr,
+                                          row_indices_ptr, column_offset_ptr,
+                                          src_s, src_e, dst_s, dst_e, edges,
+                                          batch, f, heads):
+        """gather_by_dst_from_src_heads over bfloat16 input rows."""
+        check_heads(f, heads)
+        self._lib.nts_gather_by_dst_from_src_heads_bf16(
+            self.h, _vp(x_bf16), _vp(y_ptr), _vp(w_ptr), _vp(row_indices_ptr),
+            _vp(column_offset_ptr), src_s, src_e, dst_s, dst_e, edges, batch,
+            f, heads)
+
+    def gather_by_src_from_dst_heads_bf16(self, g_bf16, y_ptr, w_ptr,
+                                          row_offset_ptr, column_indices_ptr,
+                                          src_s, src_e, dst_s, dst_e, edges,
+                                          batch, f, heads):
+        """gather_by_src_from_dst_heads over bfloat16 input rows."""
+        check_heads(f, heads)
+        self._lib.nts_gather_by_src_from_dst_heads_bf16(
+            self.h, _vp(g_bf16), _vp(y_ptr), _vp(w_ptr), _vp(row_offset_ptr),
+            _vp(column_indices_ptr), src_s, src_e, dst_s, dst_e, edges, batch,
+            f, heads)
+
+    def edge_dot_heads_bf16(self, out, dst_rows, src_rows_bf16, row_indices,
+                            column_offset, src_start, batch, edges, f, heads):
+        """edge_dot_heads with float32 dst_rows and bfloat16 src_rows;
+        heads == 1 runs the row-pair kernels with one head."""
+        check_heads(f, heads)
+        self._lib.nts_edge_dot_heads_bf16(
+            self.h, _vp(out), _vp(dst_rows), _vp(src_rows_bf16),
+            _vp(row_indices), _vp(column_offset), src_start, batch, edges, f,
+            heads)
+
+    def edge_gatv2_score_bf16(self, score, dst_rows_bf16, src_rows_bf16, att,
+                              slope, row_indices, column_offset, src_start,
+                              batch, edges, f, heads):
+        """edge_gatv2_score with both row operands bfloat16."""
+        check_heads(f, heads)
+        self._lib.nts_edge_gatv2_score_bf16(
+            self.h, _vp(score), _vp(dst_rows_bf16), _vp(src_rows_bf16),
+            _vp(att), slope, _vp(row_indices), _vp(column_offset), src_start,
+            batch, edges, f, heads)
+
+    def edge_gatv2_backward_bf16(self, grad_own, grad_att, grad_score,
+                                 own_rows_bf16, nbr_rows_bf16, att, slope,
+                                 offset, nbr_indices, nbr_start, batch, edges,
+                                 f, heads):
+        """edge_gatv2_backward with both row operands bfloat16 (the
+        gradients stay float32)."""
+        check_heads(f, heads)
+        self._lib.nts_edge_gatv2_backward_bf16(
+            self.h, _vp(grad_own), _vp(grad_att), _vp(grad_score),
+            _vp(own_rows_bf16), _vp(nbr_rows_bf16), _vp(att), slope,
+            _vp(offset), _vp(nbr_indices), nbr_start, batch, edges, f, heads)
 
     # ---- max / min aggregation; op is checked here, the library aborts on
     # an invalid value ----

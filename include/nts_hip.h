@@ -815,6 +815,56 @@ void nts_edge_softmax_backward_drop(nts_stream *s, float *msg_input_grad,
     const nts_vid *column_offset, nts_vid batch_size, nts_vid edges,
     nts_vid feature_size, float p, unsigned long long seed);
 
+/* ---- fused GAT inference forward (additive): no per-edge state ----
+ * The forward of nts_edge_attention_forward_heads followed by
+ * nts_gather_by_dst_from_src_heads[_bf16] for a caller that needs only the
+ * aggregated rows (evaluation): per edge e into destination d and head k
+ *   t = s_src_mirror[row(e)*K + k] + s_dst[d*K + k]
+ *       row(e) = mirror_index ? mirror_index[row_indices[e]] : row_indices[e]
+ *   a = lrelu(t, slope)
+ *   w = exp(a) / S[d, k]                default, S = sum_e' exp(a[e'])
+ *   w = exp(a - M[d, k]) / S[d, k]      under nts_edge_softmax_stable,
+ *                                       M = max a, S = sum exp(a - M)
+ *   output[d, c] += sum_e w[e, c / C] * input[row_indices[e]-src_start, c]
+ * in two passes over the work items of column_offset.  Pass 1 (NTS_KTAG_EDGE)
+ * reduces S, or the (M, S) pairs, into the softmax's stream-owned
+ * [batch_size, K] scratch and stores nothing per edge; when stable, the short
+ * split-sum pass over split destinations follows and recomputes exp(a - M)
+ * from the scalars.  Pass 2 (NTS_KTAG_FWD) is the heads gather with w
+ * computed in registers from the s_src value fetched next to the source row.
+ * Nothing sized by `edges` is allocated, read or written besides row_indices.
+ *   output keeps the gathers' += contract: rows without edges are untouched,
+ * the caller zeroes.  input is [src_end-src_start, feature_size] fp32 (or
+ * bf16 as raw uint16_t, widened exactly), K = heads, C = feature_size / heads,
+ * columns head-major; scalars and output are fp32.  mirror_index NULL means
+ * identity.  The softmax mode is the stream's (nts_edge_softmax_stable), with
+ * the default's NaNs and the stable mode's -inf handling, and the call is
+ * recorded for nts_edge_softmax_stable_last.  Invalid heads abort as for the
+ * heads gathers; heads == 1 runs the same kernels at K = 1.  batch_size == 0
+ * or edges == 0 launches nothing.  The edge count is the caller's: no
+ * device-to-host copy and no synchronize.  Lane geometry is the heads
+ * gather's for the same (feature_size, heads, alignment of input | output,
+ * element size): nts_gather_plan_heads[_bf16] reports it, and
+ * nts_heads_dbg_general picks pass 1's lane layout as for the attention
+ * forward.  The item cache and NTS_SPLIT apply as everywhere.
+ *   On a destination that is one work item, S (or M, S) is reduced in the
+ * order of the attention forward's pass 1, w is the expression its normalize
+ * pass evaluates (a true division), and each output element is one lane's
+ * fmaf chain in edge order: the result is bit-identical to the two-entry
+ * chain.  A split destination merges by fp32 atomics, as there. */
+void nts_gat_forward_fused(nts_stream *s, const float *input, float *output,
+    const float *s_src_mirror, const float *s_dst,
+    const nts_vid *row_indices, const nts_vid *mirror_index, float slope,
+    const nts_vid *column_offset, nts_vid src_start, nts_vid src_end,
+    nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid batch_size,
+    nts_vid feature_size, nts_vid heads);
+void nts_gat_forward_fused_bf16(nts_stream *s, const uint16_t *input,
+    float *output, const float *s_src_mirror, const float *s_dst,
+    const nts_vid *row_indices, const nts_vid *mirror_index, float slope,
+    const nts_vid *column_offset, nts_vid src_start, nts_vid src_end,
+    nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid batch_size,
+    nts_vid feature_size, nts_vid heads);
+
 /* Opt-in work-item reuse: with enable=1 the stream caches its two most
  * recent item decompositions keyed on (offset pointer, batch, edges) and
  * skips identical rebuilds.  ONLY safe while the caller keeps those

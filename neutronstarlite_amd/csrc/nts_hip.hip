@@ -1808,6 +1808,231 @@ __global__ void k_edge_reduce(const uint4 *__restrict__ items,
   }
 }
 
+/* ---- fused GAT inference forward: no per-edge state ---- */
+/* GAT's score is a function of two per-vertex scalars, so a forward that
+ * needs only y keeps nothing per edge.  Pass 1 is k_edge_reduce under the
+ * rules below — the training rules minus their per-edge stores — and leaves
+ * the per-(destination, head) sums, or (M, S) pairs, where the softmax leaves
+ * them; pass 2, k_gather_att_heads, recomputes each edge's weight in
+ * registers.  An unsplit destination's denominator is reduced in the order
+ * of the training pass 1, and a weight is the expression the normalize pass
+ * evaluates on the stash, so both have the training forward's bits. */
+
+/* EdgeScore without the m_sum stash */
+struct EdgeScoreOnly {
+  const float *__restrict__ s_src, *__restrict__ s_dst;
+  const uint32_t *__restrict__ row_indices, *__restrict__ mirror_index;
+  float slope;
+  float sd;
+  __device__ void column(uint64_t slot) { sd = s_dst[slot]; }
+  __device__ float operator()(uint32_t e, uint32_t K, uint32_t k,
+                              uint64_t) const {
+    const uint32_t src = row_indices[e];
+    const uint64_t row = mirror_index ? mirror_index[src] : src;
+    return lrelu(s_src[row * K + k] + sd, slope);
+  }
+};
+/* EdgeStashExp without the stash: the split-sum pass recomputes the
+ * activation from the scalars */
+struct EdgeScoreExp {
+  EdgeScoreOnly score;
+  const unsigned long long *pairs;
+  float M;
+  __device__ void column(uint64_t slot) {
+    score.column(slot);
+    M = ms_unkey((uint32_t)pairs[slot]);
+  }
+  __device__ float operator()(uint32_t e, uint32_t K, uint32_t k,
+                              uint64_t m) const {
+    const float a = score(e, K, k, m);
+    return __expf(a - M);
+  }
+};
+/* SumToSums<true> without the exp stash */
+struct ExpSumToSums {
+  float *__restrict__ sums;
+  using Acc = float;
+  __device__ static Acc empty() { return 0.f; }
+  __device__ static bool wants(const Item &) { return true; }
+  __device__ void add(Acc &part, float a, uint64_t, bool) const {
+    part += __expf(a);
+  }
+  __device__ void put(Acc part, uint32_t span, bool owner, uint64_t slot,
+                      bool) const {
+    part = heads_lane_sum(part, span);
+    if (owner) atomicAdd(&sums[slot], part);
+  }
+};
+/* MaxSumToPairs without the activation stash */
+struct MaxSumOnlyToPairs {
+  unsigned long long *__restrict__ pairs;
+  using Acc = MaxSum;
+  __device__ static Acc empty() { return MaxSum{-INFINITY, 0.f}; }
+  __device__ static bool wants(const Item &) { return true; }
+  __device__ void add(Acc &p, float a, uint64_t, bool shared) const {
+    ms_add(p, a, shared);
+  }
+  __device__ void put(const Acc &p, uint32_t span, bool owner, uint64_t slot,
+                      bool shared) const {
+    const float Mi = heads_lane_max(p.m, span);
+    const float Si = heads_lane_sum(ms_rescaled(p, Mi), span);
+    if (owner) ms_put(&pairs[slot], Mi, Si, shared);
+  }
+};
+
+/* what pass 2 reads in place of a weight array: the scalars and pass 1's
+ * per-(destination, head) slots (float sums, or packed pairs when STABLE) */
+struct AttSrc {
+  const float *__restrict__ s_src, *__restrict__ s_dst;
+  const uint32_t *__restrict__ mirror_index;
+  const void *__restrict__ slots;
+  float slope;
+};
+/* one (destination, head): loaded once per (item, lane) */
+struct AttDen { float sd, M, S; };
+template <bool STABLE>
+__device__ __forceinline__ AttDen att_den(const AttSrc &at, uint64_t slot) {
+  AttDen q;
+  q.sd = at.s_dst[slot];
+  if constexpr (STABLE) {
+    const MaxSum p =
+        ms_unpack(static_cast<const unsigned long long *>(at.slots)[slot]);
+    q.M = p.m;
+    q.S = p.s;
+  } else {
+    q.M = 0.f;
+    q.S = static_cast<const float *>(at.slots)[slot];
+  }
+  return q;
+}
+/* the weight of an edge whose source scalar is ss: the normalize pass's
+ * expression on the value pass 1 would have stashed.  A true division (a
+ * reciprocal taken once per item rounds differently), and no contraction of
+ * the activation's multiply into the subtraction: the stash was rounded. */
+template <bool STABLE>
+__device__ __forceinline__ float att_weight(float ss, const AttDen &q,
+                                            float slope) {
+#pragma clang fp contract(off)
+  const float t = ss + q.sd;
+  const float a = lrelu(t, slope);
+  if constexpr (STABLE) return __expf(a - q.M) / q.S;
+  else return __expf(a) / q.S;
+}
+/* MIRROR is a template parameter, not a test of the pointer in the edge loop:
+ * tested per edge it compiles to a branch and a full wait around every index
+ * load, and the four index loads of an unrolled step run one after the other
+ * (read in the ISA, as for k_gather_reduce's message form) */
+template <bool MIRROR>
+__device__ __forceinline__ const float *att_src_row(const AttSrc &at,
+                                                    uint32_t src, uint32_t K) {
+  const uint64_t row = MIRROR ? at.mirror_index[src] : src;
+  return at.s_src + row * K;
+}
+
+/* NE consecutive edges for a full vector lane: the NE source scalars are
+ * loaded with the NE rows' addresses, before the first row load is consumed */
+template <int ELEM, int NE, bool STABLE, bool MIRROR, typename T>
+__device__ __forceinline__ void att_edges_vec(float (&acc)[ELEM],
+                                              const GatherSrc<T> &g,
+                                              const AttSrc &at, uint32_t e,
+                                              uint32_t col, uint32_t K,
+                                              uint32_t head,
+                                              const AttDen &q) {
+  const T *p[NE];
+  float ss[NE], wv[NE];
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    const uint32_t src = g.nbr[e + k];
+    p[k] = g.in + (uint64_t)(src - g.nbr_start) * g.ld + col;
+    ss[k] = att_src_row<MIRROR>(at, src, K)[head];
+  }
+#pragma unroll
+  for (int k = 0; k < NE; ++k) wv[k] = att_weight<STABLE>(ss[k], q, at.slope);
+  fma_vec<ELEM, NE>(acc, p, wv);
+}
+/* strided twin: element j at column col + j*G, head hd[j] with its own
+ * (s_dst, M, S) in q[j], live while col + j*G < f */
+template <int NSTR, int NE, bool STABLE, bool MIRROR, typename T>
+__device__ __forceinline__ void att_edges_strided(
+    float (&acc)[NSTR], const GatherSrc<T> &g, const AttSrc &at, uint32_t e,
+    uint32_t col, uint32_t G, uint32_t K, const uint32_t (&hd)[NSTR],
+    const AttDen (&q)[NSTR]) {
+  const T *p[NE];
+  const float *srow[NE];
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    const uint32_t src = g.nbr[e + k];
+    p[k] = g.in + (uint64_t)(src - g.nbr_start) * g.ld + col;
+    srow[k] = att_src_row<MIRROR>(at, src, K);
+  }
+#pragma unroll
+  for (int k = 0; k < NE; ++k)
+#pragma unroll
+    for (int j = 0; j < NSTR; ++j)
+      if (col + j * G < g.f)
+        acc[j] = fmaf(att_weight<STABLE>(srow[k][hd[j]], q[j], at.slope),
+                      to_f32(p[k][j * G]), acc[j]);
+}
+
+/* Pass 2: k_gather_spmm_heads<ELEM, T> with the weight computed, not loaded.
+ * Same lane groups, tasks, 4-edge unroll, register accumulation and single
+ * store; runs at K = 1 as well (C = f).  MIRROR: at.mirror_index is set. */
+template <int ELEM, typename T, bool STABLE, bool MIRROR>
+__global__ __launch_bounds__(NTS_BLOCK) void k_gather_att_heads(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ nbr, const AttSrc at,
+    const T *__restrict__ in, float *__restrict__ out, uint32_t nbr_start,
+    uint32_t f, uint32_t G, uint32_t n_slabs, uint32_t K, uint32_t C) {
+  constexpr int NSTR = (ELEM == 1) ? 4 : 1;
+  const uint32_t n_items = *n_items_p;
+  const uint32_t glane = threadIdx.x & (G - 1);
+  const uint32_t tilef = G * ELEM * NSTR;
+  const GatherSrc<T> g{nbr, nullptr, in, nbr_start, f, f};
+  const GatherPlan pl{NTS_SCHED_ITEM, tilef, n_slabs, 1u};
+  const XcdClass xc;
+  const uint64_t total = (uint64_t)n_items * n_slabs;
+  const uint64_t stride = (gridDim.x * NTS_BLOCK) / G;
+  for (uint64_t t = (blockIdx.x * NTS_BLOCK + threadIdx.x) / G; t < total;
+       t += stride) {
+    const Task tk = decode_task<false>(pl, xc, t, n_items, f, tilef);
+    const uint32_t col = tk.fbase + glane * ELEM;
+    if (col >= f) continue;
+    const Item im = load_item(items, tk.it);
+    const uint32_t e_end = im.e0 + im.cnt;
+    uint32_t e = im.e0;
+    float acc[ELEM * NSTR] = {};
+    float *o = out + (uint64_t)im.v * f + col;
+    const uint64_t slot0 = (uint64_t)im.v * K;
+    if constexpr (ELEM == 1) {
+      uint32_t hd[NSTR];
+      AttDen q[NSTR];
+#pragma unroll
+      for (int j = 0; j < NSTR; ++j) {
+        hd[j] = (col + j * G < f) ? (col + j * G) / C : 0u;
+        q[j] = att_den<STABLE>(at, slot0 + hd[j]);
+      }
+      for (; e + 4 <= e_end; e += 4)
+        att_edges_strided<NSTR, 4, STABLE, MIRROR>(acc, g, at, e, col, G, K,
+                                                   hd, q);
+      for (; e < e_end; ++e)
+        att_edges_strided<NSTR, 1, STABLE, MIRROR>(acc, g, at, e, col, G, K,
+                                                   hd, q);
+      store_strided(o, acc, G, col, f, im.shared);
+    } else {
+      const uint32_t head = col / C;
+      const AttDen q = att_den<STABLE>(at, slot0 + head);
+      for (; e + 4 <= e_end; e += 4)
+        att_edges_vec<ELEM, 4, STABLE, MIRROR>(acc, g, at, e, col, K, head,
+                                               q);
+      for (; e < e_end; ++e)
+        att_edges_vec<ELEM, 1, STABLE, MIRROR>(acc, g, at, e, col, K, head,
+                                               q);
+      store_acc<ELEM, common_ov(ELEM, (int)sizeof(T))>(o, acc, ELEM,
+                                                       im.shared);
+    }
+  }
+}
+
 /* Normalize pass (pass 2 of the edge softmax):
  *   NORM_FWD     out = out / sum                 (out holds exp a)
  *   NORM_BWD     out = out - sum * cached        (out holds g * s)
@@ -3851,6 +4076,101 @@ void nts_edge_attention_forward_heads(
                     heads, batch_size, softmax_out, softmax_out_perm, perm_pos,
                     EdgeScore{m_sum_out, s_src_mirror, s_dst, row_indices,
                               mirror_index, slope, 0.f});
+}
+
+/* ---- fused inference forward (additive; see include/nts_hip.h) ---- */
+extern "C++" {
+template <typename T, bool STABLE, bool MIRROR>
+static void launch_gather_att(nts_stream *s, const EdgeItems &p,
+                              const GatherLaunch &L, const AttSrc &at,
+                              const T *in, float *out, const nts_vid *nbr,
+                              nts_vid nbr_start, nts_vid f, nts_vid K) {
+  /* indexed by log2(elements per lane); the last entry is the widest lane:
+   * 4 dwords, or 8 bf16 */
+  constexpr int WIDEST = 16 / (int)sizeof(T);
+  static const decltype(&k_gather_att_heads<1, T, STABLE, MIRROR>) kernels[4] =
+      {k_gather_att_heads<1, T, STABLE, MIRROR>,
+       k_gather_att_heads<2, T, STABLE, MIRROR>,
+       k_gather_att_heads<4, T, STABLE, MIRROR>,
+       k_gather_att_heads<WIDEST, T, STABLE, MIRROR>};
+  hipLaunchKernelGGL(kernels[__builtin_ctz((unsigned)L.elem)], dim3(L.grid),
+                     dim3(NTS_BLOCK), 0, s->stream, p.ib->items, p.ib->counter,
+                     nbr, at, in, out, nbr_start, f, L.G, L.pl.n_windows, K,
+                     f / K);
+}
+
+/* Pass 1 under NTS_KTAG_EDGE: the denominators, nothing per edge; pass 2
+ * under NTS_KTAG_FWD: the heads gather's launch with the weights computed in
+ * registers.  Both walk the one item decomposition of column_offset. */
+template <typename T>
+static void gat_forward_fused(nts_stream *s, const char *entry, const T *in,
+                              float *out, const EdgeScoreOnly &score,
+                              const nts_vid *offset, nts_vid nbr_start,
+                              nts_vid batch, nts_vid edges, nts_vid f,
+                              nts_vid K) {
+  check_heads(entry, f, K);
+  s->softmax_stable_last = s->softmax_stable;
+  const EdgeItems p = edge_items_known(s, offset, batch, edges);
+  if (!p.ib) return;
+  const SoftmaxScratch ws = softmax_scratch(s, (uint64_t)batch * K);
+  {
+    Tic t(s, NTS_KTAG_EDGE);
+    if (ws.pairs) {
+      launch_reduce(s, p, K, score, MaxSumOnlyToPairs{ws.pairs});
+      launch_reduce(s, p, K, EdgeScoreExp{score, ws.pairs, 0.f},
+                    SplitSumToPairs{ws.pairs});
+    } else {
+      launch_reduce(s, p, K, score, ExpSumToSums{ws.sums});
+    }
+    dbg_sync(s, "k_edge_reduce (fused forward)");
+  }
+  const GatherLaunch L = plan_gather_heads(
+      f, K, (uintptr_t)in | (uintptr_t)out, batch, edges, gather_env(),
+      sizeof(T));
+  s->sched_last = (int)L.pl.sched;
+  s->window_last = (int)L.pl.wf;
+  s->stripe_last = s->stripe_run_last = 0;
+  const AttSrc at{score.s_src, score.s_dst, score.mirror_index,
+                  ws.pairs ? (const void *)ws.pairs : (const void *)ws.sums,
+                  score.slope};
+  Tic t(s, NTS_KTAG_FWD);
+  static constexpr decltype(&launch_gather_att<T, false, false>) launch[2][2] =
+      {{launch_gather_att<T, false, false>, launch_gather_att<T, false, true>},
+       {launch_gather_att<T, true, false>, launch_gather_att<T, true, true>}};
+  launch[ws.pairs != nullptr][at.mirror_index != nullptr](
+      s, p, L, at, in, out, score.row_indices, nbr_start, f, K);
+  dbg_sync(s, "k_gather_att_heads");
+}
+}  // extern "C++"
+
+void nts_gat_forward_fused(nts_stream *s, const float *input, float *output,
+                           const float *s_src_mirror, const float *s_dst,
+                           const nts_vid *row_indices,
+                           const nts_vid *mirror_index, float slope,
+                           const nts_vid *column_offset, nts_vid src_start,
+                           nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
+                           nts_vid edges, nts_vid batch_size,
+                           nts_vid feature_size, nts_vid heads) {
+  (void)src_end; (void)dst_start; (void)dst_end;
+  gat_forward_fused(s, "nts_gat_forward_fused", input, output,
+                    EdgeScoreOnly{s_src_mirror, s_dst, row_indices,
+                                  mirror_index, slope, 0.f},
+                    column_offset, src_start, batch_size, edges, feature_size,
+                    heads);
+}
+
+void nts_gat_forward_fused_bf16(
+    nts_stream *s, const uint16_t *input, float *output,
+    const float *s_src_mirror, const float *s_dst, const nts_vid *row_indices,
+    const nts_vid *mirror_index, float slope, const nts_vid *column_offset,
+    nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
+    nts_vid edges, nts_vid batch_size, nts_vid feature_size, nts_vid heads) {
+  (void)src_end; (void)dst_start; (void)dst_end;
+  gat_forward_fused(s, "nts_gat_forward_fused_bf16", input, output,
+                    EdgeScoreOnly{s_src_mirror, s_dst, row_indices,
+                                  mirror_index, slope, 0.f},
+                    column_offset, src_start, batch_size, edges, feature_size,
+                    heads);
 }
 
 /* ---- attention dropout entries (additive; see include/nts_hip.h) ---- */

@@ -42,6 +42,13 @@ normalize pass applies while it writes and the softmax backward regenerates
 (nts_edge_attention_forward_drop, nts_edge_softmax_forward_drop,
 nts_edge_softmax_backward_drop); no mask tensor, no extra launch.
 
+Evaluation (GATLayer.infer, and `attend` under torch.no_grad() with
+dropout == 0): one fused entry (nts_gat_forward_fused[_bf16]) reduces the
+per-(destination, head) softmax denominators and aggregates with each edge's
+weight recomputed in registers from the two scalars; it returns y alone and
+allocates nothing of size E.  GATv2Layer has no such form (its score needs
+the rows), and there is no dropout in infer.
+
 bfloat16 feature rows: `h` of GATLayer and `x_l` / `x_r` of GATv2Layer may be
 torch.bfloat16.  The f-wide passes then read 2-byte rows through the *_bf16
 entries (widened exactly in registers); attention scalars, `att`, every
@@ -357,6 +364,39 @@ class GATLayer(_EdgeLayer):
             ch.src_s, ch.src_e, ch.dst_s, ch.dst_e, E, ch.dst_n, f, K)
         return y, saved
 
+    def infer(self, h: torch.Tensor, s_src: torch.Tensor,
+              s_dst: torch.Tensor, negative_slope: float = 0.2):
+        """The forward for evaluation: y of forward(h, s_src, s_dst) and
+        nothing else.  One fused entry (Stream.gat_forward_fused) reduces the
+        per-(destination, head) softmax denominators and then aggregates with
+        each edge's weight computed in registers, so no [E, K] tensor is
+        allocated, written or kept; there is no `saved` and no backward.
+
+        h: [V, K*C] float32 or bfloat16; s_src, s_dst: [V, K] float32 ([V] is
+        taken as [V, 1] on a single-head layer); y is float32.  Any heads and
+        either softmax mode of the layer; no dropout.  Inputs are checked as
+        for the heads forward and a bad one raises before any launch.  On a
+        destination of at most one work item y is bit-identical to forward's;
+        a split destination differs by the order of its fp32 atomics."""
+        ch, st, E, K = self.ch, self.stream, self.E, self.heads
+        f = self._width("h", h)
+        self._check_rows("h", h, ch.src_n, f, bf16_ok=True)
+        if K == 1:
+            s_src, s_dst = (t[:, None] if isinstance(t, torch.Tensor)
+                            and t.dim() == 1 else t for t in (s_src, s_dst))
+        self._check_rows("s_src", s_src, self.v, K)
+        self._check_rows("s_dst", s_dst, ch.dst_n, K)
+        st.items_reuse(1)
+        y = torch.zeros(ch.dst_n, f, device=h.device)
+        # mirror_index None: the layer's is the identity
+        (st.gat_forward_fused_bf16 if h.dtype == torch.bfloat16
+         else st.gat_forward_fused)(
+            h.data_ptr(), y.data_ptr(), s_src.data_ptr(), s_dst.data_ptr(),
+            ch.row_indices.data_ptr(), None, negative_slope,
+            ch.column_offset.data_ptr(), ch.src_s, ch.src_e, ch.dst_s,
+            ch.dst_e, E, ch.dst_n, f, K)
+        return y
+
     def _backward_heads(self, grad_y, saved, negative_slope):
         """Returns (grad_h[V, K*C], g_src[V, K], g_dst[V, K])."""
         ch, st, E, K = self.ch, self.stream, self.E, self.heads
@@ -460,7 +500,13 @@ def attend(h: torch.Tensor, s_src: torch.Tensor, s_dst: torch.Tensor,
     h may be bfloat16 (GATLayer.forward); h.grad then is bfloat16, the float32
     gradient of the kernels rounded once, and s_src / s_dst stay float32.
     dropout, seed: attention dropout as for GATLayer.forward (pass 0.0 for
-    evaluation); seed=None draws one from torch's default CPU generator."""
+    evaluation); seed=None draws one from torch's default CPU generator.
+    Under torch.no_grad() with dropout == 0 (evaluation) the call is
+    layer.infer: the same y, with no [E, K] tensor allocated or kept."""
+    if not torch.is_grad_enabled() and dropout == 0:
+        _draw_seed(dropout, seed)   # the same argument checks
+        return layer.infer(h.contiguous(), s_src.contiguous(),
+                           s_dst.contiguous(), negative_slope)
     return _AttendFn.apply(h, s_src, s_dst, layer, negative_slope, dropout,
                            _draw_seed(dropout, seed))
 

@@ -139,6 +139,10 @@ def lib():
     l.nts_edge_gatv2_score_bf16.argtypes = l.nts_edge_gatv2_score.argtypes
     l.nts_edge_gatv2_backward_bf16.argtypes = (
         l.nts_edge_gatv2_backward.argtypes)
+    # fused inference forward (no per-edge state)
+    l.nts_gat_forward_fused.argtypes = (
+        [_vp] + [_vp] * 6 + [_c.c_float] + [_vp] + [_u32] * 8)
+    l.nts_gat_forward_fused_bf16.argtypes = l.nts_gat_forward_fused.argtypes
     l.nts_edge_softmax_stable.argtypes = [_vp, _i32]
     l.nts_edge_softmax_stable_last.argtypes = [_vp, _vp]
     # attention dropout
@@ -725,6 +729,33 @@ class Stream:
             self.h, _vp(grad_own), _vp(grad_att), _vp(grad_score),
             _vp(own_rows_bf16), _vp(nbr_rows_bf16), _vp(att), slope,
             _vp(offset), _vp(nbr_indices), nbr_start, batch, edges, f, heads)
+
+    # ---- fused GAT inference forward: attention scores, softmax and
+    # aggregation with nothing kept per edge ----
+    def gat_forward_fused(self, x_ptr, y_ptr, s_src_mirror, s_dst,
+                          row_indices, mirror_index, slope, column_offset,
+                          src_s, src_e, dst_s, dst_e, edges, batch, f, heads):
+        """y[d, c] += sum over d's in-edges of softmax(leaky_relu(s_src[src]
+        + s_dst[d]))[e, c // C] * x[src, c]: edge_attention_forward_heads and
+        gather_by_dst_from_src_heads in two passes that allocate and write
+        nothing of size edges.  mirror_index None/0: s_src_mirror is indexed
+        by the global source id.  Honours edge_softmax_stable."""
+        check_heads(f, heads)
+        self._lib.nts_gat_forward_fused(
+            self.h, _vp(x_ptr), _vp(y_ptr), _vp(s_src_mirror), _vp(s_dst),
+            _vp(row_indices), _vp(mirror_index), slope, _vp(column_offset),
+            src_s, src_e, dst_s, dst_e, edges, batch, f, heads)
+
+    def gat_forward_fused_bf16(self, x_bf16, y_ptr, s_src_mirror, s_dst,
+                               row_indices, mirror_index, slope,
+                               column_offset, src_s, src_e, dst_s, dst_e,
+                               edges, batch, f, heads):
+        """gat_forward_fused over bfloat16 input rows."""
+        check_heads(f, heads)
+        self._lib.nts_gat_forward_fused_bf16(
+            self.h, _vp(x_bf16), _vp(y_ptr), _vp(s_src_mirror), _vp(s_dst),
+            _vp(row_indices), _vp(mirror_index), slope, _vp(column_offset),
+            src_s, src_e, dst_s, dst_e, edges, batch, f, heads)
 
     # ---- max / min aggregation; op is checked here, the library aborts on
     # an invalid value ----

@@ -912,8 +912,12 @@ void nts_scatter_grad_back_to_message(nts_stream *s, const float *input_grad,
  * replaces a uniformly chosen earlier slot with probability fanout/(j+1)).
  * For each of the `n_dst` destinations: writes min(deg, fanout) sampled
  * GLOBAL source ids into out_src[d*fanout ..] and the count into
- * out_cnt[d].  Deterministic in (seed, column content): the per-step RNG is
- * a counter hash of (seed, dst, step).  Compaction into a sampCSC-style
+ * out_cnt[d]; entries of a row past its count are left untouched.
+ * Deterministic in (seed, column content): keys are a counter hash of
+ * (seed, edge slot), for hub columns of (seed, dst, pick).  The seed goes
+ * through a full 64-bit mix, fmix64(seed + 0x9e3779b97f4a7c15), once per
+ * launch before it meets the counter, so nearby seeds (seed + step) give
+ * unrelated samples.  Compaction into a sampCSC-style
  * local subgraph is host-layer plumbing (torch unique/searchsorted on
  * device — see neutronstarlite_amd/sampler_gpu.py). */
 void nts_sample_reservoir(nts_stream *s, const nts_vid *column_offset,
@@ -921,7 +925,9 @@ void nts_sample_reservoir(nts_stream *s, const nts_vid *column_offset,
     nts_vid fanout, unsigned long long seed, nts_vid *out_src,
     nts_vid *out_cnt);
 /* TEST-ONLY twin: forces the deterministic 64-bit (key,slot) tie fallback
- * so GPU tests can exercise it; results must equal nts_sample_reservoir. */
+ * so GPU tests can exercise it; results must equal nts_sample_reservoir
+ * wherever that selects by key (every column but a hub's, in-degree > 1024
+ * at fanout <= 64, which it samples by rejection instead). */
 void nts_sample_reservoir_dbg_fallback(nts_stream *s,
     const nts_vid *column_offset, const nts_vid *row_indices,
     const nts_vid *dst_list, nts_vid n_dst, nts_vid fanout,

@@ -1205,7 +1205,26 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gather_spmm_dot_lds(
  * per-edge-slot hash keys" (identical distribution to a reservoir walk,
  * same scheme as the host sampler's random keys, deterministic in
  * (seed, edge slot)); a lane-0 sequential reservoir would serialize
- * power-law hubs (measured 133 ms/step on layer-2 batches). */
+ * power-law hubs (measured 133 ms/step on layer-2 batches).
+ *
+ * Seed mixing: the kernel never sees the caller's seed.  launch_sampler
+ * hands it mseed = sampler_mix_seed(seed) = fmix64(seed + 0x9e3779b97f4a7c15),
+ * mixed once on the host, and a key is fmix64(mseed ^ (d << 32) ^ j)
+ * truncated to 32 bits.  XORing the raw seed into the counter made
+ * key(seed ^ m, j) == key(seed, j ^ m): seeds s and s ^ m drew the same
+ * slots translated by m (the same neighbours outright on the hub path,
+ * where the seed only permuted lanes), so consecutive per-step seeds were
+ * not independent.  After the full-avalanche mix two nearby seeds differ in
+ * about half of all 64 bits, which no small difference in j, the lane or d
+ * can cancel; the odd constant keeps seed 0 off fmix64's fixed point 0. */
+static inline unsigned long long sampler_mix_seed(unsigned long long seed) {
+  unsigned long long z = seed + 0x9e3779b97f4a7c15ULL;
+  z = (z ^ (z >> 33)) * 0xff51afd7ed558ccdULL;
+  z = (z ^ (z >> 33)) * 0xc4ceb9fe1a85ec53ULL;
+  return z ^ (z >> 33);
+}
+
+/* `seed` is the MIXED seed (sampler_mix_seed), never the caller's */
 __device__ __forceinline__ uint32_t k_hash_u32(unsigned long long seed,
                                                uint32_t d, uint32_t j) {
   unsigned long long z = seed ^ ((unsigned long long)d << 32) ^ j;
@@ -4504,7 +4523,8 @@ static void launch_sampler(nts_stream *s,
   Tic t(s, NTS_KTAG_ITEMS);
   hipLaunchKernelGGL(kernel, dim3(grid_for((uint64_t)n_dst * 64)),
                      dim3(NTS_BLOCK), 0, s->stream, column_offset, row_indices,
-                     dst_list, n_dst, fanout, seed, out_src, out_cnt);
+                     dst_list, n_dst, fanout, sampler_mix_seed(seed), out_src,
+                     out_cnt);
   dbg_sync(s, "k_sample_reservoir");
 }
 
@@ -4520,7 +4540,9 @@ void nts_sample_reservoir(nts_stream *s, const nts_vid *column_offset,
 /* TEST-ONLY: same sampler with the 32-bit threshold search skipped, so the
  * deterministic 64-bit (key,slot) fallback — the path real inputs almost
  * never reach — is exercised on hardware.  Results must equal the normal
- * entry point's exactly (both select the fanout smallest (key,slot)). */
+ * entry point's exactly (both select the fanout smallest (key,slot)),
+ * except for hub columns (deg > CAP at fanout <= 64), which the normal
+ * entry samples by rejection. */
 void nts_sample_reservoir_dbg_fallback(
     nts_stream *s, const nts_vid *column_offset, const nts_vid *row_indices,
     const nts_vid *dst_list, nts_vid n_dst, nts_vid fanout,

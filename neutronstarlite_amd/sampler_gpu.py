@@ -6,7 +6,11 @@ device — nothing touches the host until the caller asks.
 
 Differences vs the host sampler (sampler.py), both within the reference's
 contract (<= fanout uniformly chosen in-neighbor slots per destination):
-  - the RNG sequence is a counter hash (deterministic in seed/dst/step);
+  - the RNG sequence is a counter hash, deterministic in (seed, edge slot)
+    and, for hubs, (seed, dst, pick).  The seed is passed through a full
+    64-bit mix, fmix64(seed + 0x9e3779b97f4a7c15), once per launch on the
+    host before it meets the counter, so the samples of nearby seeds
+    (seed + step, seed + layer) are unrelated;
   - compacted local source ids are in SORTED-global order (torch.unique)
     rather than first-occurrence order — the mapping is carried explicitly
     in `src`, so downstream arithmetic is order-independent.

@@ -1,12 +1,19 @@
 """GPU-resident sampler (nts_sample_reservoir + device compaction): the
 sampled subgraph must satisfy the reference's sampling contract, be
 deterministic in the seed, and aggregate identically to the oracle."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 import oracle
 from neutronstarlite_amd import graph as G
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from sampler_ref import hash_u32 as _hash_u32_host  # noqa: E402
+from sampler_ref import hub_sample_host as _hub_sample_host  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -76,36 +83,6 @@ def test_contract_and_determinism(setup):
     torch.cuda.synchronize()
     assert not torch.equal(ly.edge_weight, ly3.edge_weight) or \
         torch.equal(ly.row_indices_local, ly3.row_indices_local)
-
-
-def _hash_u32_host(seed, j, d=0):
-    """Host replica of k_hash_u32 (nts_hip.hip) for exactness checks."""
-    z = (np.uint64(seed) ^ (np.uint64(d) << np.uint64(32))) ^ np.uint64(j)
-    with np.errstate(over="ignore"):
-        z = (z ^ (z >> np.uint64(33))) * np.uint64(0xFF51AFD7ED558CCD)
-        z = (z ^ (z >> np.uint64(33))) * np.uint64(0xC4CEB9FE1A85EC53)
-    return ((z ^ (z >> np.uint64(33))) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
-
-
-def _hub_sample_host(seed, d, deg, fanout):
-    """Host replica of the kernel's O(fanout) hub rejection sampler
-    (nts_hip.hip: deg > CAP path): slot_p = hash(seed, d, p|attempt<<10)
-    % deg, later picks re-roll on duplicates with earlier picks' CURRENT
-    slots, round-synchronous."""
-    slots = [int(_hash_u32_host(seed, np.uint64(p), d)) % deg
-             for p in range(fanout)]
-    attempts = [0] * fanout
-    for _ in range(100):
-        dup = [any(slots[q] == slots[p] for q in range(p))
-               for p in range(fanout)]
-        if not any(dup):
-            break
-        for p in range(fanout):
-            if dup[p]:
-                attempts[p] += 1
-                slots[p] = int(_hash_u32_host(
-                    seed, np.uint64(p | (attempts[p] << 10)), d)) % deg
-    return slots
 
 
 def test_sampler_tie_fallback_deterministic_and_exact(setup):

@@ -865,6 +865,75 @@ void nts_gat_forward_fused_bf16(nts_stream *s, const uint16_t *input,
     nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid batch_size,
     nts_vid feature_size, nts_vid heads);
 
+/* ---- fused GATv2 inference forward (additive): one row pass ----
+ * The forward of nts_edge_gatv2_score[_bf16], the edge softmax and
+ * nts_gather_by_dst_from_src_heads[_bf16] for a caller that needs only the
+ * aggregated rows (evaluation).  Per edge e into destination d and head k,
+ * C = feature_size / heads, columns head-major:
+ *   t[c]   = x_l[src(e), c] + x_r[d, c]             ONE fp32 add, as the score
+ *   s      = sum_{j<C} att[k*C+j] * lrelu(t[k*C+j]) lrelu(t) = t > 0 ? t : slope*t
+ *   output[d, c] += sum_e softmax_e(s)[e, c / C] * x_l[src(e), c]
+ * with src(e) = row_indices[e] - src_start.  Every source row is read ONCE:
+ * the row a lane loads serves the score and then the aggregation, and the
+ * softmax is evaluated online per (lane, head) as (m, S, acc):
+ *   stable (nts_edge_softmax_stable): m = -inf, S = 0, acc = 0 and
+ *     m' = max(m, s), S = S*exp(m-m') + exp(s-m'), acc = acc*exp(m-m') +
+ *     exp(s-m')*x, the maximum and the rescale taken once per block of up to
+ *     four edges;
+ *   default: m = 0, never rescaled: sum exp(s)*x / sum exp(s), unspecified
+ *     wherever the default softmax is (an exp overflows, or all of a
+ *     destination's underflow).
+ * Scores must be finite.  The mode is recorded for
+ * nts_edge_softmax_stable_last.
+ *   Two forms walk the work items of column_offset.  Fast, C a power of two
+ * and C / R <= 64: a lane holds R = 4 / 2 / 1 consecutive columns (the widest
+ * that divides C and that every pointer permits: R*4 bytes of alignment for
+ * att, output and fp32 rows, R*2 for bf16 rows), a group of G <= 64 lanes
+ * owns one (item, slab of G*R columns), a head is an aligned segment of C / R
+ * lanes whose butterfly sums the score; four edges are in flight.  General,
+ * any heads and C <= 1024, and whenever nts_heads_dbg_general is set: a wave
+ * per (item, head), lane l owning the head's columns l + 64*i.
+ *   No atomics.  A destination that is one work item ends with a plain
+ * output += acc / S, so rows without edges are untouched and the caller
+ * zeroes.  A split destination's items store (acc, m, S) records into a
+ * stream-owned scratch of (batch_size + edges / NTS_SPLIT + 1) *
+ * (feature_size + 2*heads) floats (none while edges <= NTS_SPLIT; grown on
+ * demand, which synchronizes once), and a second small kernel merges them in
+ * item order:  M = max m_i,  y = sum_i exp(m_i - M)*acc_i / sum_i exp(m_i -
+ * M)*S_i.  The result is therefore bit-reproducible from launch to launch,
+ * split destinations included.  Nothing else sized by `edges` is allocated,
+ * read or written besides row_indices.
+ *   x_l is [rows, feature_size], x_r [batch_size, feature_size], both fp32 or
+ * both bf16 (raw uint16_t, widened exactly; at the same form and R the bf16
+ * entry is bit-identical to the fp32 one on the widened rows); att
+ * [feature_size] and output are fp32.  Both kernels run under NTS_KTAG_FWD;
+ * the edge count is the caller's: no device-to-host copy, no synchronize
+ * beyond scratch growth.  Invalid heads abort as for the heads gathers.
+ *   Returns 1 when the forward ran or there was nothing to do (batch_size ==
+ * 0 or edges == 0: nothing launched); 0 when C > 1024: nothing is launched
+ * or written and the caller runs the three-entry chain instead.
+ *   nts_gatv2_forward_fused_plan reports the decision without touching a
+ * device (the launch takes it from the same function): form 0 none, 1 fast,
+ * 2 general; cols_per_lane R (1 in the general form), lane_group G (64),
+ * slabs = tasks per item (heads in the general form), the grid, and the
+ * scratch size.  elem_bytes 4 or 2; row_alignment_bytes the common alignment
+ * of x_l and x_r, fp32_alignment_bytes that of att and output; general != 0
+ * as under nts_heads_dbg_general. */
+int nts_gatv2_forward_fused(nts_stream *s, const float *x_l, const float *x_r,
+    float *output, const float *att, float slope, const nts_vid *row_indices,
+    const nts_vid *column_offset, nts_vid src_start, nts_vid batch_size,
+    nts_vid edges, nts_vid feature_size, nts_vid heads);
+int nts_gatv2_forward_fused_bf16(nts_stream *s, const uint16_t *x_l,
+    const uint16_t *x_r, float *output, const float *att, float slope,
+    const nts_vid *row_indices, const nts_vid *column_offset,
+    nts_vid src_start, nts_vid batch_size, nts_vid edges,
+    nts_vid feature_size, nts_vid heads);
+void nts_gatv2_forward_fused_plan(nts_vid feature_size, nts_vid heads,
+    unsigned elem_bytes, unsigned row_alignment_bytes,
+    unsigned fp32_alignment_bytes, nts_vid batch_size, nts_vid edges,
+    int general, int *form, int *cols_per_lane, int *lane_group, int *slabs,
+    int *grid, unsigned long long *scratch_bytes);
+
 /* Opt-in work-item reuse: with enable=1 the stream caches its two most
  * recent item decompositions keyed on (offset pointer, batch, edges) and
  * skips identical rebuilds.  ONLY safe while the caller keeps those

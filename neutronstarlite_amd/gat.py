@@ -600,6 +600,30 @@ class GATv2Layer(_EdgeLayer):
             ch.src_s, ch.src_e, ch.dst_s, ch.dst_e, E, ch.dst_n, f, K)
         return y, saved
 
+    def forward_fused(self, x_l: torch.Tensor, x_r: torch.Tensor,
+                      att: torch.Tensor, negative_slope: float = 0.2):
+        """The forward for evaluation: y of forward(x_l, x_r, att) and
+        nothing else.  One entry (Stream.gatv2_forward_fused) reads every
+        source row once, for the score and then the aggregation, with the
+        softmax evaluated online, so no [E, K] tensor is allocated, written
+        or kept; there is no `saved`, no dropout and no backward.  Inputs as
+        for forward (checked the same way, a bad one raises before any
+        launch); either softmax mode of the layer.  y is bit-reproducible
+        from call to call, split destinations included.  A head wider than
+        1024 columns runs forward instead."""
+        ch, st, E, K = self.ch, self.stream, self.E, self.heads
+        f = self._check_inputs(x_l, x_r, att)
+        st.items_reuse(1)
+        y = torch.zeros(ch.dst_n, f, device=x_l.device)
+        ran = (st.gatv2_forward_fused_bf16 if x_l.dtype == torch.bfloat16
+               else st.gatv2_forward_fused)(
+            x_l.data_ptr(), x_r.data_ptr(), y.data_ptr(), att.data_ptr(),
+            negative_slope, ch.row_indices.data_ptr(),
+            ch.column_offset.data_ptr(), ch.src_s, ch.dst_n, E, f, K)
+        if not ran:
+            return self.forward(x_l, x_r, att, negative_slope)[0]
+        return y
+
     def backward(self, grad_y: torch.Tensor, saved,
                  negative_slope: float = 0.2):
         """Returns (grad_x_l[src_n, K*C], grad_x_r[dst_n, K*C],
@@ -694,6 +718,12 @@ def attend_v2(x_l: torch.Tensor, x_r: torch.Tensor, att: torch.Tensor,
     contiguous, on the device; anything else raises before a launch).  The
     projections stay in torch: x_l = x @ W_l, x_r = x @ W_r.  Weight sharing
     (x_l is x_r) needs no special case: autograd adds the two gradients.
-    dropout, seed: attention dropout as for `attend`."""
+    dropout, seed: attention dropout as for `attend`.
+    Under torch.no_grad() with dropout == 0 (evaluation) the call is
+    layer.forward_fused: the same y, with no [E, K] tensor allocated or
+    kept."""
+    if not torch.is_grad_enabled() and dropout == 0:
+        _draw_seed(dropout, seed)   # the same argument checks
+        return layer.forward_fused(x_l, x_r, att, negative_slope)
     return _AttendV2Fn.apply(x_l, x_r, att, layer, negative_slope, dropout,
                              _draw_seed(dropout, seed))

@@ -143,6 +143,15 @@ def lib():
     l.nts_gat_forward_fused.argtypes = (
         [_vp] + [_vp] * 6 + [_c.c_float] + [_vp] + [_u32] * 8)
     l.nts_gat_forward_fused_bf16.argtypes = l.nts_gat_forward_fused.argtypes
+    # fused GATv2 inference forward (one row pass, online softmax)
+    l.nts_gatv2_forward_fused.argtypes = (
+        [_vp] + [_vp] * 4 + [_c.c_float] + [_vp] * 2 + [_u32] * 5)
+    l.nts_gatv2_forward_fused.restype = _i32
+    l.nts_gatv2_forward_fused_bf16.argtypes = (
+        l.nts_gatv2_forward_fused.argtypes)
+    l.nts_gatv2_forward_fused_bf16.restype = _i32
+    l.nts_gatv2_forward_fused_plan.argtypes = (
+        [_u32] * 2 + [_c.c_uint] * 3 + [_u32] * 2 + [_i32] + [_vp] * 6)
     l.nts_edge_softmax_stable.argtypes = [_vp, _i32]
     l.nts_edge_softmax_stable_last.argtypes = [_vp, _vp]
     # attention dropout
@@ -287,6 +296,26 @@ def gather_plan_heads_bf16(f, heads, alignment, batch, edges):
     input and the output in bytes."""
     return _plan_heads(lib().nts_gather_plan_heads_bf16, f, heads, alignment,
                        batch, edges)
+
+
+def gatv2_forward_fused_plan(f, heads, elem_bytes, row_alignment,
+                             fp32_alignment, batch, edges, general=False):
+    """The launch decision of Stream.gatv2_forward_fused[_bf16] (no device
+    access): dict of form (0 none: C > 1024, 1 fast, 2 general),
+    cols_per_lane, lane_group, slabs (tasks per item), grid and
+    scratch_bytes.  elem_bytes 4 or 2; row_alignment the common alignment of
+    x_l and x_r in bytes, fp32_alignment that of att and the output; general
+    as under Stream.heads_dbg_general."""
+    check_heads(f, heads)
+    names = ("form", "cols_per_lane", "lane_group", "slabs", "grid")
+    out = [_i32(0) for _ in names]
+    scratch = _c.c_ulonglong(0)
+    lib().nts_gatv2_forward_fused_plan(
+        f, heads, elem_bytes, row_alignment, fp32_alignment, batch, edges,
+        1 if general else 0, *[_c.byref(o) for o in out], _c.byref(scratch))
+    plan = {n: o.value for n, o in zip(names, out)}
+    plan["scratch_bytes"] = scratch.value
+    return plan
 
 
 def check_dropout(p, seed):
@@ -756,6 +785,33 @@ class Stream:
             self.h, _vp(x_bf16), _vp(y_ptr), _vp(s_src_mirror), _vp(s_dst),
             _vp(row_indices), _vp(mirror_index), slope, _vp(column_offset),
             src_s, src_e, dst_s, dst_e, edges, batch, f, heads)
+
+    # ---- fused GATv2 inference forward: score, online softmax and
+    # aggregation from one load of every source row ----
+    def gatv2_forward_fused(self, x_l, x_r, y_ptr, att, slope, row_indices,
+                            column_offset, src_start, batch, edges, f, heads):
+        """y[d, c] += sum over d's in-edges of softmax(att[k] . leaky_relu(
+        x_l[src] + x_r[d]))[e, c // C] * x_l[src, c]: edge_gatv2_score, the
+        edge softmax and gather_by_dst_from_src_heads in one row pass that
+        keeps nothing per edge and uses no atomics (bit-reproducible).
+        Honours edge_softmax_stable.  Returns 1 when it ran (or there was
+        nothing to do), 0 when C > 1024: nothing was launched and the caller
+        runs the three-entry chain."""
+        check_heads(f, heads)
+        return self._lib.nts_gatv2_forward_fused(
+            self.h, _vp(x_l), _vp(x_r), _vp(y_ptr), _vp(att), slope,
+            _vp(row_indices), _vp(column_offset), src_start, batch, edges, f,
+            heads)
+
+    def gatv2_forward_fused_bf16(self, x_l_bf16, x_r_bf16, y_ptr, att, slope,
+                                 row_indices, column_offset, src_start, batch,
+                                 edges, f, heads):
+        """gatv2_forward_fused with both row operands bfloat16."""
+        check_heads(f, heads)
+        return self._lib.nts_gatv2_forward_fused_bf16(
+            self.h, _vp(x_l_bf16), _vp(x_r_bf16), _vp(y_ptr), _vp(att), slope,
+            _vp(row_indices), _vp(column_offset), src_start, batch, edges, f,
+            heads)
 
     # ---- max / min aggregation; op is checked here, the library aborts on
     # an invalid value ----

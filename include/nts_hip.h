@@ -934,6 +934,98 @@ void nts_gatv2_forward_fused_plan(nts_vid feature_size, nts_vid heads,
     int general, int *form, int *cols_per_lane, int *lane_group, int *slabs,
     int *grid, unsigned long long *scratch_bytes);
 
+/* ---- fused GAT training backward (additive): no per-edge state ----
+ * The backward of nts_gat_forward_fused[_bf16] (equally of the attention
+ * forward + heads gather chain without dropout) for a caller that kept only
+ * the forward's inputs and output.  Per edge e = (u -> d) and head k, C =
+ * feature_size / heads, columns head-major, u = row_indices[e] - src_start:
+ *   t      = s_src[u*K + k] + s_dst[d*K + k]
+ *   alpha  = exp(lrelu(t) - M[d, k]) / S[d, k]       M = 0 in the default mode
+ *   gdot   = sum_{j<C} grad_output[d, k*C+j] * input[u, k*C+j]
+ *   D[d,k] = sum_{j<C} grad_output[d, k*C+j] * output[d, k*C+j]
+ *   g_t    = alpha * (gdot - D[d, k]) * (t > 0 ? 1 : slope)
+ *   grad_input[u, c]   += sum_{e out of u} alpha[e, c / C] * grad_output[d, c]
+ *   grad_s_src[u*K+k]  += sum_{e out of u} g_t
+ *   grad_s_dst[d*K+k]  += sum_{e into d}   g_t
+ * `output` is the y the forward returned for the same inputs: D, the softmax
+ * backward's per-destination sum, is a row dot with it and needs no edge pass.
+ *   Four steps.  (1) Pass 1 of nts_gat_forward_fused again (NTS_KTAG_EDGE):
+ * S, or the (M, S) pairs with the split-sum pass when stable, into the
+ * softmax's stream-owned scratch.  (2) A record pass (NTS_KTAG_EDGE) writes
+ * {s_dst, M, S, D} per (d, k), 16 bytes, into a stream-owned scratch of
+ * 16 * (dst_end - dst_start) * heads bytes (grown on demand, which
+ * synchronizes once).  (3) The CSC walk (NTS_KTAG_BWD) over the items of
+ * column_offset keeps grad_output[d] and d's record in registers, gathers
+ * input[u] and s_src[u] per in-edge and accumulates grad_s_dst.  (4) The CSR
+ * walk (NTS_KTAG_BWD) over the items of row_offset keeps input[u] and
+ * s_src[u] in registers, gathers grad_output[d] and d's record (one 16-byte
+ * load) per out-edge and accumulates grad_input and grad_s_src.
+ * column_indices holds global destination ids (d = column_indices[e] -
+ * dst_start).  Nothing sized by `edges` is allocated, read or written besides
+ * the two index lists.  There is no mirror_index and no dropout.
+ *   Both walks are one kernel template in the forms and geometry of
+ * nts_gatv2_forward_fused.  Fast, C a power of two and C / R <= 64: a lane
+ * holds R = 4 / 2 / 1 consecutive columns (the widest that divides C and that
+ * every pointer permits: R*4 bytes of alignment for grad_output, grad_input
+ * and fp32 input rows, R*2 for bf16 input rows), a group of G <= 64 lanes
+ * owns one (item, slab of G*R columns), gdot is a butterfly over the head's
+ * C / R lanes, four edges are in flight.  General, any heads with C <= 1024,
+ * and whenever nts_heads_dbg_general is set: a wave per (item, head), lane l
+ * owning the head's columns l + 64*i.
+ *   alpha is the expression of the fused forward's pass 2 (a true division),
+ * and each grad_input element is one lane's fmaf chain in edge order: for a
+ * source that is one work item and whose destinations are each one work item,
+ * grad_input is bit-identical to nts_gather_by_src_from_dst_heads on the
+ * training forward's CSR-order softmax.  A vertex that is one work item
+ * stores with a plain read-add-write, so its results are bit-reproducible
+ * from call to call; a split vertex merges its items by fp32 atomics, one per
+ * (item, element).
+ *   All three gradient outputs keep the += contract (the caller zeroes; rows
+ * without edges are untouched).  input is [src_end - src_start, feature_size]
+ * fp32, or bf16 as raw uint16_t, widened exactly; everything else is fp32:
+ * output and grad_output [dst_end - dst_start, feature_size], s_src and
+ * grad_s_src [src rows, heads], s_dst and grad_s_dst [dst rows, heads].  s_src
+ * points at the row of vertex src_start: step 1 indexes by the global source
+ * id and is handed the address s_src - src_start * heads floats, which is
+ * formed but never dereferenced below s_src (a binding must pass a pointer
+ * for which that subtraction does not wrap).  The
+ * softmax mode is the stream's and the call is recorded for
+ * nts_edge_softmax_stable_last.  The edge count is the caller's: no
+ * device-to-host copy, no synchronize beyond scratch growth.  Invalid heads
+ * abort as for the heads gathers.
+ *   Returns 1 when the backward ran or there was nothing to do (edges == 0 or
+ * no rows on either side: nothing launched); 0 when C > 1024: nothing is
+ * launched or written and the caller runs the training chain instead.
+ *   nts_gat_backward_fused_plan reports the decision without touching a
+ * device (the launch takes it from the same function): form 0 none, 1 fast,
+ * 2 general; cols_per_lane R (1 in the general form), lane_group G, slabs =
+ * tasks per item (heads in the general form), the two walks' grids and the
+ * record scratch size (0 at form 0).  elem_bytes 4 or 2; row_alignment_bytes
+ * the alignment of input, fp32_alignment_bytes the common alignment of
+ * grad_output and grad_input; general != 0 as under nts_heads_dbg_general. */
+int nts_gat_backward_fused(nts_stream *s, const float *input,
+    const float *output, const float *grad_output, float *grad_input,
+    float *grad_s_src, float *grad_s_dst, const float *s_src,
+    const float *s_dst, float slope, const nts_vid *row_indices,
+    const nts_vid *column_offset, const nts_vid *row_offset,
+    const nts_vid *column_indices, nts_vid src_start, nts_vid src_end,
+    nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid feature_size,
+    nts_vid heads);
+int nts_gat_backward_fused_bf16(nts_stream *s, const uint16_t *input,
+    const float *output, const float *grad_output, float *grad_input,
+    float *grad_s_src, float *grad_s_dst, const float *s_src,
+    const float *s_dst, float slope, const nts_vid *row_indices,
+    const nts_vid *column_offset, const nts_vid *row_offset,
+    const nts_vid *column_indices, nts_vid src_start, nts_vid src_end,
+    nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid feature_size,
+    nts_vid heads);
+void nts_gat_backward_fused_plan(nts_vid feature_size, nts_vid heads,
+    unsigned elem_bytes, unsigned row_alignment_bytes,
+    unsigned fp32_alignment_bytes, nts_vid src_rows, nts_vid dst_rows,
+    nts_vid edges, int general, int *form, int *cols_per_lane,
+    int *lane_group, int *slabs, int *grid_csr, int *grid_csc,
+    unsigned long long *scratch_bytes);
+
 /* Opt-in work-item reuse: with enable=1 the stream caches its two most
  * recent item decompositions keyed on (offset pointer, batch, edges) and
  * skips identical rebuilds.  ONLY safe while the caller keeps those

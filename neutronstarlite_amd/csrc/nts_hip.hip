@@ -139,6 +139,8 @@ struct nts_stream {
   uint32_t stripe_last = 0, stripe_run_last = 0; /* what the last gather ran */
   float *v2_ws = nullptr;    /* fused GATv2 forward: records of shared items */
   uint64_t v2_cap = 0;       /* in bytes */
+  float4 *rec_ws = nullptr;  /* fused GAT backward: (destination, head) records */
+  uint64_t rec_cap = 0;      /* in bytes */
 };
 
 namespace {
@@ -2588,6 +2590,280 @@ NTS_NO_PK __global__ void k_gatv2_fused_merge(
   }
 }
 
+/* ---- GAT training backward that recomputes the attention weights ---- */
+/* An edge's weight alpha_e = exp(lrelu(s_src[u] + s_dst[d]) - M[d]) / S[d] is
+ * a function of two per-vertex scalars and the destination's denominator, so
+ * the backward keeps nothing per edge either.  With gdot_e = gy[d] . h[u]
+ * over the head's columns and D[d] = sum_e alpha_e * gdot_e = gy[d] . y[d]
+ * (the softmax backward's per-destination sum is a row dot with the forward's
+ * own output):
+ *   g_t_e        = alpha_e * (gdot_e - D[d]) * lrelu'(t_e)
+ *   grad_h[u]    += sum_{e out of u} alpha_e * gy[d]
+ *   grad_s_src[u] += sum_{e out of u} g_t_e
+ *   grad_s_dst[d] += sum_{e into d}   g_t_e
+ * Pass 1 of the fused forward leaves (M, S) again; k_gat_bwd_record folds
+ * them, s_dst and D into one 16-byte record per (destination, head), which
+ * the CSR walk — destinations in scattered order — fetches with one load per
+ * edge and lane.  One walker template runs both directions: the item's own
+ * row stays in registers, the neighbour row is gathered per edge, the head's
+ * lanes sum the dot by a butterfly, the weight is att_weight on the record.
+ *   CSR walk (items of row_offset, own row h[u], gathered gy[d] + record):
+ *     accumulates grad_h[u] and grad_s_src[u];
+ *   CSC walk (items of column_offset, own row gy[d] + record, gathered h[u] +
+ *     s_src[u]): accumulates grad_s_dst[d], no row output.
+ * Either scalar gradient by per-edge atomics onto the other side's vertex
+ * would serialise on hubs, hence a walk per direction.  Each grad_h element
+ * is one lane's fmaf chain in edge order (fma_vec's), an unsplit vertex ends
+ * with a plain read-add-write, a split one with one atomic per (item,
+ * element).  Built without packed fp32 instructions, as the fused GATv2
+ * forward above. */
+
+/* {s_dst, M, S, D} of one (destination, head); M = 0 in the default mode */
+template <bool STABLE>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gat_bwd_record(
+    const float *__restrict__ gy, const float *__restrict__ y,
+    const float *__restrict__ s_dst, const void *__restrict__ slots,
+    float4 *__restrict__ recs, uint32_t rows, uint32_t f, uint32_t K,
+    uint32_t C, uint32_t G) {
+  const uint32_t glane = threadIdx.x & (G - 1);
+  const AttSrc at{nullptr, s_dst, nullptr, slots, 0.f};
+  const uint64_t total = (uint64_t)rows * K;
+  const uint64_t stride = (gridDim.x * NTS_BLOCK) / G;
+  /* a group of G lanes per (destination, head): lanes stride the head's C
+   * columns, seg_sum over the group */
+  for (uint64_t t = (blockIdx.x * NTS_BLOCK + threadIdx.x) / G; t < total;
+       t += stride) {
+    const uint64_t base = (t / K) * f + (t % K) * C;
+    float d = 0.f;
+    for (uint32_t c = glane; c < C; c += G)
+      d = fmaf(gy[base + c], y[base + c], d);
+    d = seg_sum(d, G);
+    if (glane == 0) {
+      const AttDen q = att_den<STABLE>(at, t);
+      recs[t] = make_float4(q.sd, q.M, q.S, d);
+    }
+  }
+}
+
+/* one walk: TO / TG = element types of the own and the gathered rows */
+template <typename TO, typename TG>
+struct GatBwd {
+  const uint32_t *__restrict__ nbr;
+  const TO *__restrict__ own;     /* CSR: h,  CSC: gy */
+  const TG *__restrict__ rows;    /* CSR: gy, CSC: h */
+  const float *__restrict__ s_src;
+  const float4 *__restrict__ recs;
+  float *__restrict__ grad_rows;  /* CSR: grad_h; CSC: none */
+  float *__restrict__ grad_s;     /* CSR: grad_s_src, CSC: grad_s_dst */
+  float slope;
+  uint32_t nbr_start, f, K, C;
+};
+/* what an edge's weight needs: the source scalar, the destination's
+ * (s_dst, M, S) and D.  One half is the item's own (loaded once), the other
+ * the neighbour's (loaded per edge). */
+struct BwdEdge { float ss; AttDen q; float D; };
+template <bool CSR, typename TO, typename TG>
+__device__ __forceinline__ BwdEdge bwd_own(const GatBwd<TO, TG> &g,
+                                           uint32_t v, uint32_t head) {
+  BwdEdge o{};
+  if constexpr (CSR) {
+    o.ss = g.s_src[(uint64_t)v * g.K + head];
+  } else {
+    const float4 r = g.recs[(uint64_t)v * g.K + head];
+    o.q = AttDen{r.x, r.y, r.z};
+    o.D = r.w;
+  }
+  return o;
+}
+template <bool CSR, typename TO, typename TG>
+__device__ __forceinline__ BwdEdge bwd_nbr(const GatBwd<TO, TG> &g,
+                                           uint32_t n, uint32_t head,
+                                           BwdEdge o) {
+  if constexpr (CSR) {
+    const float4 r = g.recs[(uint64_t)n * g.K + head];
+    o.q = AttDen{r.x, r.y, r.z};
+    o.D = r.w;
+  } else {
+    o.ss = g.s_src[(uint64_t)n * g.K + head];
+  }
+  return o;
+}
+/* NE edges into the accumulators: N columns per lane in xv, the head's dots
+ * in gd */
+template <int N, int NE, bool STABLE, bool CSR>
+__device__ __forceinline__ void bwd_update(float (&acc)[N], float &acc_s,
+                                           const BwdEdge (&ed)[NE],
+                                           const float (&gd)[NE],
+                                           const float (&xv)[NE][N],
+                                           float slope) {
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    const float alpha = att_weight<STABLE>(ed[k].ss, ed[k].q, slope);
+    if constexpr (CSR) {
+#pragma unroll
+      for (int j = 0; j < N; ++j) acc[j] = fmaf(alpha, xv[k][j], acc[j]);
+    }
+    const float dl = (ed[k].ss + ed[k].q.sd) > 0.f ? 1.f : slope;
+    acc_s += alpha * (gd[k] - ed[k].D) * dl;
+  }
+}
+/* the scalar gradient of one (item, head), by the lane that owns it */
+__device__ __forceinline__ void bwd_store_scalar(float *p, float v,
+                                                 bool shared) {
+  if (shared) atomicAdd(p, v);
+  else *p += v;
+}
+
+/* fast form: NE consecutive edges; indices, records / scalars and rows are
+ * issued before the first row is consumed */
+template <int R, int NE, bool STABLE, bool CSR, typename TO, typename TG>
+__device__ __forceinline__ void bwd_edges_seg(float (&acc)[R], float &acc_s,
+                                              const GatBwd<TO, TG> &g,
+                                              uint32_t e, uint32_t col,
+                                              uint32_t head, uint32_t L,
+                                              const float (&own)[R],
+                                              const BwdEdge &o) {
+  const TG *p[NE];
+  BwdEdge ed[NE];
+  float xv[NE][R], gd[NE];
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    const uint32_t n = g.nbr[e + k] - g.nbr_start;
+    p[k] = g.rows + (uint64_t)n * g.f + col;
+    ed[k] = bwd_nbr<CSR>(g, n, head, o);
+  }
+#pragma unroll
+  for (int k = 0; k < NE; ++k) load_cols<R>(p[k], xv[k]);
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    gd[k] = 0.f;
+#pragma unroll
+    for (int j = 0; j < R; ++j) gd[k] = fmaf(own[j], xv[k][j], gd[k]);
+  }
+  for (uint32_t w = L >> 1; w >= 1; w >>= 1)
+#pragma unroll
+    for (int k = 0; k < NE; ++k) gd[k] += __shfl_xor(gd[k], w, 64);
+  bwd_update<R, NE, STABLE, CSR>(acc, acc_s, ed, gd, xv, g.slope);
+}
+
+/* Fast form, C a power of two and L = C/R <= 64 lanes per head: the geometry
+ * of k_gatv2_fused_seg.  A group of G lanes owns a task (item, slab of G*R
+ * columns), a lane R consecutive columns of one head; lanes past the row's
+ * end are whole segments and take no part; the lanes of a segment share
+ * their task, so the butterfly only reads lanes that run with it. */
+template <int R, bool STABLE, bool CSR, typename TO, typename TG>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gat_bwd_seg(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const GatBwd<TO, TG> g, uint32_t G, uint32_t n_slabs) {
+  const uint32_t n_items = *n_items_p;
+  const uint32_t glane = threadIdx.x & (G - 1);
+  const uint32_t L = g.C / R;
+  const uint64_t total = (uint64_t)n_items * n_slabs;
+  const uint64_t stride = (gridDim.x * NTS_BLOCK) / G;
+  for (uint64_t t = (blockIdx.x * NTS_BLOCK + threadIdx.x) / G; t < total;
+       t += stride) {
+    const uint32_t it = (uint32_t)(t / n_slabs);
+    const uint32_t col = (uint32_t)(t % n_slabs) * G * R + glane * R;
+    if (col >= g.f) continue;
+    const Item im = load_item(items, it);
+    const uint32_t head = col / g.C;
+    float own[R], acc[R] = {};
+    load_cols<R>(g.own + (uint64_t)im.v * g.f + col, own);
+    const BwdEdge o = bwd_own<CSR>(g, im.v, head);
+    float acc_s = 0.f;
+    const uint32_t e_end = im.e0 + im.cnt;
+    uint32_t e = im.e0;
+    for (; e + 4 <= e_end; e += 4)
+      bwd_edges_seg<R, 4, STABLE, CSR>(acc, acc_s, g, e, col, head, L, own, o);
+    for (; e < e_end; ++e)
+      bwd_edges_seg<R, 1, STABLE, CSR>(acc, acc_s, g, e, col, head, L, own, o);
+    if constexpr (CSR)
+      store_acc<R>(g.grad_rows + (uint64_t)im.v * g.f + col, acc, R,
+                   im.shared);
+    if ((glane & (L - 1)) == 0)
+      bwd_store_scalar(g.grad_s + (uint64_t)im.v * g.K + head, acc_s,
+                       im.shared);
+  }
+}
+
+/* general form: NE consecutive edges of one (item, head) across the wave */
+template <int NCH, int NE, bool STABLE, bool CSR, typename TO, typename TG>
+__device__ __forceinline__ void bwd_edges_wave(float (&acc)[NCH], float &acc_s,
+                                               const GatBwd<TO, TG> &g,
+                                               uint32_t e, uint32_t col,
+                                               uint32_t head, uint32_t lane,
+                                               const float (&own)[NCH],
+                                               const BwdEdge &o) {
+  const TG *p[NE];
+  BwdEdge ed[NE];
+  float xv[NE][NCH], gd[NE];
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    const uint32_t n = g.nbr[e + k] - g.nbr_start;
+    p[k] = g.rows + (uint64_t)n * g.f + col;
+    ed[k] = bwd_nbr<CSR>(g, n, head, o);
+  }
+#pragma unroll
+  for (int k = 0; k < NE; ++k)
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+      xv[k][i] = (lane + 64 * i < g.C) ? to_f32(p[k][64 * i]) : 0.f;
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    float pr = 0.f;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) pr = fmaf(own[i], xv[k][i], pr);
+    gd[k] = wave_sum(pr);
+  }
+  bwd_update<NCH, NE, STABLE, CSR>(acc, acc_s, ed, gd, xv, g.slope);
+}
+
+/* General form, any K and C <= 64*NCH: a wave runs one (item, head), lane l
+ * owns the head's columns l + 64*i, i < NCH (dead ones hold zeros and are
+ * never stored); the dot is a wave_sum.  NE as in k_gatv2_fused_wave. */
+template <int NCH, bool STABLE, bool CSR, typename TO, typename TG>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gat_bwd_wave(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const GatBwd<TO, TG> g) {
+  constexpr int NE = NCH <= 4 ? 4 : 16 / NCH;
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  const uint64_t total = (uint64_t)n_items * g.K;
+  for (uint64_t t = w.wave; t < total; t += w.n_waves) {
+    const uint32_t it = (uint32_t)(t / g.K), head = (uint32_t)(t % g.K);
+    const Item im = load_item(items, it);
+    const uint32_t col = head * g.C + w.lane;
+    float own[NCH], acc[NCH] = {};
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+      own[i] = (w.lane + 64 * i < g.C)
+                   ? to_f32(g.own[(uint64_t)im.v * g.f + col + 64 * i])
+                   : 0.f;
+    const BwdEdge o = bwd_own<CSR>(g, im.v, head);
+    float acc_s = 0.f;
+    const uint32_t e_end = im.e0 + im.cnt;
+    uint32_t e = im.e0;
+    for (; e + NE <= e_end; e += NE)
+      bwd_edges_wave<NCH, NE, STABLE, CSR>(acc, acc_s, g, e, col, head, w.lane,
+                                           own, o);
+    for (; e < e_end; ++e)
+      bwd_edges_wave<NCH, 1, STABLE, CSR>(acc, acc_s, g, e, col, head, w.lane,
+                                          own, o);
+    if constexpr (CSR) {
+      float *op = g.grad_rows + (uint64_t)im.v * g.f + col;
+#pragma unroll
+      for (int i = 0; i < NCH; ++i)
+        if (w.lane + 64 * i < g.C) {
+          if (im.shared) atomicAdd(&op[64 * i], acc[i]);
+          else op[64 * i] += acc[i];
+        }
+    }
+    if (w.lane == 0)
+      bwd_store_scalar(g.grad_s + (uint64_t)im.v * g.K + head, acc_s,
+                       im.shared);
+  }
+}
+
 /* ---- GATv2 attention: the backward of the f-wide per-edge score ---- */
 
 /* One walk over an offset array, the shape of k_gather_spmm_heads: a group of
@@ -3446,6 +3722,7 @@ void nts_stream_destroy(nts_stream *s) {
   if (s->keys_ws) hipFree(s->keys_ws);
   if (s->stage_ws) hipFree(s->stage_ws);
   if (s->v2_ws) hipFree(s->v2_ws);
+  if (s->rec_ws) hipFree(s->rec_ws);
   if (s->owned) hipStreamDestroy(s->stream);
   delete s;
 }
@@ -4885,6 +5162,223 @@ void nts_gatv2_forward_fused_plan(nts_vid feature_size, nts_vid heads,
   if (lane_group) *lane_group = (int)p.G;
   if (slabs) *slabs = (int)p.slabs;
   if (grid) *grid = (int)p.grid;
+  if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+}
+
+/* ---- fused GAT training backward (additive; see include/nts_hip.h) ---- */
+extern "C++" {
+/* The launch decision, pure: the plan entry reports it and the launch takes
+ * it.  One geometry serves both walks.  form 0: C > 1024, nothing runs.
+ * form 1 (fast): R columns per lane as pair_cols has it (h by its own element
+ * size; grad_output and grad_input, accessed in R-float vectors, as fp32), G
+ * lanes per task, slabs of G*R columns.  form 2 (general): a wave per (item,
+ * head), R = 1, G = 64, slabs = K tasks per item, nch = the NCH
+ * instantiation. */
+struct GatBwdPlan {
+  int form = 0;
+  uint32_t R = 0, G = 0, slabs = 0, nch = 0, grid_csr = 0, grid_csc = 0;
+  uint64_t scratch_bytes = 0;
+};
+static GatBwdPlan plan_gat_backward(uint32_t f, uint32_t K,
+                                    uint32_t elem_bytes,
+                                    uintptr_t row_alignment,
+                                    uintptr_t fp32_alignment,
+                                    uint32_t src_rows, uint32_t dst_rows,
+                                    uint32_t edges, bool general) {
+  GatBwdPlan p;
+  const uint32_t C = f / K;
+  if (C > 1024) return p;
+  p.scratch_bytes = (uint64_t)dst_rows * K * sizeof(float4);
+  const uint64_t items_csr = (uint64_t)src_rows + edges / NTS_SPLIT + 1;
+  const uint64_t items_csc = (uint64_t)dst_rows + edges / NTS_SPLIT + 1;
+  const bool bf16 = elem_bytes == sizeof(uint16_t);
+  const uint32_t R = pair_cols(C, fp32_alignment | (bf16 ? 0 : row_alignment),
+                               bf16 ? row_alignment : 0);
+  if (!general && (C & (C - 1)) == 0 && C / R <= 64) {
+    p.form = 1;
+    p.R = R;
+    p.G = 64;
+    while (p.G / 2 >= f / R) p.G /= 2;
+    p.slabs = (f + p.G * R - 1) / (p.G * R);
+  } else {
+    p.form = 2;
+    p.R = 1;
+    p.G = 64;
+    p.slabs = K;
+    p.nch = 1;
+    while (p.nch * 64 < C) p.nch *= 2;
+  }
+  p.grid_csr = grid_for(items_csr * p.slabs * p.G);
+  p.grid_csc = grid_for(items_csc * p.slabs * p.G);
+  return p;
+}
+
+/* grown on demand, never cleared: the record pass writes every record of
+ * the call before a walk reads one */
+static float4 *get_rec_scratch(nts_stream *s, uint64_t bytes) {
+  if (s->rec_cap < bytes) {
+    NTS_CHECK(hipStreamSynchronize(s->stream));
+    if (s->rec_ws) NTS_CHECK(hipFree(s->rec_ws));
+    NTS_CHECK(hipMalloc(&s->rec_ws, bytes));
+    s->rec_cap = bytes;
+  }
+  return s->rec_ws;
+}
+
+template <bool CSR, typename TO, typename TG>
+static void launch_gat_bwd_walk(nts_stream *s, const EdgeItems &p,
+                                const GatBwdPlan &pl, uint32_t grid,
+                                const GatBwd<TO, TG> &g) {
+  const bool st = s->softmax_stable;
+  if (pl.form == 1) {
+#define NTS_K(RR)                                                             \
+  (st ? k_gat_bwd_seg<RR, true, CSR, TO, TG>                                  \
+      : k_gat_bwd_seg<RR, false, CSR, TO, TG>)
+    hipLaunchKernelGGL(pl.R == 4 ? NTS_K(4) : pl.R == 2 ? NTS_K(2) : NTS_K(1),
+                       dim3(grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                       p.ib->counter, g, pl.G, pl.slabs);
+#undef NTS_K
+  } else {
+    /* indexed by log2(NCH) */
+    static const decltype(&k_gat_bwd_wave<1, false, CSR, TO, TG>)
+        kernels[2][5] = {{k_gat_bwd_wave<1, false, CSR, TO, TG>,
+                          k_gat_bwd_wave<2, false, CSR, TO, TG>,
+                          k_gat_bwd_wave<4, false, CSR, TO, TG>,
+                          k_gat_bwd_wave<8, false, CSR, TO, TG>,
+                          k_gat_bwd_wave<16, false, CSR, TO, TG>},
+                         {k_gat_bwd_wave<1, true, CSR, TO, TG>,
+                          k_gat_bwd_wave<2, true, CSR, TO, TG>,
+                          k_gat_bwd_wave<4, true, CSR, TO, TG>,
+                          k_gat_bwd_wave<8, true, CSR, TO, TG>,
+                          k_gat_bwd_wave<16, true, CSR, TO, TG>}};
+    hipLaunchKernelGGL(kernels[st][__builtin_ctz(pl.nch)], dim3(grid),
+                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                       p.ib->counter, g);
+  }
+}
+
+/* Pass 1 and the record pass under NTS_KTAG_EDGE, the two walks under
+ * NTS_KTAG_BWD.  Everything over the CSC items runs before the CSR items are
+ * asked for: the stream keeps two item buffers and a third request may
+ * rebuild the first. */
+template <typename T>
+static int gat_backward_fused(nts_stream *s, const char *entry, const T *h,
+                              const float *y, const float *gy, float *grad_h,
+                              float *grad_s_src, float *grad_s_dst,
+                              const float *s_src, const float *s_dst,
+                              float slope, const nts_vid *row_indices,
+                              const nts_vid *column_offset,
+                              const nts_vid *row_offset,
+                              const nts_vid *column_indices, nts_vid src_start,
+                              nts_vid src_end, nts_vid dst_start,
+                              nts_vid dst_end, nts_vid edges, nts_vid f,
+                              nts_vid K) {
+  check_heads(entry, f, K);
+  s->softmax_stable_last = s->softmax_stable;
+  const uint32_t src_rows = src_end > src_start ? src_end - src_start : 0;
+  const uint32_t dst_rows = dst_end > dst_start ? dst_end - dst_start : 0;
+  if (!edges || !src_rows || !dst_rows) return 1;
+  const GatBwdPlan pl = plan_gat_backward(
+      f, K, sizeof(T), (uintptr_t)h, (uintptr_t)gy | (uintptr_t)grad_h,
+      src_rows, dst_rows, edges, s->heads_general);
+  if (!pl.form) return 0;
+  const uint32_t C = f / K;
+  const EdgeItems csc = edge_items_known(s, column_offset, dst_rows, edges);
+  const SoftmaxScratch ws = softmax_scratch(s, (uint64_t)dst_rows * K);
+  float4 *recs = get_rec_scratch(s, pl.scratch_bytes);
+  {
+    Tic t(s, NTS_KTAG_EDGE);
+    /* pass 1 indexes s_src by the global source id */
+    const EdgeScoreOnly score{s_src - (size_t)src_start * K, s_dst,
+                              row_indices, nullptr, slope, 0.f};
+    if (ws.pairs) {
+      launch_reduce(s, csc, K, score, MaxSumOnlyToPairs{ws.pairs});
+      launch_reduce(s, csc, K, EdgeScoreExp{score, ws.pairs, 0.f},
+                    SplitSumToPairs{ws.pairs});
+    } else {
+      launch_reduce(s, csc, K, score, ExpSumToSums{ws.sums});
+    }
+    uint32_t G = 1;
+    while (G < C && G < 64) G *= 2;
+    const dim3 grid(grid_for((uint64_t)dst_rows * K * G));
+    if (ws.pairs)
+      hipLaunchKernelGGL(k_gat_bwd_record<true>, grid, dim3(NTS_BLOCK), 0,
+                         s->stream, gy, y, s_dst, (const void *)ws.pairs, recs,
+                         dst_rows, f, K, C, G);
+    else
+      hipLaunchKernelGGL(k_gat_bwd_record<false>, grid, dim3(NTS_BLOCK), 0,
+                         s->stream, gy, y, s_dst, (const void *)ws.sums, recs,
+                         dst_rows, f, K, C, G);
+    dbg_sync(s, "k_gat_bwd_record");
+  }
+  {
+    Tic t(s, NTS_KTAG_BWD);
+    launch_gat_bwd_walk<false>(
+        s, csc, pl, pl.grid_csc,
+        GatBwd<float, T>{row_indices, gy, h, s_src, recs, nullptr, grad_s_dst,
+                         slope, src_start, f, K, C});
+    dbg_sync(s, "k_gat_bwd (CSC walk)");
+  }
+  const EdgeItems csr = edge_items_known(s, row_offset, src_rows, edges);
+  Tic t(s, NTS_KTAG_BWD);
+  launch_gat_bwd_walk<true>(
+      s, csr, pl, pl.grid_csr,
+      GatBwd<T, float>{column_indices, h, gy, s_src, recs, grad_h, grad_s_src,
+                       slope, dst_start, f, K, C});
+  dbg_sync(s, "k_gat_bwd (CSR walk)");
+  return 1;
+}
+}  // extern "C++"
+
+int nts_gat_backward_fused(
+    nts_stream *s, const float *input, const float *output,
+    const float *grad_output, float *grad_input, float *grad_s_src,
+    float *grad_s_dst, const float *s_src, const float *s_dst, float slope,
+    const nts_vid *row_indices, const nts_vid *column_offset,
+    const nts_vid *row_offset, const nts_vid *column_indices,
+    nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
+    nts_vid edges, nts_vid feature_size, nts_vid heads) {
+  return gat_backward_fused(s, "nts_gat_backward_fused", input, output,
+                            grad_output, grad_input, grad_s_src, grad_s_dst,
+                            s_src, s_dst, slope, row_indices, column_offset,
+                            row_offset, column_indices, src_start, src_end,
+                            dst_start, dst_end, edges, feature_size, heads);
+}
+
+int nts_gat_backward_fused_bf16(
+    nts_stream *s, const uint16_t *input, const float *output,
+    const float *grad_output, float *grad_input, float *grad_s_src,
+    float *grad_s_dst, const float *s_src, const float *s_dst, float slope,
+    const nts_vid *row_indices, const nts_vid *column_offset,
+    const nts_vid *row_offset, const nts_vid *column_indices,
+    nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
+    nts_vid edges, nts_vid feature_size, nts_vid heads) {
+  return gat_backward_fused(s, "nts_gat_backward_fused_bf16", input, output,
+                            grad_output, grad_input, grad_s_src, grad_s_dst,
+                            s_src, s_dst, slope, row_indices, column_offset,
+                            row_offset, column_indices, src_start, src_end,
+                            dst_start, dst_end, edges, feature_size, heads);
+}
+
+void nts_gat_backward_fused_plan(nts_vid feature_size, nts_vid heads,
+                                 unsigned elem_bytes,
+                                 unsigned row_alignment_bytes,
+                                 unsigned fp32_alignment_bytes,
+                                 nts_vid src_rows, nts_vid dst_rows,
+                                 nts_vid edges, int general, int *form,
+                                 int *cols_per_lane, int *lane_group,
+                                 int *slabs, int *grid_csr, int *grid_csc,
+                                 unsigned long long *scratch_bytes) {
+  check_heads("nts_gat_backward_fused_plan", feature_size, heads);
+  const GatBwdPlan p = plan_gat_backward(
+      feature_size, heads, elem_bytes, row_alignment_bytes,
+      fp32_alignment_bytes, src_rows, dst_rows, edges, general != 0);
+  if (form) *form = p.form;
+  if (cols_per_lane) *cols_per_lane = (int)p.R;
+  if (lane_group) *lane_group = (int)p.G;
+  if (slabs) *slabs = (int)p.slabs;
+  if (grid_csr) *grid_csr = (int)p.grid_csr;
+  if (grid_csc) *grid_csc = (int)p.grid_csc;
   if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
 }
 

@@ -49,6 +49,14 @@ weight recomputed in registers from the two scalars; it returns y alone and
 allocates nothing of size E.  GATv2Layer has no such form (its score needs
 the rows), and there is no dropout in infer.
 
+Training without per-edge state (GATLayer.forward_recompute, and `attend`
+with recompute=True): the forward is `infer` and keeps only (h, s_src, s_dst,
+y); the backward (nts_gat_backward_fused[_bf16]) reduces the denominators
+again, folds them with s_dst and D = grad_y . y into one 16-byte record per
+(destination, head) and recomputes every edge's weight in registers in one
+walk over the CSC (grad_s_dst) and one over the CSR (grad_h, grad_s_src).  A
+training step then allocates nothing of size E.  No dropout on this path.
+
 bfloat16 feature rows: `h` of GATLayer and `x_l` / `x_r` of GATv2Layer may be
 torch.bfloat16.  The f-wide passes then read 2-byte rows through the *_bf16
 entries (widened exactly in registers); attention scalars, `att`, every
@@ -238,7 +246,15 @@ class GATLayer(_EdgeLayer):
     def backward(self, grad_y: torch.Tensor, saved,
                  negative_slope: float = 0.2):
         """Returns (grad_h from the aggregation, grad_s_src[V], grad_s_dst[V]);
-        the two scalar gradients are [V, heads] for a multi-head layer."""
+        the two scalar gradients are [V, heads] for a multi-head layer.
+        A `saved` of forward_recompute runs the recomputing backward, with
+        the same shapes and dtypes."""
+        if saved.get("recompute"):
+            grad_h, g_src, g_dst = self._backward_recompute(
+                grad_y, saved, negative_slope)
+            if self.heads == 1:
+                return grad_h, g_src[:, 0], g_dst[:, 0]
+            return grad_h, g_src, g_dst
         if self._heads_path:
             return self._backward_heads(grad_y, saved, negative_slope)
         if saved["h"].dtype == torch.bfloat16:
@@ -397,6 +413,62 @@ class GATLayer(_EdgeLayer):
             ch.dst_e, E, ch.dst_n, f, K)
         return y
 
+    def forward_recompute(self, h: torch.Tensor, s_src: torch.Tensor,
+                          s_dst: torch.Tensor, negative_slope: float = 0.2):
+        """The forward for training without per-edge state: y of `infer`
+        and a `saved` of (h, s_src, s_dst, y) alone, from which `backward`
+        recomputes every attention weight (Stream.gat_backward_fused).
+        `backward` reads saved["y"], which is the returned tensor itself: do
+        not modify y in place before the backward (`attend` saves it through
+        autograd, which then raises).
+        Neither call allocates, writes or keeps an [E, K] tensor.  Inputs,
+        dtypes and checks as for `infer`; either softmax mode; no dropout.
+        A head wider than 1024 columns has no such backward: then this is
+        forward(h, s_src, s_dst, negative_slope)."""
+        ch, K = self.ch, self.heads
+        f = self._width("h", h)
+        elem = 2 if isinstance(h, torch.Tensor) and h.dtype == torch.bfloat16 \
+            else 4
+        if not shim.gat_backward_fused_plan(f, K, elem, 256, 256, ch.src_n,
+                                            ch.dst_n, self.E)["form"]:
+            return self.forward(h, s_src, s_dst, negative_slope)
+        y = self.infer(h, s_src, s_dst, negative_slope)
+        if K == 1:
+            s_src, s_dst = (t[:, None] if t.dim() == 1 else t
+                            for t in (s_src, s_dst))
+        return y, {"h": h, "s_src": s_src, "s_dst": s_dst, "y": y,
+                   "recompute": True}
+
+    def _backward_recompute(self, grad_y, saved, negative_slope):
+        """Returns (grad_h[V, K*C], g_src[V, K], g_dst[V, K]) from a `saved`
+        of forward_recompute."""
+        ch, st, E, K = self.ch, self.stream, self.E, self.heads
+        f = self._width("grad_y", grad_y)
+        self._check_rows("grad_y", grad_y, ch.dst_n, f)
+        h = saved["h"]
+        if tuple(h.shape) != (ch.src_n, f):
+            raise ValueError("grad_y does not match the saved forward input")
+        dev = grad_y.device
+        st.items_reuse(1)
+        grad_h = torch.zeros(ch.src_n, f, device=dev)
+        g_src = torch.zeros(ch.src_n, K, device=dev)
+        g_dst = torch.zeros(ch.dst_n, K, device=dev)
+        ran = (st.gat_backward_fused_bf16 if h.dtype == torch.bfloat16
+               else st.gat_backward_fused)(
+            h.data_ptr(), saved["y"].data_ptr(), grad_y.data_ptr(),
+            grad_h.data_ptr(), g_src.data_ptr(), g_dst.data_ptr(),
+            # the layer's s_src is indexed by the global source id, the
+            # entry's from src_s
+            saved["s_src"].data_ptr() + 4 * ch.src_s * K,
+            saved["s_dst"].data_ptr(),
+            negative_slope, ch.row_indices.data_ptr(),
+            ch.column_offset.data_ptr(), ch.row_offset.data_ptr(),
+            ch.column_indices.data_ptr(), ch.src_s, ch.src_e, ch.dst_s,
+            ch.dst_e, E, f, K)
+        if not ran:   # forward_recompute never saves such a width
+            raise RuntimeError("gat_backward_fused has no form for this width")
+        return grad_h, g_src, g_dst
+
     def _backward_heads(self, grad_y, saved, negative_slope):
         """Returns (grad_h[V, K*C], g_src[V, K], g_dst[V, K])."""
         ch, st, E, K = self.ch, self.stream, self.E, self.heads
@@ -458,23 +530,34 @@ class _AttendFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, s_src, s_dst, layer, negative_slope, dropout=0.0,
-                seed=0):
-        y, saved = layer.forward(h.detach().contiguous(),
-                                 s_src.detach().contiguous(),
-                                 s_dst.detach().contiguous(), negative_slope,
-                                 dropout, seed)
+                seed=0, recompute=False):
+        args = (h.detach().contiguous(), s_src.detach().contiguous(),
+                s_dst.detach().contiguous(), negative_slope)
+        if recompute:
+            y, saved = layer.forward_recompute(*args)
+            if saved.get("recompute"):
+                # the backward reads y: saved through autograd, so that an
+                # in-place change of attend's output raises there
+                saved = {k: t for k, t in saved.items() if k != "y"}
+                ctx.save_for_backward(y)
+        else:
+            y, saved = layer.forward(*args, dropout, seed)
         ctx.layer, ctx.saved, ctx.slope = layer, saved, negative_slope
         ctx.scalar_shapes = (s_src.shape, s_dst.shape)
         return y
 
     @staticmethod
     def backward(ctx, grad_y):
-        grad_h, g_src, g_dst = ctx.layer.backward(grad_y.contiguous(),
-                                                  ctx.saved, ctx.slope)
+        saved = ctx.saved
+        if saved.get("recompute"):
+            saved = dict(saved, y=ctx.saved_tensors[0])
+        grad_h, g_src, g_dst = ctx.layer.backward(grad_y.contiguous(), saved,
+                                                  ctx.slope)
         # fp32 out of the kernels; bf16 only if h itself was
         grad_h = grad_h.to(ctx.saved["h"].dtype)
         return (grad_h, g_src.reshape(ctx.scalar_shapes[0]),
-                g_dst.reshape(ctx.scalar_shapes[1]), None, None, None, None)
+                g_dst.reshape(ctx.scalar_shapes[1]), None, None, None, None,
+                None)
 
 
 def _draw_seed(dropout, seed):
@@ -492,7 +575,8 @@ def _draw_seed(dropout, seed):
 
 def attend(h: torch.Tensor, s_src: torch.Tensor, s_dst: torch.Tensor,
            layer: GATLayer, negative_slope: float = 0.2,
-           dropout: float = 0.0, seed=None) -> torch.Tensor:
+           dropout: float = 0.0, seed=None,
+           recompute: bool = False) -> torch.Tensor:
     """Autograd-aware attention-weighted aggregation on `layer`'s graph:
     y = layer.forward(h, s_src, s_dst), differentiable in all three.  The
     projections stay in torch, e.g. for K heads of C columns
@@ -502,11 +586,21 @@ def attend(h: torch.Tensor, s_src: torch.Tensor, s_dst: torch.Tensor,
     dropout, seed: attention dropout as for GATLayer.forward (pass 0.0 for
     evaluation); seed=None draws one from torch's default CPU generator.
     Under torch.no_grad() with dropout == 0 (evaluation) the call is
-    layer.infer: the same y, with no [E, K] tensor allocated or kept."""
+    layer.infer: the same y, with no [E, K] tensor allocated or kept.
+    recompute=True trains without per-edge state (GATLayer.forward_recompute
+    and its backward): the same y and gradients up to rounding, nothing of
+    size E allocated in either direction.  That path has no dropout:
+    recompute=True with dropout > 0 raises ValueError before any launch.
+    recompute=False makes exactly the calls described above."""
+    if recompute and dropout > 0:
+        raise ValueError("attend(recompute=True) has no attention dropout")
     if not torch.is_grad_enabled() and dropout == 0:
         _draw_seed(dropout, seed)   # the same argument checks
         return layer.infer(h.contiguous(), s_src.contiguous(),
                            s_dst.contiguous(), negative_slope)
+    if recompute:
+        return _AttendFn.apply(h, s_src, s_dst, layer, negative_slope, 0.0,
+                               _draw_seed(dropout, seed), True)
     return _AttendFn.apply(h, s_src, s_dst, layer, negative_slope, dropout,
                            _draw_seed(dropout, seed))
 

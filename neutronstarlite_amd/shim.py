@@ -152,6 +152,15 @@ def lib():
     l.nts_gatv2_forward_fused_bf16.restype = _i32
     l.nts_gatv2_forward_fused_plan.argtypes = (
         [_u32] * 2 + [_c.c_uint] * 3 + [_u32] * 2 + [_i32] + [_vp] * 6)
+    # fused GAT training backward (recomputed weights, no per-edge state)
+    l.nts_gat_backward_fused.argtypes = (
+        [_vp] + [_vp] * 8 + [_c.c_float] + [_vp] * 4 + [_u32] * 7)
+    l.nts_gat_backward_fused.restype = _i32
+    l.nts_gat_backward_fused_bf16.argtypes = (
+        l.nts_gat_backward_fused.argtypes)
+    l.nts_gat_backward_fused_bf16.restype = _i32
+    l.nts_gat_backward_fused_plan.argtypes = (
+        [_u32] * 2 + [_c.c_uint] * 3 + [_u32] * 3 + [_i32] + [_vp] * 7)
     l.nts_edge_softmax_stable.argtypes = [_vp, _i32]
     l.nts_edge_softmax_stable_last.argtypes = [_vp, _vp]
     # attention dropout
@@ -313,6 +322,30 @@ def gatv2_forward_fused_plan(f, heads, elem_bytes, row_alignment,
     lib().nts_gatv2_forward_fused_plan(
         f, heads, elem_bytes, row_alignment, fp32_alignment, batch, edges,
         1 if general else 0, *[_c.byref(o) for o in out], _c.byref(scratch))
+    plan = {n: o.value for n, o in zip(names, out)}
+    plan["scratch_bytes"] = scratch.value
+    return plan
+
+
+def gat_backward_fused_plan(f, heads, elem_bytes, row_alignment,
+                            fp32_alignment, src_rows, dst_rows, edges,
+                            general=False):
+    """The launch decision of Stream.gat_backward_fused[_bf16] (no device
+    access): dict of form (0 none: C > 1024, 1 fast, 2 general),
+    cols_per_lane, lane_group, slabs (tasks per item), grid_csr, grid_csc and
+    scratch_bytes (the 16-byte records, one per destination and head).
+    elem_bytes 4 or 2; row_alignment the alignment of h in bytes,
+    fp32_alignment the common one of grad_y and grad_h; general as under
+    Stream.heads_dbg_general."""
+    check_heads(f, heads)
+    names = ("form", "cols_per_lane", "lane_group", "slabs", "grid_csr",
+             "grid_csc")
+    out = [_i32(0) for _ in names]
+    scratch = _c.c_ulonglong(0)
+    lib().nts_gat_backward_fused_plan(
+        f, heads, elem_bytes, row_alignment, fp32_alignment, src_rows,
+        dst_rows, edges, 1 if general else 0, *[_c.byref(o) for o in out],
+        _c.byref(scratch))
     plan = {n: o.value for n, o in zip(names, out)}
     plan["scratch_bytes"] = scratch.value
     return plan
@@ -812,6 +845,40 @@ class Stream:
             self.h, _vp(x_l_bf16), _vp(x_r_bf16), _vp(y_ptr), _vp(att), slope,
             _vp(row_indices), _vp(column_offset), src_start, batch, edges, f,
             heads)
+
+    # ---- fused GAT training backward: the weights recomputed from the
+    # scalars, nothing kept per edge ----
+    def gat_backward_fused(self, x_ptr, y_ptr, grad_y, grad_x, grad_s_src,
+                           grad_s_dst, s_src, s_dst, slope, row_indices,
+                           column_offset, row_offset, column_indices, src_s,
+                           src_e, dst_s, dst_e, edges, f, heads):
+        """The backward of gat_forward_fused from its inputs (x, s_src,
+        s_dst, both indexed from src_s / dst_s) and its output y: grad_x,
+        grad_s_src and grad_s_dst are added to (the caller zeroes).  A
+        denominator pass, a 16-byte record per (destination, head), one walk
+        over the CSC and one over the CSR; nothing of size edges is
+        allocated.  Honours edge_softmax_stable.  Returns 1 when it ran (or
+        there was nothing to do), 0 when C > 1024: nothing was launched."""
+        check_heads(f, heads)
+        return self._lib.nts_gat_backward_fused(
+            self.h, _vp(x_ptr), _vp(y_ptr), _vp(grad_y), _vp(grad_x),
+            _vp(grad_s_src), _vp(grad_s_dst), _vp(s_src), _vp(s_dst), slope,
+            _vp(row_indices), _vp(column_offset), _vp(row_offset),
+            _vp(column_indices), src_s, src_e, dst_s, dst_e, edges, f, heads)
+
+    def gat_backward_fused_bf16(self, x_bf16, y_ptr, grad_y, grad_x,
+                                grad_s_src, grad_s_dst, s_src, s_dst, slope,
+                                row_indices, column_offset, row_offset,
+                                column_indices, src_s, src_e, dst_s, dst_e,
+                                edges, f, heads):
+        """gat_backward_fused over bfloat16 input rows (every gradient stays
+        float32)."""
+        check_heads(f, heads)
+        return self._lib.nts_gat_backward_fused_bf16(
+            self.h, _vp(x_bf16), _vp(y_ptr), _vp(grad_y), _vp(grad_x),
+            _vp(grad_s_src), _vp(grad_s_dst), _vp(s_src), _vp(s_dst), slope,
+            _vp(row_indices), _vp(column_offset), _vp(row_offset),
+            _vp(column_indices), src_s, src_e, dst_s, dst_e, edges, f, heads)
 
     # ---- max / min aggregation; op is checked here, the library aborts on
     # an invalid value ----

@@ -88,6 +88,25 @@ def edge_case_graph():
 
 
 @functools.lru_cache(maxsize=None)
+def grid_case_graph():
+    """The in-degrees, id range and size of edge_case_graph with sources
+    forced so that the walk by SOURCE has edge cases of its own (uniform
+    sources leave every out-degree under about 15): one source of 600
+    out-edges (three work items at the default split, the last short) and 80
+    sources of 12 to 20 out-edges each, on edge slots drawn without
+    replacement.  For tests/grid_cases.py; edge_case_graph itself is pinned
+    by other tests and stays as it is."""
+    base = edge_case_graph()
+    rng = np.random.default_rng(20242)
+    out_deg = np.concatenate([[600], rng.integers(12, 21, 80)])
+    slots = rng.permutation(base.edges)[:int(out_deg.sum())]
+    srcs = np.repeat(base.src_start + 7 * np.arange(len(out_deg)) + 5, out_deg)
+    forced = list(zip(slots.tolist(), srcs.tolist()))
+    return build_graph(base.deg, base.v_src, base.src_start, seed=20243,
+                       forced=forced)
+
+
+@functools.lru_cache(maxsize=None)
 def small_graph():
     """A second, smaller topology (40 destinations, one of them split)."""
     rng = np.random.default_rng(77)

@@ -1026,6 +1026,101 @@ void nts_gat_backward_fused_plan(nts_vid feature_size, nts_vid heads,
     int *lane_group, int *slabs, int *grid_csr, int *grid_csc,
     unsigned long long *scratch_bytes);
 
+/* ---- fused GATv2 training (additive): no per-edge state ----
+ * nts_gatv2_forward_fused_stats[_bf16] is nts_gatv2_forward_fused[_bf16]
+ * (same plan, same launches' arithmetic, output bit-identical) whose kernels
+ * also leave the softmax statistics of every destination that has in-edges in
+ * ms, [batch_size, heads, 2] fp32: ms[d, k] = (M, S) with S = sum over d's
+ * in-edges of exp(score - M), M the running maximum in the stable mode and
+ * exactly 0 in the default mode.  An unsplit destination's item stores its
+ * own pair; the merge kernel stores (M, den) of a split one.  ms of a
+ * destination without in-edges is never written (and never read below).  ms
+ * must not be NULL.
+ *   nts_gatv2_backward_fused[_bf16] is the backward for a caller that kept
+ * x_l, x_r, att, the forward's output y and ms.  Per edge e = (u -> d) and
+ * head k over the head's columns c (t one fp32 add, lrelu'(0) = slope):
+ *   t[c]    = x_l[u, c] + x_r[d, c]
+ *   score   = sum_c att[c] * lrelu(t[c])
+ *   alpha   = exp(score - M[d, k]) / S[d, k]
+ *   gdot    = sum_c grad_output[d, c] * x_l[u, c]
+ *   D[d, k] = sum_c grad_output[d, c] * output[d, c]
+ *   gs      = alpha * (gdot - D[d, k])
+ *   grad_x_r[d, c] += gs * att[c] * lrelu'(t[c])
+ *   grad_x_l[u, c] += alpha * grad_output[d, c] + gs * att[c] * lrelu'(t[c])
+ *   grad_att[c]    += gs * lrelu(t[c])
+ *   Three launches.  (1) A record pass (NTS_KTAG_EDGE) writes {M, S, D, -}
+ * per (d, k) with in-edges, 16 bytes, into the stream-owned record scratch of
+ * nts_gat_backward_fused.  (2) The CSC walk (NTS_KTAG_BWD) over the items of
+ * column_offset keeps x_r[d], grad_output[d], att and d's record in
+ * registers and gathers x_l[u] per in-edge: grad_x_r and grad_att.  (3) The
+ * CSR walk (NTS_KTAG_BWD) over the items of row_offset keeps x_l[u] and att in
+ * registers and gathers x_r[d], grad_output[d] and d's record (one 16-byte
+ * load) per out-edge: grad_x_l.  column_indices holds global destination ids
+ * (d = column_indices[e] - dst_start).  Nothing sized by `edges` is
+ * allocated, read or written besides the two index lists; no dropout.
+ *   Forms and geometry are those of nts_gatv2_forward_fused: fast (C a power
+ * of two, C / R <= 64; R = 4 / 2 / 1 the widest that divides C and that every
+ * pointer permits: R*4 bytes of alignment for grad_output, att, grad_x_l,
+ * grad_x_r and fp32 rows, R*2 for bf16 rows), where the partial score and the
+ * partial gdot of four edges in flight are summed over the head's C / R lanes
+ * by one interleaved butterfly; general (any heads, C <= 1024, and whenever
+ * nts_heads_dbg_general is set), a wave per (item, head).  A vertex that is
+ * one work item ends with a plain read-add-write; a split one adds by fp32
+ * atomics, one per (item, element), and needs no merge since every item holds
+ * the destination's whole (M, S, D).  grad_att: the CSC walk runs the column
+ * slab (general form: the head) as its outer loop, a lane carries its
+ * partials in registers over all its items, the workgroup sums them in LDS
+ * and one atomicAdd per (workgroup, column) reaches memory; its value is
+ * therefore not bit-reproducible.
+ *   All three gradients keep the += contract (the caller zeroes; rows without
+ * edges are untouched).  x_l is [src_end - src_start, feature_size], x_r
+ * [dst_end - dst_start, feature_size], both fp32 or both bf16 (raw uint16_t,
+ * widened exactly); att and grad_att [feature_size], output, grad_output and
+ * grad_x_r [dst rows, feature_size], grad_x_l [src rows, feature_size] and ms
+ * are fp32.  The softmax mode is the stream's (it must be the forward's) and
+ * the call is recorded for nts_edge_softmax_stable_last.  The edge count is
+ * the caller's: no device-to-host copy, no synchronize beyond scratch growth.
+ *   Returns 1 when the backward ran or there was nothing to do (edges == 0 or
+ * no rows on either side: nothing launched or written); 0 when C > 1024:
+ * nothing is launched or written.
+ *   nts_gatv2_backward_fused_plan reports the decision without touching a
+ * device, as nts_gat_backward_fused_plan does (grid_csc is sized by the items
+ * alone: that walk loops over the slabs itself).  row_alignment_bytes is the
+ * common alignment of x_l and x_r, fp32_alignment_bytes that of grad_output,
+ * att, grad_x_l and grad_x_r. */
+int nts_gatv2_forward_fused_stats(nts_stream *s, const float *x_l,
+    const float *x_r, float *output, const float *att, float slope,
+    const nts_vid *row_indices, const nts_vid *column_offset,
+    nts_vid src_start, nts_vid batch_size, nts_vid edges,
+    nts_vid feature_size, nts_vid heads, float *ms);
+int nts_gatv2_forward_fused_stats_bf16(nts_stream *s, const uint16_t *x_l,
+    const uint16_t *x_r, float *output, const float *att, float slope,
+    const nts_vid *row_indices, const nts_vid *column_offset,
+    nts_vid src_start, nts_vid batch_size, nts_vid edges,
+    nts_vid feature_size, nts_vid heads, float *ms);
+int nts_gatv2_backward_fused(nts_stream *s, const float *x_l,
+    const float *x_r, const float *att, const float *output, const float *ms,
+    const float *grad_output, float *grad_x_l, float *grad_x_r,
+    float *grad_att, float slope, const nts_vid *row_indices,
+    const nts_vid *column_offset, const nts_vid *row_offset,
+    const nts_vid *column_indices, nts_vid src_start, nts_vid src_end,
+    nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid feature_size,
+    nts_vid heads);
+int nts_gatv2_backward_fused_bf16(nts_stream *s, const uint16_t *x_l,
+    const uint16_t *x_r, const float *att, const float *output,
+    const float *ms, const float *grad_output, float *grad_x_l,
+    float *grad_x_r, float *grad_att, float slope, const nts_vid *row_indices,
+    const nts_vid *column_offset, const nts_vid *row_offset,
+    const nts_vid *column_indices, nts_vid src_start, nts_vid src_end,
+    nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid feature_size,
+    nts_vid heads);
+void nts_gatv2_backward_fused_plan(nts_vid feature_size, nts_vid heads,
+    unsigned elem_bytes, unsigned row_alignment_bytes,
+    unsigned fp32_alignment_bytes, nts_vid src_rows, nts_vid dst_rows,
+    nts_vid edges, int general, int *form, int *cols_per_lane,
+    int *lane_group, int *slabs, int *grid_csr, int *grid_csc,
+    unsigned long long *scratch_bytes);
+
 /* Opt-in work-item reuse: with enable=1 the stream caches its two most
  * recent item decompositions keyed on (offset pointer, batch, edges) and
  * skips identical rebuilds.  ONLY safe while the caller keeps those

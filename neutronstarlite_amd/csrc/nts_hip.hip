@@ -2424,14 +2424,14 @@ __device__ __forceinline__ void v2_edges_seg(float &m, float &S,
  * past the row's end are whole segments and take no part.  The lanes of a
  * segment share their task, hence every trip count, so the butterfly only
  * ever reads lanes that run with it. */
-template <int R, bool STABLE, typename T>
-NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_fused_seg(
+template <int R, bool STABLE, bool STATS, typename T>
+NTS_NO_PK __device__ __forceinline__ void gatv2_fused_seg(
     const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
     const uint32_t *__restrict__ nbr, const T *__restrict__ x_l,
     const T *__restrict__ x_r, const float *__restrict__ att,
     float *__restrict__ out, float *__restrict__ scratch, float slope,
     uint32_t nbr_start, uint32_t f, uint32_t K, uint32_t C, uint32_t G,
-    uint32_t n_slabs) {
+    uint32_t n_slabs, float *__restrict__ ms) {
   const uint32_t n_items = *n_items_p;
   const uint32_t glane = threadIdx.x & (G - 1);
   const uint32_t L = C / R;
@@ -2459,6 +2459,13 @@ NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_fused_seg(
 #pragma unroll
       for (int j = 0; j < R; ++j) acc[j] /= S;
       store_acc<R>(out + (uint64_t)im.v * f + col, acc, R, false);
+      if constexpr (STATS) {
+        if ((glane & (L - 1)) == 0) {
+          float *q = ms + 2 * ((uint64_t)im.v * K + col / C);
+          q[0] = m;
+          q[1] = S;
+        }
+      }
     } else {
       float *rec = scratch + (uint64_t)it * (f + 2 * K);
 #pragma unroll
@@ -2469,6 +2476,31 @@ NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_fused_seg(
       }
     }
   }
+}
+template <int R, bool STABLE, typename T>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_fused_seg(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ nbr, const T *__restrict__ x_l,
+    const T *__restrict__ x_r, const float *__restrict__ att,
+    float *__restrict__ out, float *__restrict__ scratch, float slope,
+    uint32_t nbr_start, uint32_t f, uint32_t K, uint32_t C, uint32_t G,
+    uint32_t n_slabs) {
+  gatv2_fused_seg<R, STABLE, false, T>(items, n_items_p, nbr, x_l, x_r, att,
+                                       out, scratch, slope, nbr_start, f, K, C,
+                                       G, n_slabs, nullptr);
+}
+/* the training twin: an unsplit item also leaves its (m, S) in ms[d, k] */
+template <int R, bool STABLE, typename T>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_fused_seg_stats(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ nbr, const T *__restrict__ x_l,
+    const T *__restrict__ x_r, const float *__restrict__ att,
+    float *__restrict__ out, float *__restrict__ scratch, float slope,
+    uint32_t nbr_start, uint32_t f, uint32_t K, uint32_t C, uint32_t G,
+    uint32_t n_slabs, float *__restrict__ ms) {
+  gatv2_fused_seg<R, STABLE, true, T>(items, n_items_p, nbr, x_l, x_r, att,
+                                      out, scratch, slope, nbr_start, f, K, C,
+                                      G, n_slabs, ms);
 }
 
 /* general form: NE consecutive edges of one (item, head) across the wave */
@@ -2505,13 +2537,14 @@ __device__ __forceinline__ void v2_edges_wave(float &m, float &S,
  * owns the head's columns l + 64*i, i < NCH (dead ones hold zeros and are
  * never stored); the score is a wave_sum.  NE = edges in flight, fewer at
  * the wide instantiations so that the rows stay in registers. */
-template <int NCH, bool STABLE, typename T>
-NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_fused_wave(
+template <int NCH, bool STABLE, bool STATS, typename T>
+NTS_NO_PK __device__ __forceinline__ void gatv2_fused_wave(
     const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
     const uint32_t *__restrict__ nbr, const T *__restrict__ x_l,
     const T *__restrict__ x_r, const float *__restrict__ att,
     float *__restrict__ out, float *__restrict__ scratch, float slope,
-    uint32_t nbr_start, uint32_t f, uint32_t K, uint32_t C) {
+    uint32_t nbr_start, uint32_t f, uint32_t K, uint32_t C,
+    float *__restrict__ ms) {
   constexpr int NE = NCH <= 4 ? 4 : 16 / NCH;
   const uint32_t n_items = *n_items_p;
   const WaveId w = wave_id();
@@ -2543,6 +2576,13 @@ NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_fused_wave(
 #pragma unroll
       for (int i = 0; i < NCH; ++i)
         if (w.lane + 64 * i < C) o[64 * i] += acc[i] / S;
+      if constexpr (STATS) {
+        if (w.lane == 0) {
+          float *q = ms + 2 * ((uint64_t)im.v * K + head);
+          q[0] = m;
+          q[1] = S;
+        }
+      }
     } else {
       float *rec = scratch + (uint64_t)it * (f + 2 * K);
 #pragma unroll
@@ -2555,17 +2595,41 @@ NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_fused_wave(
     }
   }
 }
+template <int NCH, bool STABLE, typename T>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_fused_wave(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ nbr, const T *__restrict__ x_l,
+    const T *__restrict__ x_r, const float *__restrict__ att,
+    float *__restrict__ out, float *__restrict__ scratch, float slope,
+    uint32_t nbr_start, uint32_t f, uint32_t K, uint32_t C) {
+  gatv2_fused_wave<NCH, STABLE, false, T>(items, n_items_p, nbr, x_l, x_r, att,
+                                          out, scratch, slope, nbr_start, f, K,
+                                          C, nullptr);
+}
+template <int NCH, bool STABLE, typename T>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_fused_wave_stats(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ nbr, const T *__restrict__ x_l,
+    const T *__restrict__ x_r, const float *__restrict__ att,
+    float *__restrict__ out, float *__restrict__ scratch, float slope,
+    uint32_t nbr_start, uint32_t f, uint32_t K, uint32_t C,
+    float *__restrict__ ms) {
+  gatv2_fused_wave<NCH, STABLE, true, T>(items, n_items_p, nbr, x_l, x_r, att,
+                                         out, scratch, slope, nbr_start, f, K,
+                                         C, ms);
+}
 
 /* The records of a split destination, merged by the wave that meets its
  * first item (shared && e0 == offset[v]): the n = ceil(deg / split) records
  * it .. it+n-1 are contiguous and in edge order in the item list.  One lane
  * per column:  M = max m_i,  y = sum_i exp(m_i - M) acc_i / sum_i exp(m_i -
  * M) S_i,  out += y.  Default-mode records carry m = 0 and exp(0) = 1. */
-NTS_NO_PK __global__ void k_gatv2_fused_merge(
+template <bool STATS>
+NTS_NO_PK __device__ __forceinline__ void gatv2_fused_merge(
     const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
     const uint32_t *__restrict__ offset, const float *__restrict__ scratch,
     float *__restrict__ out, uint32_t split, uint32_t f, uint32_t K,
-    uint32_t C) {
+    uint32_t C, float *__restrict__ stats) {
   const uint32_t n_items = *n_items_p;
   const WaveId w = wave_id();
   const uint64_t pitch = f + 2 * K;
@@ -2586,8 +2650,32 @@ NTS_NO_PK __global__ void k_gatv2_fused_merge(
         den = fmaf(r, ms[i * pitch + 1], den);
       }
       out[(uint64_t)im.v * f + c] += num / den;
+      if constexpr (STATS) {
+        if (c % C == 0) {
+          float *q = stats + 2 * ((uint64_t)im.v * K + c / C);
+          q[0] = M;
+          q[1] = den;
+        }
+      }
     }
   }
+}
+NTS_NO_PK __global__ void k_gatv2_fused_merge(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ offset, const float *__restrict__ scratch,
+    float *__restrict__ out, uint32_t split, uint32_t f, uint32_t K,
+    uint32_t C) {
+  gatv2_fused_merge<false>(items, n_items_p, offset, scratch, out, split, f, K,
+                           C, nullptr);
+}
+/* the training twin: (M, den) of the split destination into ms[d, k] */
+NTS_NO_PK __global__ void k_gatv2_fused_merge_stats(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ offset, const float *__restrict__ scratch,
+    float *__restrict__ out, uint32_t split, uint32_t f, uint32_t K,
+    uint32_t C, float *__restrict__ stats) {
+  gatv2_fused_merge<true>(items, n_items_p, offset, scratch, out, split, f, K,
+                          C, stats);
 }
 
 /* ---- GAT training backward that recomputes the attention weights ---- */
@@ -2955,6 +3043,374 @@ __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_backward(
             sum[j] += part[(g * G + threadIdx.x) * R + j];
 #pragma unroll
         for (int j = 0; j < R; ++j) atomicAdd(&grad_att[col + j], sum[j]);
+      }
+      __syncthreads();
+    }
+  }
+}
+
+/* ---- GATv2 training backward that recomputes the attention weights ---- */
+/* A GATv2 score is a function of the two rows, so with (M, S) per
+ * (destination, head) from the stats forward and D[d, k] = grad_y[d] . y[d]
+ * over the head's columns, an edge's alpha = exp(score - M) / S and
+ * gs = alpha * (gdot - D) (the softmax backward) are recomputed from the rows
+ * the walks gather anyway; nothing per edge is read or written:
+ *   CSC walk (items of column_offset): x_r[d], grad_y[d], att and d's record
+ *     in registers, x_l[u] gathered (its only row gather): grad_x_r[d] +=
+ *     att * sum gs*lrelu'(t), grad_att += sum gs*lrelu(t);
+ *   CSR walk (items of row_offset): x_l[u] and att in registers, x_r[d],
+ *     grad_y[d] and d's record gathered: grad_x_l[u] += sum alpha*grad_y[d] +
+ *     att * sum gs*lrelu'(t).
+ * The partial score and the partial gdot of up to four edges in flight are
+ * summed over the head's lanes by ONE interleaved butterfly (2*NE independent
+ * exchanges per step).  A split item needs no merge: it holds the whole
+ * destination's (M, S, D) and adds its share by atomics.
+ *   grad_att as in k_gatv2_backward: in the CSC walk the column slab (wave
+ * form: the head) is the outer loop and the items the inner one, so a lane
+ * carries its grad_att partials in registers across all its items, the
+ * workgroup meets in LDS and one atomicAdd per (workgroup, column) reaches
+ * memory.  The CSR walk has no such sum and flattens (item, slab) tasks.
+ *   Built without packed fp32 instructions, as the fused forward. */
+
+/* {M, S, D, -} of one (destination, head); a destination without in-edges
+ * gets no record (its ms was never written, and no edge asks for it) */
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_bwd_record(
+    const float *__restrict__ gy, const float *__restrict__ y,
+    const float *__restrict__ ms, const uint32_t *__restrict__ offset,
+    float4 *__restrict__ recs, uint32_t rows, uint32_t f, uint32_t K,
+    uint32_t C, uint32_t G) {
+  const uint32_t glane = threadIdx.x & (G - 1);
+  const uint64_t total = (uint64_t)rows * K;
+  const uint64_t stride = (gridDim.x * NTS_BLOCK) / G;
+  /* a group of G lanes per (destination, head): lanes stride the head's C
+   * columns, seg_sum over the group (k_gat_bwd_record's D) */
+  for (uint64_t t = (blockIdx.x * NTS_BLOCK + threadIdx.x) / G; t < total;
+       t += stride) {
+    const uint32_t d = (uint32_t)(t / K);
+    if (offset[d + 1] == offset[d]) continue;   /* the whole group leaves */
+    const uint64_t base = (uint64_t)d * f + (t % K) * C;
+    float dot = 0.f;
+    for (uint32_t c = glane; c < C; c += G)
+      dot = fmaf(gy[base + c], y[base + c], dot);
+    dot = seg_sum(dot, G);
+    if (glane == 0) recs[t] = make_float4(ms[2 * t], ms[2 * t + 1], dot, 0.f);
+  }
+}
+
+/* one walk.  CSC: own = x_r, rows = x_l, grad_own = grad_x_r; CSR: own =
+ * x_l, rows = x_r, grad_own = grad_x_l; gy and recs are indexed by the
+ * destination, which is the item's vertex (CSC) or the neighbour (CSR) */
+template <typename T>
+struct V2Bwd {
+  const uint32_t *__restrict__ nbr;
+  const T *__restrict__ own;
+  const T *__restrict__ rows;
+  const float *__restrict__ gy;
+  const float *__restrict__ att;
+  const float4 *__restrict__ recs;
+  float *__restrict__ grad_own;
+  float *__restrict__ grad_att;   /* CSC only */
+  float slope;
+  uint32_t nbr_start, f, K, C;
+};
+
+/* alpha and gs of NE edges from the head's scores and dots */
+template <int NE, bool STABLE>
+__device__ __forceinline__ void v2b_weights(float (&alpha)[NE], float (&gs)[NE],
+                                            const float (&sc)[NE],
+                                            const float (&gd)[NE],
+                                            const float4 (&rec)[NE]) {
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    alpha[k] = (STABLE ? __expf(sc[k] - rec[k].x) : __expf(sc[k])) / rec[k].y;
+    gs[k] = alpha[k] * (gd[k] - rec[k].z);
+  }
+}
+
+/* NE consecutive edges of one (item, lane's N columns).  LOAD(p, x) fills the
+ * lane's N columns from the row pointer p, SUM2 sums the NE partial scores
+ * and dots over the head's lanes.  CSC: a1 = sum gs*lrelu'(t), a2 = sum
+ * gs*lrelu(t) (grad_att).  CSR: a1 = sum alpha*grad_y, a2 = sum gs*lrelu'(t). */
+template <int N, int NE, bool STABLE, bool CSR, typename T, class Load,
+          class Sum2>
+__device__ __forceinline__ void v2b_edges(float (&a1)[N], float (&a2)[N],
+                                          const V2Bwd<T> &g, uint32_t e,
+                                          uint32_t col, uint32_t head,
+                                          const float (&own)[N],
+                                          const float (&gyo)[N],
+                                          const float (&av)[N],
+                                          const float4 &rec_own,
+                                          const Load &load, const Sum2 &sum2) {
+  uint32_t n[NE];
+  float xv[NE][N], gv[CSR ? NE : 1][N], sc[NE], gd[NE], alpha[NE], gs[NE];
+  float4 rec[NE];
+#pragma unroll
+  for (int k = 0; k < NE; ++k) n[k] = g.nbr[e + k] - g.nbr_start;
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    load(g.rows + (uint64_t)n[k] * g.f + col, xv[k]);
+    if constexpr (CSR) {
+      load(g.gy + (uint64_t)n[k] * g.f + col, gv[k]);
+      rec[k] = g.recs[(uint64_t)n[k] * g.K + head];
+    } else {
+      rec[k] = rec_own;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    sc[k] = gd[k] = 0.f;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      /* t = x_l + x_r, one fp32 add; the score term of Gatv2Term */
+      sc[k] = fmaf(av[j], lrelu(own[j] + xv[k][j], g.slope), sc[k]);
+      /* gdot = grad_y[d] . x_l[u] */
+      if constexpr (CSR) gd[k] = fmaf(gv[k][j], own[j], gd[k]);
+      else gd[k] = fmaf(gyo[j], xv[k][j], gd[k]);
+    }
+  }
+  sum2(sc, gd);
+  v2b_weights<NE, STABLE>(alpha, gs, sc, gd, rec);
+#pragma unroll
+  for (int k = 0; k < NE; ++k)
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const float t = own[j] + xv[k][j];
+      const float dl = gs[k] * (t > 0.f ? 1.f : g.slope);
+      if constexpr (CSR) {
+        a1[j] = fmaf(alpha[k], gv[k][j], a1[j]);
+        a2[j] += dl;
+      } else {
+        a1[j] += dl;
+        a2[j] = fmaf(gs[k], lrelu(t, g.slope), a2[j]);
+      }
+    }
+}
+
+/* all edges of one item into (a1, a2), NE at a time and then one by one */
+template <int N, int NE, bool STABLE, bool CSR, typename T, class Load,
+          class Sum2>
+__device__ __forceinline__ void v2b_item(float (&a1)[N], float (&a2)[N],
+                                         const V2Bwd<T> &g, const Item &im,
+                                         uint32_t col, uint32_t head,
+                                         const float (&own)[N],
+                                         const float (&av)[N],
+                                         const Load &load, const Sum2 &sum2) {
+  float gyo[N] = {};
+  float4 rec_own = make_float4(0.f, 1.f, 0.f, 0.f);
+  if constexpr (!CSR) {
+    load(g.gy + (uint64_t)im.v * g.f + col, gyo);
+    rec_own = g.recs[(uint64_t)im.v * g.K + head];
+  }
+  const uint32_t e_end = im.e0 + im.cnt;
+  uint32_t e = im.e0;
+  for (; e + NE <= e_end; e += NE)
+    v2b_edges<N, NE, STABLE, CSR>(a1, a2, g, e, col, head, own, gyo, av,
+                                  rec_own, load, sum2);
+  for (; e < e_end; ++e)
+    v2b_edges<N, 1, STABLE, CSR>(a1, a2, g, e, col, head, own, gyo, av,
+                                 rec_own, load, sum2);
+}
+
+/* fast form: a lane's R consecutive columns, the head's L lanes */
+template <int R>
+struct V2bLoadSeg {
+  template <typename P>
+  __device__ __forceinline__ void operator()(const P *p, float (&x)[R]) const {
+    load_cols<R>(p, x);
+  }
+};
+struct V2bSumSeg {
+  uint32_t L;
+  template <int NE>
+  __device__ __forceinline__ void operator()(float (&sc)[NE],
+                                             float (&gd)[NE]) const {
+    for (uint32_t w = L >> 1; w >= 1; w >>= 1)
+#pragma unroll
+      for (int k = 0; k < NE; ++k) {
+        sc[k] += __shfl_xor(sc[k], w, 64);
+        gd[k] += __shfl_xor(gd[k], w, 64);
+      }
+  }
+};
+
+/* one (item, slab) task of the fast form: returns through datt (CSC) */
+template <int R, bool STABLE, bool CSR, typename T>
+__device__ __forceinline__ void v2b_seg_task(const V2Bwd<T> &g, const Item &im,
+                                             uint32_t col, uint32_t L,
+                                             const float (&av)[R],
+                                             float (&datt)[R]) {
+  const uint32_t head = col / g.C;
+  float own[R], a1[R] = {};
+  load_cols<R>(g.own + (uint64_t)im.v * g.f + col, own);
+  if constexpr (CSR) {
+    float a2[R] = {};
+    v2b_item<R, 4, STABLE, true>(a1, a2, g, im, col, head, own, av,
+                                 V2bLoadSeg<R>{}, V2bSumSeg{L});
+#pragma unroll
+    for (int j = 0; j < R; ++j) a1[j] = fmaf(av[j], a2[j], a1[j]);
+  } else {
+    v2b_item<R, 4, STABLE, false>(a1, datt, g, im, col, head, own, av,
+                                  V2bLoadSeg<R>{}, V2bSumSeg{L});
+#pragma unroll
+    for (int j = 0; j < R; ++j) a1[j] *= av[j];
+  }
+  store_acc<R>(g.grad_own + (uint64_t)im.v * g.f + col, a1, R, im.shared);
+}
+
+/* Fast form, C a power of two and L = C/R <= 64: the geometry of
+ * k_gatv2_fused_seg (G lanes per task, a lane R consecutive columns of one
+ * head, slabs of whole heads, lanes past the row's end whole segments that
+ * take no part).  CSR: tasks (item, slab) flattened.  CSC: slab outer, the
+ * group's items inner, grad_att through LDS. */
+template <int R, bool STABLE, bool CSR, typename T>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_bwd_seg(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const V2Bwd<T> g, uint32_t G, uint32_t n_slabs) {
+  __shared__ float part[CSR ? 1 : NTS_BLOCK * R];
+  const uint32_t n_items = *n_items_p;
+  const uint32_t glane = threadIdx.x & (G - 1);
+  const uint32_t L = g.C / R;
+  const uint32_t group = (blockIdx.x * NTS_BLOCK + threadIdx.x) / G;
+  const uint32_t n_groups = (gridDim.x * NTS_BLOCK) / G;
+  if constexpr (CSR) {
+    const uint64_t total = (uint64_t)n_items * n_slabs;
+    for (uint64_t t = group; t < total; t += n_groups) {
+      const uint32_t col = (uint32_t)(t % n_slabs) * G * R + glane * R;
+      if (col >= g.f) continue;
+      float av[R], none[R];
+      load_cols<R>(g.att + col, av);
+      v2b_seg_task<R, STABLE, true>(g, load_item(items, (uint32_t)(t / n_slabs)),
+                                    col, L, av, none);
+    }
+  } else {
+    for (uint32_t slab = 0; slab < n_slabs; ++slab) {
+      const uint32_t col = slab * G * R + glane * R;
+      const bool live = col < g.f;
+      float datt[R] = {};
+      if (live) {
+        float av[R];
+        load_cols<R>(g.att + col, av);
+        for (uint32_t it = group; it < n_items; it += n_groups)
+          v2b_seg_task<R, STABLE, false>(g, load_item(items, it), col, L, av,
+                                         datt);
+      }
+      /* every thread of the workgroup arrives: the slab loop is uniform */
+#pragma unroll
+      for (int j = 0; j < R; ++j) part[threadIdx.x * R + j] = datt[j];
+      __syncthreads();
+      if (threadIdx.x < G && live) {
+        float sum[R] = {};
+        for (uint32_t q = 0; q < NTS_BLOCK / G; ++q)
+#pragma unroll
+          for (int j = 0; j < R; ++j)
+            sum[j] += part[(q * G + threadIdx.x) * R + j];
+#pragma unroll
+        for (int j = 0; j < R; ++j) atomicAdd(&g.grad_att[col + j], sum[j]);
+      }
+      __syncthreads();
+    }
+  }
+}
+
+/* general form: lane l owns the head's columns l + 64*i, i < NCH */
+template <int NCH>
+struct V2bLoadWave {
+  uint32_t lane, C;
+  template <typename P>
+  __device__ __forceinline__ void operator()(const P *p,
+                                             float (&x)[NCH]) const {
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+      x[i] = (lane + 64 * i < C) ? to_f32(p[64 * i]) : 0.f;
+  }
+};
+struct V2bSumWave {
+  template <int NE>
+  __device__ __forceinline__ void operator()(float (&sc)[NE],
+                                             float (&gd)[NE]) const {
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1)
+#pragma unroll
+      for (int k = 0; k < NE; ++k) {
+        sc[k] += __shfl_xor(sc[k], w, 64);
+        gd[k] += __shfl_xor(gd[k], w, 64);
+      }
+  }
+};
+
+/* one (item, head) task of the general form; dead columns hold zeros (att
+ * too, so they add nothing to the score or the dot) and are never stored */
+template <int NCH, bool STABLE, bool CSR, typename T>
+__device__ __forceinline__ void v2b_wave_task(const V2Bwd<T> &g,
+                                              const Item &im, uint32_t head,
+                                              uint32_t lane,
+                                              const float (&av)[NCH],
+                                              float (&datt)[NCH]) {
+  constexpr int NE = NCH <= 4 ? 4 : 16 / NCH;
+  const uint32_t col = head * g.C + lane;
+  const V2bLoadWave<NCH> load{lane, g.C};
+  float own[NCH], a1[NCH] = {};
+  load(g.own + (uint64_t)im.v * g.f + col, own);
+  if constexpr (CSR) {
+    float a2[NCH] = {};
+    v2b_item<NCH, NE, STABLE, true>(a1, a2, g, im, col, head, own, av, load,
+                                    V2bSumWave{});
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) a1[i] = fmaf(av[i], a2[i], a1[i]);
+  } else {
+    v2b_item<NCH, NE, STABLE, false>(a1, datt, g, im, col, head, own, av, load,
+                                     V2bSumWave{});
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) a1[i] *= av[i];
+  }
+  float *op = g.grad_own + (uint64_t)im.v * g.f + col;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i)
+    if (lane + 64 * i < g.C) {
+      if (im.shared) atomicAdd(&op[64 * i], a1[i]);
+      else op[64 * i] += a1[i];
+    }
+}
+
+/* General form, any K and C <= 64*NCH: a wave per (item, head).  CSR: tasks
+ * flattened.  CSC: head outer, the wave's items inner; the workgroup's four
+ * waves then meet in LDS for grad_att. */
+template <int NCH, bool STABLE, bool CSR, typename T>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_bwd_wave(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const V2Bwd<T> g) {
+  __shared__ float part[CSR ? 1 : NTS_BLOCK * NCH];
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  if constexpr (CSR) {
+    const uint64_t total = (uint64_t)n_items * g.K;
+    for (uint64_t t = w.wave; t < total; t += w.n_waves) {
+      const uint32_t head = (uint32_t)(t % g.K);
+      float av[NCH], none[NCH];
+      V2bLoadWave<NCH>{w.lane, g.C}(g.att + head * g.C + w.lane, av);
+      v2b_wave_task<NCH, STABLE, true>(g, load_item(items, (uint32_t)(t / g.K)),
+                                       head, w.lane, av, none);
+    }
+  } else {
+    for (uint32_t head = 0; head < g.K; ++head) {
+      float av[NCH], datt[NCH] = {};
+      V2bLoadWave<NCH>{w.lane, g.C}(g.att + head * g.C + w.lane, av);
+      for (uint32_t it = w.wave; it < n_items; it += w.n_waves)
+        v2b_wave_task<NCH, STABLE, false>(g, load_item(items, it), head,
+                                          w.lane, av, datt);
+      /* every thread of the workgroup arrives: the head loop is uniform */
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) part[threadIdx.x * NCH + i] = datt[i];
+      __syncthreads();
+      if (threadIdx.x < 64) {
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+          float sum = 0.f;
+          for (uint32_t q = 0; q < NTS_BLOCK / 64; ++q)
+            sum += part[(q * 64 + threadIdx.x) * NCH + i];
+          if (threadIdx.x + 64 * i < g.C)
+            atomicAdd(&g.grad_att[head * g.C + threadIdx.x + 64 * i], sum);
+        }
       }
       __syncthreads();
     }
@@ -5069,13 +5525,60 @@ static float *get_v2_scratch(nts_stream *s, uint64_t bytes) {
   return s->v2_ws;
 }
 
+/* the launches of the stats entries: the twins that also store (M, S) */
+template <typename T>
+static void launch_gatv2_fused_stats(nts_stream *s, const Gatv2FusedPlan &pl,
+                                     const EdgeItems &p, const T *x_l,
+                                     const T *x_r, float *out,
+                                     const float *att, float *scratch,
+                                     float slope, const nts_vid *row_indices,
+                                     const nts_vid *offset, nts_vid src_start,
+                                     nts_vid f, nts_vid K, float *ms) {
+  const bool st = s->softmax_stable;
+  const uint32_t C = f / K;
+  if (pl.form == 1) {
+#define NTS_K(RR)                                                             \
+  (st ? k_gatv2_fused_seg_stats<RR, true, T>                                  \
+      : k_gatv2_fused_seg_stats<RR, false, T>)
+    hipLaunchKernelGGL(pl.R == 4 ? NTS_K(4) : pl.R == 2 ? NTS_K(2) : NTS_K(1),
+                       dim3(pl.grid), dim3(NTS_BLOCK), 0, s->stream,
+                       p.ib->items, p.ib->counter, row_indices, x_l, x_r, att,
+                       out, scratch, slope, src_start, f, K, C, pl.G,
+                       pl.slabs, ms);
+#undef NTS_K
+  } else {
+    /* indexed by log2(NCH) */
+    static const decltype(&k_gatv2_fused_wave_stats<1, false, T>)
+        kernels[2][5] = {{k_gatv2_fused_wave_stats<1, false, T>,
+                          k_gatv2_fused_wave_stats<2, false, T>,
+                          k_gatv2_fused_wave_stats<4, false, T>,
+                          k_gatv2_fused_wave_stats<8, false, T>,
+                          k_gatv2_fused_wave_stats<16, false, T>},
+                         {k_gatv2_fused_wave_stats<1, true, T>,
+                          k_gatv2_fused_wave_stats<2, true, T>,
+                          k_gatv2_fused_wave_stats<4, true, T>,
+                          k_gatv2_fused_wave_stats<8, true, T>,
+                          k_gatv2_fused_wave_stats<16, true, T>}};
+    hipLaunchKernelGGL(kernels[st][__builtin_ctz(pl.nch)], dim3(pl.grid),
+                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                       p.ib->counter, row_indices, x_l, x_r, att, out, scratch,
+                       slope, src_start, f, K, C, ms);
+  }
+  if (scratch)
+    hipLaunchKernelGGL(k_gatv2_fused_merge_stats, dim3(p.grid),
+                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                       p.ib->counter, offset, scratch, out, NTS_SPLIT, f, K, C,
+                       ms);
+}
+
+/* ms != nullptr: the stats entries */
 template <typename T>
 static int gatv2_forward_fused(nts_stream *s, const char *entry, const T *x_l,
                                const T *x_r, float *out, const float *att,
                                float slope, const nts_vid *row_indices,
                                const nts_vid *offset, nts_vid src_start,
                                nts_vid batch, nts_vid edges, nts_vid f,
-                               nts_vid K) {
+                               nts_vid K, float *ms = nullptr) {
   check_heads(entry, f, K);
   s->softmax_stable_last = s->softmax_stable;
   if (!batch || !edges) return 1;
@@ -5089,6 +5592,12 @@ static int gatv2_forward_fused(nts_stream *s, const char *entry, const T *x_l,
   const bool st = s->softmax_stable;
   const uint32_t C = f / K;
   Tic t(s, NTS_KTAG_FWD);
+  if (ms) {
+    launch_gatv2_fused_stats(s, pl, p, x_l, x_r, out, att, scratch, slope,
+                             row_indices, offset, src_start, f, K, ms);
+    dbg_sync(s, "k_gatv2_fused (stats)");
+    return 1;
+  }
   if (pl.form == 1) {
 #define NTS_K(RR)                                                             \
   (st ? k_gatv2_fused_seg<RR, true, T> : k_gatv2_fused_seg<RR, false, T>)
@@ -5143,6 +5652,34 @@ int nts_gatv2_forward_fused_bf16(nts_stream *s, const uint16_t *x_l,
   return gatv2_forward_fused(s, "nts_gatv2_forward_fused_bf16", x_l, x_r,
                              output, att, slope, row_indices, column_offset,
                              src_start, batch_size, edges, feature_size, heads);
+}
+
+int nts_gatv2_forward_fused_stats(nts_stream *s, const float *x_l,
+                                  const float *x_r, float *output,
+                                  const float *att, float slope,
+                                  const nts_vid *row_indices,
+                                  const nts_vid *column_offset,
+                                  nts_vid src_start, nts_vid batch_size,
+                                  nts_vid edges, nts_vid feature_size,
+                                  nts_vid heads, float *ms) {
+  return gatv2_forward_fused(s, "nts_gatv2_forward_fused_stats", x_l, x_r,
+                             output, att, slope, row_indices, column_offset,
+                             src_start, batch_size, edges, feature_size, heads,
+                             ms);
+}
+
+int nts_gatv2_forward_fused_stats_bf16(nts_stream *s, const uint16_t *x_l,
+                                       const uint16_t *x_r, float *output,
+                                       const float *att, float slope,
+                                       const nts_vid *row_indices,
+                                       const nts_vid *column_offset,
+                                       nts_vid src_start, nts_vid batch_size,
+                                       nts_vid edges, nts_vid feature_size,
+                                       nts_vid heads, float *ms) {
+  return gatv2_forward_fused(s, "nts_gatv2_forward_fused_stats_bf16", x_l, x_r,
+                             output, att, slope, row_indices, column_offset,
+                             src_start, batch_size, edges, feature_size, heads,
+                             ms);
 }
 
 void nts_gatv2_forward_fused_plan(nts_vid feature_size, nts_vid heads,
@@ -5371,6 +5908,163 @@ void nts_gat_backward_fused_plan(nts_vid feature_size, nts_vid heads,
                                  unsigned long long *scratch_bytes) {
   check_heads("nts_gat_backward_fused_plan", feature_size, heads);
   const GatBwdPlan p = plan_gat_backward(
+      feature_size, heads, elem_bytes, row_alignment_bytes,
+      fp32_alignment_bytes, src_rows, dst_rows, edges, general != 0);
+  if (form) *form = p.form;
+  if (cols_per_lane) *cols_per_lane = (int)p.R;
+  if (lane_group) *lane_group = (int)p.G;
+  if (slabs) *slabs = (int)p.slabs;
+  if (grid_csr) *grid_csr = (int)p.grid_csr;
+  if (grid_csc) *grid_csc = (int)p.grid_csc;
+  if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+}
+
+/* ---- fused GATv2 training backward (additive; see include/nts_hip.h) ---- */
+extern "C++" {
+/* plan_gat_backward's geometry; the CSC walk loops over the slabs (heads)
+ * itself, so its grid is sized by the items alone */
+static GatBwdPlan plan_gatv2_backward(uint32_t f, uint32_t K,
+                                      uint32_t elem_bytes,
+                                      uintptr_t row_alignment,
+                                      uintptr_t fp32_alignment,
+                                      uint32_t src_rows, uint32_t dst_rows,
+                                      uint32_t edges, bool general) {
+  GatBwdPlan p = plan_gat_backward(f, K, elem_bytes, row_alignment,
+                                   fp32_alignment, src_rows, dst_rows, edges,
+                                   general);
+  if (p.form)
+    p.grid_csc =
+        grid_for(((uint64_t)dst_rows + edges / NTS_SPLIT + 1) * p.G);
+  return p;
+}
+
+template <bool CSR, typename T>
+static void launch_gatv2_bwd_walk(nts_stream *s, const EdgeItems &p,
+                                  const GatBwdPlan &pl, uint32_t grid,
+                                  const V2Bwd<T> &g) {
+  const bool st = s->softmax_stable;
+  if (pl.form == 1) {
+#define NTS_K(RR)                                                             \
+  (st ? k_gatv2_bwd_seg<RR, true, CSR, T> : k_gatv2_bwd_seg<RR, false, CSR, T>)
+    hipLaunchKernelGGL(pl.R == 4 ? NTS_K(4) : pl.R == 2 ? NTS_K(2) : NTS_K(1),
+                       dim3(grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                       p.ib->counter, g, pl.G, pl.slabs);
+#undef NTS_K
+  } else {
+    /* indexed by log2(NCH) */
+    static const decltype(&k_gatv2_bwd_wave<1, false, CSR, T>) kernels[2][5] =
+        {{k_gatv2_bwd_wave<1, false, CSR, T>, k_gatv2_bwd_wave<2, false, CSR, T>,
+          k_gatv2_bwd_wave<4, false, CSR, T>, k_gatv2_bwd_wave<8, false, CSR, T>,
+          k_gatv2_bwd_wave<16, false, CSR, T>},
+         {k_gatv2_bwd_wave<1, true, CSR, T>, k_gatv2_bwd_wave<2, true, CSR, T>,
+          k_gatv2_bwd_wave<4, true, CSR, T>, k_gatv2_bwd_wave<8, true, CSR, T>,
+          k_gatv2_bwd_wave<16, true, CSR, T>}};
+    hipLaunchKernelGGL(kernels[st][__builtin_ctz(pl.nch)], dim3(grid),
+                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                       p.ib->counter, g);
+  }
+}
+
+/* The record pass under NTS_KTAG_EDGE, the two walks under NTS_KTAG_BWD.
+ * Everything over the CSC items runs before the CSR items are asked for: the
+ * stream keeps two item buffers and a third request may rebuild the first. */
+template <typename T>
+static int gatv2_backward_fused(nts_stream *s, const char *entry, const T *x_l,
+                                const T *x_r, const float *att, const float *y,
+                                const float *ms, const float *gy,
+                                float *grad_x_l, float *grad_x_r,
+                                float *grad_att, float slope,
+                                const nts_vid *row_indices,
+                                const nts_vid *column_offset,
+                                const nts_vid *row_offset,
+                                const nts_vid *column_indices,
+                                nts_vid src_start, nts_vid src_end,
+                                nts_vid dst_start, nts_vid dst_end,
+                                nts_vid edges, nts_vid f, nts_vid K) {
+  check_heads(entry, f, K);
+  s->softmax_stable_last = s->softmax_stable;
+  const uint32_t src_rows = src_end > src_start ? src_end - src_start : 0;
+  const uint32_t dst_rows = dst_end > dst_start ? dst_end - dst_start : 0;
+  if (!edges || !src_rows || !dst_rows) return 1;
+  const GatBwdPlan pl = plan_gatv2_backward(
+      f, K, sizeof(T), (uintptr_t)x_l | (uintptr_t)x_r,
+      (uintptr_t)gy | (uintptr_t)att | (uintptr_t)grad_x_l |
+          (uintptr_t)grad_x_r,
+      src_rows, dst_rows, edges, s->heads_general);
+  if (!pl.form) return 0;
+  const uint32_t C = f / K;
+  const EdgeItems csc = edge_items_known(s, column_offset, dst_rows, edges);
+  float4 *recs = get_rec_scratch(s, pl.scratch_bytes);
+  {
+    Tic t(s, NTS_KTAG_EDGE);
+    uint32_t G = 1;
+    while (G < C && G < 64) G *= 2;
+    hipLaunchKernelGGL(k_gatv2_bwd_record,
+                       dim3(grid_for((uint64_t)dst_rows * K * G)),
+                       dim3(NTS_BLOCK), 0, s->stream, gy, y, ms, column_offset,
+                       recs, dst_rows, f, K, C, G);
+    dbg_sync(s, "k_gatv2_bwd_record");
+  }
+  {
+    Tic t(s, NTS_KTAG_BWD);
+    launch_gatv2_bwd_walk<false>(
+        s, csc, pl, pl.grid_csc,
+        V2Bwd<T>{row_indices, x_r, x_l, gy, att, recs, grad_x_r, grad_att,
+                 slope, src_start, f, K, C});
+    dbg_sync(s, "k_gatv2_bwd (CSC walk)");
+  }
+  const EdgeItems csr = edge_items_known(s, row_offset, src_rows, edges);
+  Tic t(s, NTS_KTAG_BWD);
+  launch_gatv2_bwd_walk<true>(
+      s, csr, pl, pl.grid_csr,
+      V2Bwd<T>{column_indices, x_l, x_r, gy, att, recs, grad_x_l, nullptr,
+               slope, dst_start, f, K, C});
+  dbg_sync(s, "k_gatv2_bwd (CSR walk)");
+  return 1;
+}
+}  // extern "C++"
+
+int nts_gatv2_backward_fused(
+    nts_stream *s, const float *x_l, const float *x_r, const float *att,
+    const float *output, const float *ms, const float *grad_output,
+    float *grad_x_l, float *grad_x_r, float *grad_att, float slope,
+    const nts_vid *row_indices, const nts_vid *column_offset,
+    const nts_vid *row_offset, const nts_vid *column_indices,
+    nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
+    nts_vid edges, nts_vid feature_size, nts_vid heads) {
+  return gatv2_backward_fused(s, "nts_gatv2_backward_fused", x_l, x_r, att,
+                              output, ms, grad_output, grad_x_l, grad_x_r,
+                              grad_att, slope, row_indices, column_offset,
+                              row_offset, column_indices, src_start, src_end,
+                              dst_start, dst_end, edges, feature_size, heads);
+}
+
+int nts_gatv2_backward_fused_bf16(
+    nts_stream *s, const uint16_t *x_l, const uint16_t *x_r, const float *att,
+    const float *output, const float *ms, const float *grad_output,
+    float *grad_x_l, float *grad_x_r, float *grad_att, float slope,
+    const nts_vid *row_indices, const nts_vid *column_offset,
+    const nts_vid *row_offset, const nts_vid *column_indices,
+    nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
+    nts_vid edges, nts_vid feature_size, nts_vid heads) {
+  return gatv2_backward_fused(s, "nts_gatv2_backward_fused_bf16", x_l, x_r,
+                              att, output, ms, grad_output, grad_x_l, grad_x_r,
+                              grad_att, slope, row_indices, column_offset,
+                              row_offset, column_indices, src_start, src_end,
+                              dst_start, dst_end, edges, feature_size, heads);
+}
+
+void nts_gatv2_backward_fused_plan(nts_vid feature_size, nts_vid heads,
+                                   unsigned elem_bytes,
+                                   unsigned row_alignment_bytes,
+                                   unsigned fp32_alignment_bytes,
+                                   nts_vid src_rows, nts_vid dst_rows,
+                                   nts_vid edges, int general, int *form,
+                                   int *cols_per_lane, int *lane_group,
+                                   int *slabs, int *grid_csr, int *grid_csc,
+                                   unsigned long long *scratch_bytes) {
+  check_heads("nts_gatv2_backward_fused_plan", feature_size, heads);
+  const GatBwdPlan p = plan_gatv2_backward(
       feature_size, heads, elem_bytes, row_alignment_bytes,
       fp32_alignment_bytes, src_rows, dst_rows, edges, general != 0);
   if (form) *form = p.form;

@@ -56,6 +56,11 @@ again, folds them with s_dst and D = grad_y . y into one 16-byte record per
 (destination, head) and recomputes every edge's weight in registers in one
 walk over the CSC (grad_s_dst) and one over the CSR (grad_h, grad_s_src).  A
 training step then allocates nothing of size E.  No dropout on this path.
+GATv2Layer.forward_recompute (`attend_v2` with recompute=True) is the same
+for GATv2: the one-pass fused forward also stores the softmax maximum and
+denominator per (destination, head) (nts_gatv2_forward_fused_stats[_bf16]),
+and the backward (nts_gatv2_backward_fused[_bf16]) recomputes every score
+from the rows its two walks gather anyway; it keeps (x_l, x_r, att, y, ms).
 
 bfloat16 feature rows: `h` of GATLayer and `x_l` / `x_r` of GATv2Layer may be
 torch.bfloat16.  The f-wide passes then read 2-byte rows through the *_bf16
@@ -718,10 +723,69 @@ class GATv2Layer(_EdgeLayer):
             return self.forward(x_l, x_r, att, negative_slope)[0]
         return y
 
+    def forward_recompute(self, x_l: torch.Tensor, x_r: torch.Tensor,
+                          att: torch.Tensor, negative_slope: float = 0.2):
+        """The forward for training without per-edge state: y of
+        forward_fused (bit for bit) and a `saved` of (x_l, x_r, att, y, ms)
+        alone, ms [dst_n, K, 2] being the softmax maximum and denominator per
+        (destination, head) that the forward's kernels leave behind
+        (Stream.gatv2_forward_fused_stats).  `backward` recomputes every
+        score and weight from them (Stream.gatv2_backward_fused).  It reads
+        saved["y"], which is the returned tensor itself: do not modify y in
+        place before the backward (`attend_v2` saves it through autograd,
+        which then raises).  Neither call allocates, writes or keeps an
+        [E, K] tensor.  Inputs and checks as for forward; either softmax
+        mode; no dropout.  A head wider than 1024 columns has no such form:
+        then this is forward(x_l, x_r, att, negative_slope)."""
+        ch, st, E, K = self.ch, self.stream, self.E, self.heads
+        f = self._check_inputs(x_l, x_r, att)
+        bf16 = x_l.dtype == torch.bfloat16
+        if not shim.gatv2_backward_fused_plan(f, K, 2 if bf16 else 4, 256, 256,
+                                              ch.src_n, ch.dst_n, E)["form"]:
+            return self.forward(x_l, x_r, att, negative_slope)
+        st.items_reuse(1)
+        y = torch.zeros(ch.dst_n, f, device=x_l.device)
+        # rows of destinations without in-edges are never written or read
+        ms = torch.empty(ch.dst_n, K, 2, device=x_l.device)
+        ran = (st.gatv2_forward_fused_stats_bf16 if bf16
+               else st.gatv2_forward_fused_stats)(
+            x_l.data_ptr(), x_r.data_ptr(), y.data_ptr(), att.data_ptr(),
+            negative_slope, ch.row_indices.data_ptr(),
+            ch.column_offset.data_ptr(), ch.src_s, ch.dst_n, E, f, K,
+            ms.data_ptr())
+        if not ran:   # the two plans share their width limit
+            raise RuntimeError("gatv2_forward_fused_stats has no form here")
+        return y, {"x_l": x_l, "x_r": x_r, "att": att, "y": y, "ms": ms,
+                   "recompute": True}
+
+    def _backward_recompute(self, grad_y, saved, negative_slope):
+        ch, st, E, K = self.ch, self.stream, self.E, self.heads
+        x_l, x_r, att = saved["x_l"], saved["x_r"], saved["att"]
+        f = int(x_l.shape[1])
+        dev = grad_y.device
+        st.items_reuse(1)
+        grad_xl = torch.zeros(ch.src_n, f, device=dev)
+        grad_xr = torch.zeros(ch.dst_n, f, device=dev)
+        grad_att = torch.zeros(K, f // K, device=dev)
+        ran = (st.gatv2_backward_fused_bf16 if x_l.dtype == torch.bfloat16
+               else st.gatv2_backward_fused)(
+            x_l.data_ptr(), x_r.data_ptr(), att.data_ptr(),
+            saved["y"].data_ptr(), saved["ms"].data_ptr(), grad_y.data_ptr(),
+            grad_xl.data_ptr(), grad_xr.data_ptr(), grad_att.data_ptr(),
+            negative_slope, ch.row_indices.data_ptr(),
+            ch.column_offset.data_ptr(), ch.row_offset.data_ptr(),
+            ch.column_indices.data_ptr(), ch.src_s, ch.src_e, ch.dst_s,
+            ch.dst_e, E, f, K)
+        if not ran:   # forward_recompute never saves such a width
+            raise RuntimeError(
+                "gatv2_backward_fused has no form for this width")
+        return grad_xl, grad_xr, grad_att
+
     def backward(self, grad_y: torch.Tensor, saved,
                  negative_slope: float = 0.2):
         """Returns (grad_x_l[src_n, K*C], grad_x_r[dst_n, K*C],
-        grad_att[K, C])."""
+        grad_att[K, C]).  A `saved` of forward_recompute runs the
+        recomputing backward, with the same shapes and dtypes."""
         ch, st, E, K = self.ch, self.stream, self.E, self.heads
         x_l, x_r, att = saved["x_l"], saved["x_r"], saved["att"]
         f = int(x_l.shape[1])
@@ -729,6 +793,8 @@ class GATv2Layer(_EdgeLayer):
                 or int(grad_y.shape[1]) != f:
             raise ValueError("grad_y does not match the saved forward input")
         self._check_rows("grad_y", grad_y, ch.dst_n, f)
+        if "recompute" in saved:
+            return self._backward_recompute(grad_y, saved, negative_slope)
         dev = grad_y.device
         bf16 = x_l.dtype == torch.bfloat16
         walk = st.edge_gatv2_backward_bf16 if bf16 else st.edge_gatv2_backward
@@ -787,25 +853,37 @@ class _AttendV2Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_l, x_r, att, layer, negative_slope, dropout=0.0,
-                seed=0):
-        y, saved = layer.forward(x_l.detach(), x_r.detach(), att.detach(),
-                                 negative_slope, dropout, seed)
+                seed=0, recompute=False):
+        args = (x_l.detach(), x_r.detach(), att.detach(), negative_slope)
+        if recompute:
+            y, saved = layer.forward_recompute(*args)
+            if "recompute" in saved:
+                # the backward reads y: saved through autograd, so that an
+                # in-place change of attend_v2's output raises there
+                saved = {k: t for k, t in saved.items() if k != "y"}
+                ctx.save_for_backward(y)
+        else:
+            y, saved = layer.forward(*args, dropout, seed)
         ctx.layer, ctx.saved, ctx.slope = layer, saved, negative_slope
         return y
 
     @staticmethod
     def backward(ctx, grad_y):
+        saved = ctx.saved
+        if "recompute" in saved:
+            saved = dict(saved, y=ctx.saved_tensors[0])
         grad_xl, grad_xr, grad_att = ctx.layer.backward(
-            grad_y.contiguous(), ctx.saved, ctx.slope)
+            grad_y.contiguous(), saved, ctx.slope)
         # fp32 out of the kernels; bf16 only if the rows themselves were
         dt = ctx.saved["x_l"].dtype
         return (grad_xl.to(dt), grad_xr.to(dt), grad_att, None, None, None,
-                None)
+                None, None)
 
 
 def attend_v2(x_l: torch.Tensor, x_r: torch.Tensor, att: torch.Tensor,
               layer: GATv2Layer, negative_slope: float = 0.2,
-              dropout: float = 0.0, seed=None) -> torch.Tensor:
+              dropout: float = 0.0, seed=None,
+              recompute: bool = False) -> torch.Tensor:
     """Autograd-aware GATv2 aggregation on `layer`'s graph, differentiable in
     x_l [src_n, K*C], x_r [dst_n, K*C] and att [K, C] (att float32, x_l and
     x_r both float32 or both bfloat16, their gradients in their own dtype;
@@ -815,9 +893,20 @@ def attend_v2(x_l: torch.Tensor, x_r: torch.Tensor, att: torch.Tensor,
     dropout, seed: attention dropout as for `attend`.
     Under torch.no_grad() with dropout == 0 (evaluation) the call is
     layer.forward_fused: the same y, with no [E, K] tensor allocated or
-    kept."""
+    kept.
+    recompute=True trains without per-edge state
+    (GATv2Layer.forward_recompute and its backward): the same y and
+    gradients up to rounding, nothing of size E allocated in either
+    direction.  That path has no dropout: recompute=True with dropout > 0
+    raises ValueError before any launch.  recompute=False makes exactly the
+    calls described above."""
+    if recompute and dropout > 0:
+        raise ValueError("attend_v2(recompute=True) has no attention dropout")
     if not torch.is_grad_enabled() and dropout == 0:
         _draw_seed(dropout, seed)   # the same argument checks
         return layer.forward_fused(x_l, x_r, att, negative_slope)
+    if recompute:
+        return _AttendV2Fn.apply(x_l, x_r, att, layer, negative_slope, 0.0,
+                                 _draw_seed(dropout, seed), True)
     return _AttendV2Fn.apply(x_l, x_r, att, layer, negative_slope, dropout,
                              _draw_seed(dropout, seed))

@@ -161,6 +161,18 @@ def lib():
     l.nts_gat_backward_fused_bf16.restype = _i32
     l.nts_gat_backward_fused_plan.argtypes = (
         [_u32] * 2 + [_c.c_uint] * 3 + [_u32] * 3 + [_i32] + [_vp] * 7)
+    # fused GATv2 training: the forward that also emits (M, S), the backward
+    # that recomputes the weights from them
+    for name in ("nts_gatv2_forward_fused_stats",
+                 "nts_gatv2_forward_fused_stats_bf16"):
+        getattr(l, name).argtypes = l.nts_gatv2_forward_fused.argtypes + [_vp]
+        getattr(l, name).restype = _i32
+    for name in ("nts_gatv2_backward_fused", "nts_gatv2_backward_fused_bf16"):
+        getattr(l, name).argtypes = (
+            [_vp] + [_vp] * 9 + [_c.c_float] + [_vp] * 4 + [_u32] * 7)
+        getattr(l, name).restype = _i32
+    l.nts_gatv2_backward_fused_plan.argtypes = (
+        l.nts_gat_backward_fused_plan.argtypes)
     l.nts_edge_softmax_stable.argtypes = [_vp, _i32]
     l.nts_edge_softmax_stable_last.argtypes = [_vp, _vp]
     # attention dropout
@@ -343,6 +355,28 @@ def gat_backward_fused_plan(f, heads, elem_bytes, row_alignment,
     out = [_i32(0) for _ in names]
     scratch = _c.c_ulonglong(0)
     lib().nts_gat_backward_fused_plan(
+        f, heads, elem_bytes, row_alignment, fp32_alignment, src_rows,
+        dst_rows, edges, 1 if general else 0, *[_c.byref(o) for o in out],
+        _c.byref(scratch))
+    plan = {n: o.value for n, o in zip(names, out)}
+    plan["scratch_bytes"] = scratch.value
+    return plan
+
+
+def gatv2_backward_fused_plan(f, heads, elem_bytes, row_alignment,
+                              fp32_alignment, src_rows, dst_rows, edges,
+                              general=False):
+    """The launch decision of Stream.gatv2_backward_fused[_bf16] (no device
+    access): the dict of gat_backward_fused_plan.  row_alignment is the
+    common alignment of x_l and x_r in bytes, fp32_alignment that of grad_y,
+    att, grad_x_l and grad_x_r; grid_csc is sized by the items alone (that
+    walk loops over the slabs itself)."""
+    check_heads(f, heads)
+    names = ("form", "cols_per_lane", "lane_group", "slabs", "grid_csr",
+             "grid_csc")
+    out = [_i32(0) for _ in names]
+    scratch = _c.c_ulonglong(0)
+    lib().nts_gatv2_backward_fused_plan(
         f, heads, elem_bytes, row_alignment, fp32_alignment, src_rows,
         dst_rows, edges, 1 if general else 0, *[_c.byref(o) for o in out],
         _c.byref(scratch))
@@ -878,6 +912,64 @@ class Stream:
             self.h, _vp(x_bf16), _vp(y_ptr), _vp(grad_y), _vp(grad_x),
             _vp(grad_s_src), _vp(grad_s_dst), _vp(s_src), _vp(s_dst), slope,
             _vp(row_indices), _vp(column_offset), _vp(row_offset),
+            _vp(column_indices), src_s, src_e, dst_s, dst_e, edges, f, heads)
+
+    # ---- fused GATv2 training: forward that also emits (M, S) per
+    # (destination, head), backward that recomputes the weights ----
+    def gatv2_forward_fused_stats(self, x_l, x_r, y_ptr, att, slope,
+                                  row_indices, column_offset, src_start,
+                                  batch, edges, f, heads, ms):
+        """gatv2_forward_fused (y bit-identical) that also stores ms[d, k] =
+        (M, S), fp32 [batch, heads, 2], for every destination with in-edges:
+        what gatv2_backward_fused needs besides y.  M is exactly 0 in the
+        default softmax mode."""
+        check_heads(f, heads)
+        return self._lib.nts_gatv2_forward_fused_stats(
+            self.h, _vp(x_l), _vp(x_r), _vp(y_ptr), _vp(att), slope,
+            _vp(row_indices), _vp(column_offset), src_start, batch, edges, f,
+            heads, _vp(ms))
+
+    def gatv2_forward_fused_stats_bf16(self, x_l_bf16, x_r_bf16, y_ptr, att,
+                                       slope, row_indices, column_offset,
+                                       src_start, batch, edges, f, heads, ms):
+        """gatv2_forward_fused_stats with both row operands bfloat16."""
+        check_heads(f, heads)
+        return self._lib.nts_gatv2_forward_fused_stats_bf16(
+            self.h, _vp(x_l_bf16), _vp(x_r_bf16), _vp(y_ptr), _vp(att), slope,
+            _vp(row_indices), _vp(column_offset), src_start, batch, edges, f,
+            heads, _vp(ms))
+
+    def gatv2_backward_fused(self, x_l, x_r, att, y_ptr, ms, grad_y, grad_x_l,
+                             grad_x_r, grad_att, slope, row_indices,
+                             column_offset, row_offset, column_indices, src_s,
+                             src_e, dst_s, dst_e, edges, f, heads):
+        """The backward of gatv2_forward_fused_stats from its inputs, its
+        output y and ms: grad_x_l, grad_x_r and grad_att are added to (the
+        caller zeroes).  A 16-byte record per (destination, head), one walk
+        over the CSC and one over the CSR, every edge's score, weight and
+        softmax gradient recomputed in registers; nothing of size edges is
+        allocated.  Honours edge_softmax_stable (as the forward did).
+        Returns 1 when it ran (or there was nothing to do), 0 when C > 1024:
+        nothing was launched."""
+        check_heads(f, heads)
+        return self._lib.nts_gatv2_backward_fused(
+            self.h, _vp(x_l), _vp(x_r), _vp(att), _vp(y_ptr), _vp(ms),
+            _vp(grad_y), _vp(grad_x_l), _vp(grad_x_r), _vp(grad_att), slope,
+            _vp(row_indices), _vp(column_offset), _vp(row_offset),
+            _vp(column_indices), src_s, src_e, dst_s, dst_e, edges, f, heads)
+
+    def gatv2_backward_fused_bf16(self, x_l_bf16, x_r_bf16, att, y_ptr, ms,
+                                  grad_y, grad_x_l, grad_x_r, grad_att, slope,
+                                  row_indices, column_offset, row_offset,
+                                  column_indices, src_s, src_e, dst_s, dst_e,
+                                  edges, f, heads):
+        """gatv2_backward_fused over bfloat16 x_l and x_r (everything else,
+        every gradient included, stays float32)."""
+        check_heads(f, heads)
+        return self._lib.nts_gatv2_backward_fused_bf16(
+            self.h, _vp(x_l_bf16), _vp(x_r_bf16), _vp(att), _vp(y_ptr),
+            _vp(ms), _vp(grad_y), _vp(grad_x_l), _vp(grad_x_r), _vp(grad_att),
+            slope, _vp(row_indices), _vp(column_offset), _vp(row_offset),
             _vp(column_indices), src_s, src_e, dst_s, dst_e, edges, f, heads)
 
     # ---- max / min aggregation; op is checked here, the library aborts on

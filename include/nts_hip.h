@@ -934,6 +934,76 @@ void nts_gatv2_forward_fused_plan(nts_vid feature_size, nts_vid heads,
     int general, int *form, int *cols_per_lane, int *lane_group, int *slabs,
     int *grid, unsigned long long *scratch_bytes);
 
+/* ---- fused dot-product attention forward (additive): one row pass ----
+ * Scaled dot-product attention over edges (TransformerConv / Graph
+ * Transformer) for a caller that needs only the aggregated rows: the forward
+ * of nts_edge_dot_heads[_bf16] on the scaled q, the edge softmax and
+ * nts_gather_by_dst_from_src_heads[_bf16] of v.  Per edge e into destination
+ * d and head h, C = feature_size / heads, columns head-major, u =
+ * row_indices[e] - src_start:
+ *   qs[c]  = scale * q[d, c]                 ONE fp32 multiply, when d's row
+ *                                            is loaded
+ *   s      = sum_{j<C} qs[h*C+j] * k[u, h*C+j]          an fp32 sum
+ *   output[d, c] += sum_e softmax_e(s)[e, c / C] * v[u, c]
+ * Every k row and every v row is read ONCE per edge, qs stays in registers
+ * for the whole work item, and the softmax is evaluated online per (lane,
+ * head) as (m, S, acc), exactly as in nts_gatv2_forward_fused:
+ *   stable (nts_edge_softmax_stable): m = -inf, S = 0, acc = 0 and
+ *     m' = max(m, s), S = S*exp(m-m') + exp(s-m'), acc = acc*exp(m-m') +
+ *     exp(s-m')*v, the maximum and the rescale taken once per block of up to
+ *     four edges;
+ *   default: m = 0, never rescaled: sum exp(s)*v / sum exp(s), unspecified
+ *     wherever the default softmax is.
+ * Scores must be finite.  The mode is recorded for
+ * nts_edge_softmax_stable_last.
+ *   Forms and geometry are those of nts_gatv2_forward_fused.  Fast, C a
+ * power of two and C / R <= 64: a lane holds R = 4 / 2 / 1 consecutive
+ * columns of one head (the widest that divides C and that every pointer
+ * permits: R*4 bytes of alignment for output and fp32 rows, R*2 for bf16
+ * rows), a group of G <= 64 lanes owns one (item, slab of G*R columns), a
+ * head is an aligned segment of L = C / R lanes; per block of four edges the
+ * four index loads, four k loads and four v loads are issued together and
+ * the four partial dots go through one interleaved butterfly over the L
+ * lanes.  General, any heads and C <= 1024, and whenever
+ * nts_heads_dbg_general is set: a wave per (item, head), lane l owning the
+ * head's columns l + 64*i.
+ *   No atomics.  A destination that is one work item ends with a plain
+ * output += acc / S, so rows without in-edges are untouched and the caller
+ * zeroes.  A split destination's items store (acc, m, S) records in the
+ * record format and the stream scratch of nts_gatv2_forward_fused (same
+ * size rule, grown on demand, which synchronizes once) and its merge kernel
+ * folds them in item order.  The result is therefore bit-reproducible from
+ * launch to launch, split destinations included.  Nothing sized by `edges`
+ * is allocated, read or written besides row_indices.
+ *   q is [batch_size, feature_size], k and v [rows, feature_size]; all three
+ * fp32, or all three bf16 (raw uint16_t, widened exactly; at the same form
+ * and R the bf16 entry is bit-identical to the fp32 one on the widened
+ * rows); output is fp32.  Both kernels run under NTS_KTAG_FWD; the edge count
+ * is the caller's: no device-to-host copy, no synchronize beyond scratch
+ * growth.  Invalid heads abort as for the heads gathers.
+ *   Returns 1 when the forward ran or there was nothing to do (batch_size ==
+ * 0 or edges == 0: nothing launched); 0 when C > 1024: nothing is launched
+ * or written and the caller runs the three-entry chain instead.
+ *   nts_dot_attention_forward_fused_plan reports the decision without
+ * touching a device (the launch takes it from the same function, which is
+ * nts_gatv2_forward_fused_plan's): row_alignment_bytes is the common
+ * alignment of q, k and v, fp32_alignment_bytes that of output. */
+int nts_dot_attention_forward_fused(nts_stream *s, const float *q,
+    const float *k, const float *v, float *output, float scale,
+    const nts_vid *row_indices, const nts_vid *column_offset,
+    nts_vid src_start, nts_vid batch_size, nts_vid edges,
+    nts_vid feature_size, nts_vid heads);
+int nts_dot_attention_forward_fused_bf16(nts_stream *s, const uint16_t *q,
+    const uint16_t *k, const uint16_t *v, float *output, float scale,
+    const nts_vid *row_indices, const nts_vid *column_offset,
+    nts_vid src_start, nts_vid batch_size, nts_vid edges,
+    nts_vid feature_size, nts_vid heads);
+void nts_dot_attention_forward_fused_plan(nts_vid feature_size, nts_vid heads,
+    unsigned elem_bytes, unsigned row_alignment_bytes,
+    unsigned fp32_alignment_bytes, nts_vid batch_size, nts_vid edges,
+    int general, int *form, int *cols_per_lane, int *lane_group, int *slabs,
+    int *grid, unsigned long long *scratch_bytes);
+
 /* ---- fused GAT training backward (additive): no per-edge state ----
  * The backward of nts_gat_forward_fused[_bf16] (equally of the attention
  * forward + heads gather chain without dropout) for a caller that kept only

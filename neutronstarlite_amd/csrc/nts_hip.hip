@@ -2678,6 +2678,192 @@ NTS_NO_PK __global__ void k_gatv2_fused_merge_stats(
                           C, stats);
 }
 
+/* ---- fused dot-product attention forward: one pass over k and v ---- */
+/* score[e, k] = scale * q[d, head k] . k[src(e), head k], softmax over d's
+ * in-edges per head, y[d] += sum_e alpha_e * v[src(e)].  An edge reads two
+ * rows, k[u] for the score and v[u] for the value, each once; everything
+ * after the score is the online (m, S, acc) of the GATv2 fused forward
+ * (v2_update), with the same items, lane geometry, record format, scratch
+ * and merge kernel (k_gatv2_fused_merge), hence no atomics either.
+ *   The destination's row is scaled once when it is loaded, qs = scale * q[d]
+ * (one fp32 multiply), and stays in registers for the whole item; the
+ * partial dot of a lane is an fmaf chain of qs[j] * k[u, j] over its columns.
+ *   Edge block of the fast form (NE = 4): four index loads, then the four k
+ * loads AND the four v loads are issued before the first k is consumed, so
+ * eight row loads are in flight over the butterfly and the exps; the v rows
+ * cost 4*R registers that are live across the butterfly (DESIGN.md §3 has the
+ * register counts of this and of the variant that loads v after it). */
+template <typename T>
+struct DotSrc {
+  const uint32_t *__restrict__ nbr;
+  const T *__restrict__ k;
+  const T *__restrict__ v;
+  uint32_t nbr_start, f;
+};
+
+/* fast form: NE consecutive edges, the butterfly interleaved as in
+ * v2_edges_seg */
+template <int R, int NE, bool STABLE, typename T>
+__device__ __forceinline__ void dot_edges_seg(float &m, float &S,
+                                              float (&acc)[R],
+                                              const DotSrc<T> &g, uint32_t e,
+                                              uint32_t col, uint32_t L,
+                                              const float (&qs)[R]) {
+  uint64_t off[NE];
+  float kv[NE][R], vv[NE][R], sc[NE];
+#pragma unroll
+  for (int k = 0; k < NE; ++k)
+    off[k] = (uint64_t)(g.nbr[e + k] - g.nbr_start) * g.f + col;
+#pragma unroll
+  for (int k = 0; k < NE; ++k) load_cols<R>(g.k + off[k], kv[k]);
+#pragma unroll
+  for (int k = 0; k < NE; ++k) load_cols<R>(g.v + off[k], vv[k]);
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    sc[k] = 0.f;
+#pragma unroll
+    for (int j = 0; j < R; ++j) sc[k] = fmaf(qs[j], kv[k][j], sc[k]);
+  }
+  for (uint32_t w = L >> 1; w >= 1; w >>= 1)
+#pragma unroll
+    for (int k = 0; k < NE; ++k) sc[k] += __shfl_xor(sc[k], w, 64);
+  v2_update<R, NE, STABLE>(m, S, acc, sc, vv);
+}
+
+/* Fast form: the task and lane geometry of k_gatv2_fused_seg (a group of G
+ * lanes per (item, slab of G*R columns), a head an aligned segment of L = C/R
+ * lanes, lanes past the row's end whole segments that take no part). */
+template <int R, bool STABLE, typename T>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_seg(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ nbr, const T *__restrict__ q,
+    const T *__restrict__ k, const T *__restrict__ v, float *__restrict__ out,
+    float *__restrict__ scratch, float scale, uint32_t nbr_start, uint32_t f,
+    uint32_t K, uint32_t C, uint32_t G, uint32_t n_slabs) {
+  const uint32_t n_items = *n_items_p;
+  const uint32_t glane = threadIdx.x & (G - 1);
+  const uint32_t L = C / R;
+  const DotSrc<T> g{nbr, k, v, nbr_start, f};
+  const uint64_t total = (uint64_t)n_items * n_slabs;
+  const uint64_t stride = (gridDim.x * NTS_BLOCK) / G;
+  for (uint64_t t = (blockIdx.x * NTS_BLOCK + threadIdx.x) / G; t < total;
+       t += stride) {
+    const uint32_t it = (uint32_t)(t / n_slabs);
+    const uint32_t col = (uint32_t)(t % n_slabs) * G * R + glane * R;
+    if (col >= f) continue;
+    const Item im = load_item(items, it);
+    float qs[R], acc[R] = {};
+    load_cols<R>(q + (uint64_t)im.v * f + col, qs);
+#pragma unroll
+    for (int j = 0; j < R; ++j) qs[j] *= scale;
+    float m = STABLE ? -INFINITY : 0.f, S = 0.f;
+    const uint32_t e_end = im.e0 + im.cnt;
+    uint32_t e = im.e0;
+    for (; e + 4 <= e_end; e += 4)
+      dot_edges_seg<R, 4, STABLE>(m, S, acc, g, e, col, L, qs);
+    for (; e < e_end; ++e)
+      dot_edges_seg<R, 1, STABLE>(m, S, acc, g, e, col, L, qs);
+    if (!im.shared) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) acc[j] /= S;
+      store_acc<R>(out + (uint64_t)im.v * f + col, acc, R, false);
+    } else {
+      float *rec = scratch + (uint64_t)it * (f + 2 * K);
+#pragma unroll
+      for (int j = 0; j < R; ++j) rec[col + j] = acc[j];
+      if ((glane & (L - 1)) == 0) {
+        rec[f + 2 * (col / C)] = m;
+        rec[f + 2 * (col / C) + 1] = S;
+      }
+    }
+  }
+}
+
+/* general form: NE consecutive edges of one (item, head) across the wave;
+ * dead columns (lane + 64*i >= C) hold zeros in qs, kv and vv */
+template <int NCH, int NE, bool STABLE, typename T>
+__device__ __forceinline__ void dot_edges_wave(float &m, float &S,
+                                               float (&acc)[NCH],
+                                               const DotSrc<T> &g, uint32_t e,
+                                               uint32_t col, uint32_t lane,
+                                               uint32_t C,
+                                               const float (&qs)[NCH]) {
+  uint64_t off[NE];
+  float kv[NE][NCH], vv[NE][NCH], sc[NE];
+#pragma unroll
+  for (int k = 0; k < NE; ++k)
+    off[k] = (uint64_t)(g.nbr[e + k] - g.nbr_start) * g.f + col;
+#pragma unroll
+  for (int k = 0; k < NE; ++k)
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+      kv[k][i] = (lane + 64 * i < C) ? to_f32(g.k[off[k] + 64 * i]) : 0.f;
+#pragma unroll
+  for (int k = 0; k < NE; ++k)
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+      vv[k][i] = (lane + 64 * i < C) ? to_f32(g.v[off[k] + 64 * i]) : 0.f;
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    float pr = 0.f;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) pr = fmaf(qs[i], kv[k][i], pr);
+    sc[k] = wave_sum(pr);
+  }
+  v2_update<NCH, NE, STABLE>(m, S, acc, sc, vv);
+}
+
+/* General form, any K and C <= 64*NCH: a wave runs one (item, head), lane l
+ * owns the head's columns l + 64*i, i < NCH, as in k_gatv2_fused_wave.  Two
+ * gathered rows per edge: NE = 4 / 4 / 2 / 1 / 1 edges in flight at NCH = 1 /
+ * 2 / 4 / 8 / 16, so that both rows of every edge stay in registers. */
+template <int NCH, bool STABLE, typename T>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_wave(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ nbr, const T *__restrict__ q,
+    const T *__restrict__ k, const T *__restrict__ v, float *__restrict__ out,
+    float *__restrict__ scratch, float scale, uint32_t nbr_start, uint32_t f,
+    uint32_t K, uint32_t C) {
+  constexpr int NE = NCH <= 2 ? 4 : NCH <= 8 ? 8 / NCH : 1;
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  const DotSrc<T> g{nbr, k, v, nbr_start, f};
+  const uint64_t total = (uint64_t)n_items * K;
+  for (uint64_t t = w.wave; t < total; t += w.n_waves) {
+    const uint32_t it = (uint32_t)(t / K), head = (uint32_t)(t % K);
+    const Item im = load_item(items, it);
+    const uint32_t col = head * C + w.lane;
+    float qs[NCH], acc[NCH] = {};
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+      qs[i] = (w.lane + 64 * i < C)
+                  ? scale * to_f32(q[(uint64_t)im.v * f + col + 64 * i])
+                  : 0.f;
+    float m = STABLE ? -INFINITY : 0.f, S = 0.f;
+    const uint32_t e_end = im.e0 + im.cnt;
+    uint32_t e = im.e0;
+    for (; e + NE <= e_end; e += NE)
+      dot_edges_wave<NCH, NE, STABLE>(m, S, acc, g, e, col, w.lane, C, qs);
+    for (; e < e_end; ++e)
+      dot_edges_wave<NCH, 1, STABLE>(m, S, acc, g, e, col, w.lane, C, qs);
+    if (!im.shared) {
+      float *o = out + (uint64_t)im.v * f + col;
+#pragma unroll
+      for (int i = 0; i < NCH; ++i)
+        if (w.lane + 64 * i < C) o[64 * i] += acc[i] / S;
+    } else {
+      float *rec = scratch + (uint64_t)it * (f + 2 * K);
+#pragma unroll
+      for (int i = 0; i < NCH; ++i)
+        if (w.lane + 64 * i < C) rec[col + 64 * i] = acc[i];
+      if (w.lane == 0) {
+        rec[f + 2 * head] = m;
+        rec[f + 2 * head + 1] = S;
+      }
+    }
+  }
+}
+
 /* ---- GAT training backward that recomputes the attention weights ---- */
 /* An edge's weight alpha_e = exp(lrelu(s_src[u] + s_dst[d]) - M[d]) / S[d] is
  * a function of two per-vertex scalars and the destination's denominator, so
@@ -5691,6 +5877,108 @@ void nts_gatv2_forward_fused_plan(nts_vid feature_size, nts_vid heads,
                                   int *lane_group, int *slabs, int *grid,
                                   unsigned long long *scratch_bytes) {
   check_heads("nts_gatv2_forward_fused_plan", feature_size, heads);
+  const Gatv2FusedPlan p = plan_gatv2_fused(
+      feature_size, heads, elem_bytes, row_alignment_bytes,
+      fp32_alignment_bytes, batch_size, edges, general != 0);
+  if (form) *form = p.form;
+  if (cols_per_lane) *cols_per_lane = (int)p.R;
+  if (lane_group) *lane_group = (int)p.G;
+  if (slabs) *slabs = (int)p.slabs;
+  if (grid) *grid = (int)p.grid;
+  if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+}
+
+/* ---- fused dot-product attention forward (additive; see nts_hip.h) ---- */
+extern "C++" {
+/* The plan is plan_gatv2_fused's: q, k and v are the rows, the output the
+ * only fp32 operand. */
+template <typename T>
+static int dot_attention_forward_fused(nts_stream *s, const char *entry,
+                                       const T *q, const T *k, const T *v,
+                                       float *out, float scale,
+                                       const nts_vid *row_indices,
+                                       const nts_vid *offset,
+                                       nts_vid src_start, nts_vid batch,
+                                       nts_vid edges, nts_vid f, nts_vid K) {
+  check_heads(entry, f, K);
+  s->softmax_stable_last = s->softmax_stable;
+  if (!batch || !edges) return 1;
+  const Gatv2FusedPlan pl = plan_gatv2_fused(
+      f, K, sizeof(T), (uintptr_t)q | (uintptr_t)k | (uintptr_t)v,
+      (uintptr_t)out, batch, edges, s->heads_general);
+  if (!pl.form) return 0;
+  const EdgeItems p = edge_items_known(s, offset, batch, edges);
+  float *scratch =
+      pl.scratch_bytes ? get_v2_scratch(s, pl.scratch_bytes) : nullptr;
+  const bool st = s->softmax_stable;
+  const uint32_t C = f / K;
+  Tic t(s, NTS_KTAG_FWD);
+  if (pl.form == 1) {
+#define NTS_K(RR)                                                             \
+  (st ? k_dot_fused_seg<RR, true, T> : k_dot_fused_seg<RR, false, T>)
+    hipLaunchKernelGGL(pl.R == 4 ? NTS_K(4) : pl.R == 2 ? NTS_K(2) : NTS_K(1),
+                       dim3(pl.grid), dim3(NTS_BLOCK), 0, s->stream,
+                       p.ib->items, p.ib->counter, row_indices, q, k, v, out,
+                       scratch, scale, src_start, f, K, C, pl.G, pl.slabs);
+#undef NTS_K
+  } else {
+    /* indexed by log2(NCH) */
+    static const decltype(&k_dot_fused_wave<1, false, T>) kernels[2][5] = {
+        {k_dot_fused_wave<1, false, T>, k_dot_fused_wave<2, false, T>,
+         k_dot_fused_wave<4, false, T>, k_dot_fused_wave<8, false, T>,
+         k_dot_fused_wave<16, false, T>},
+        {k_dot_fused_wave<1, true, T>, k_dot_fused_wave<2, true, T>,
+         k_dot_fused_wave<4, true, T>, k_dot_fused_wave<8, true, T>,
+         k_dot_fused_wave<16, true, T>}};
+    hipLaunchKernelGGL(kernels[st][__builtin_ctz(pl.nch)], dim3(pl.grid),
+                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                       p.ib->counter, row_indices, q, k, v, out, scratch,
+                       scale, src_start, f, K, C);
+  }
+  if (scratch)
+    hipLaunchKernelGGL(k_gatv2_fused_merge, dim3(p.grid), dim3(NTS_BLOCK), 0,
+                       s->stream, p.ib->items, p.ib->counter, offset, scratch,
+                       out, NTS_SPLIT, f, K, C);
+  dbg_sync(s, "k_dot_fused");
+  return 1;
+}
+}  // extern "C++"
+
+int nts_dot_attention_forward_fused(nts_stream *s, const float *q,
+                                    const float *k, const float *v,
+                                    float *output, float scale,
+                                    const nts_vid *row_indices,
+                                    const nts_vid *column_offset,
+                                    nts_vid src_start, nts_vid batch_size,
+                                    nts_vid edges, nts_vid feature_size,
+                                    nts_vid heads) {
+  return dot_attention_forward_fused(
+      s, "nts_dot_attention_forward_fused", q, k, v, output, scale,
+      row_indices, column_offset, src_start, batch_size, edges, feature_size,
+      heads);
+}
+
+int nts_dot_attention_forward_fused_bf16(nts_stream *s, const uint16_t *q,
+                                         const uint16_t *k, const uint16_t *v,
+                                         float *output, float scale,
+                                         const nts_vid *row_indices,
+                                         const nts_vid *column_offset,
+                                         nts_vid src_start, nts_vid batch_size,
+                                         nts_vid edges, nts_vid feature_size,
+                                         nts_vid heads) {
+  return dot_attention_forward_fused(
+      s, "nts_dot_attention_forward_fused_bf16", q, k, v, output, scale,
+      row_indices, column_offset, src_start, batch_size, edges, feature_size,
+      heads);
+}
+
+void nts_dot_attention_forward_fused_plan(
+    nts_vid feature_size, nts_vid heads, unsigned elem_bytes,
+    unsigned row_alignment_bytes, unsigned fp32_alignment_bytes,
+    nts_vid batch_size, nts_vid edges, int general, int *form,
+    int *cols_per_lane, int *lane_group, int *slabs, int *grid,
+    unsigned long long *scratch_bytes) {
+  check_heads("nts_dot_attention_forward_fused_plan", feature_size, heads);
   const Gatv2FusedPlan p = plan_gatv2_fused(
       feature_size, heads, elem_bytes, row_alignment_bytes,
       fp32_alignment_bytes, batch_size, edges, general != 0);

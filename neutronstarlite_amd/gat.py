@@ -62,6 +62,15 @@ denominator per (destination, head) (nts_gatv2_forward_fused_stats[_bf16]),
 and the backward (nts_gatv2_backward_fused[_bf16]) recomputes every score
 from the rows its two walks gather anyway; it keeps (x_l, x_r, att, y, ms).
 
+Dot-product attention (DotAttentionLayer, `attend_dot`): the score is scale *
+q[dst] . k[src] per head and the value row is v[src].  Training runs on the
+entries above (the per-head edge dot on the scaled q, the dual-order softmax
+or its dropout twin, heads gathers for y and for all three row gradients);
+evaluation (`forward_fused`, `attend_dot` under torch.no_grad()) is one entry
+of its own (nts_dot_attention_forward_fused[_bf16]) that reads k[src] and
+v[src] once per edge with the softmax evaluated online and keeps nothing per
+edge.  q, k and v are all float32 or all bfloat16.
+
 bfloat16 feature rows: `h` of GATLayer and `x_l` / `x_r` of GATv2Layer may be
 torch.bfloat16.  The f-wide passes then read 2-byte rows through the *_bf16
 entries (widened exactly in registers); attention scalars, `att`, every
@@ -910,3 +919,211 @@ def attend_v2(x_l: torch.Tensor, x_r: torch.Tensor, att: torch.Tensor,
                                  _draw_seed(dropout, seed), True)
     return _AttendV2Fn.apply(x_l, x_r, att, layer, negative_slope, dropout,
                              _draw_seed(dropout, seed))
+
+
+class DotAttentionLayer(_EdgeLayer):
+    """Scaled dot-product attention over edges (the TransformerConv of UniMP,
+    the Graph Transformer layers) on one chunk:
+
+      score[e, k] = scale * q[dst(e), head k] . k[src(e), head k]
+      alpha       = softmax of score over dst(e)'s in-edges, per head
+      y[d, c]     = sum_{e into d} alpha[e, c // C] * v[src(e), c]
+
+    The training step is built from the entries the other layers use: the
+    score is the per-head edge dot (nts_edge_dot_heads) on the scaled q, the
+    softmax the dual emission, the aggregation and all three row gradients
+    heads gathers.  `forward_fused` is one kernel of its own
+    (nts_dot_attention_forward_fused) that keeps nothing per edge."""
+
+    def __init__(self, ch: Chunk, v: int, device, heads: int = 1,
+                 stable: bool = False):
+        """heads = K heads over head-major column blocks (heads == 1: C = f);
+        stable=True runs the max-subtracted softmax, as for GATLayer."""
+        self._setup(ch, v, device, heads, stable)
+
+    def _check_inputs(self, q, k, v, scale):
+        ch, K = self.ch, self.heads
+        if not isinstance(q, torch.Tensor) or q.dim() != 2:
+            raise ValueError("q must be a 2-d tensor")
+        f = int(q.shape[1])
+        if f < K or f % K != 0:
+            raise ValueError(
+                f"q has {f} columns, not a multiple of heads={K}")
+        self._check_rows("q", q, ch.dst_n, f, bf16_ok=True)
+        self._check_rows("k", k, ch.src_n, f, bf16_ok=True)
+        self._check_rows("v", v, ch.src_n, f, bf16_ok=True)
+        if not q.dtype == k.dtype == v.dtype:
+            raise TypeError(
+                f"q, k and v must have one dtype, got {q.dtype}, {k.dtype} "
+                f"and {v.dtype}")
+        scale = (f // K) ** -0.5 if scale is None else float(scale)
+        if not np.isfinite(scale):
+            raise ValueError(f"scale must be finite, got {scale!r}")
+        return f, scale
+
+    def forward(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                scale=None, dropout: float = 0.0, seed: int = 0):
+        """q: [dst_n, K*C], k and v: [src_n, K*C], all float32 or all
+        bfloat16; scale=None is C ** -0.5.  Returns (y[dst_n, K*C] float32,
+        saved).  q is scaled once per vertex (a V-sized pass), never the
+        [E, K] scores.  dropout, seed: attention dropout exactly as for
+        GATLayer.forward — `saved` then carries alpha (the cache), w and
+        w_csr (the dropped gather weights), p and seed."""
+        drop = self._drop(dropout, seed)
+        ch, st, E, K = self.ch, self.stream, self.E, self.heads
+        f, scale = self._check_inputs(q, k, v, scale)
+        dev = q.device
+        bf16 = q.dtype == torch.bfloat16
+        st.items_reuse(1)
+        qs = q.float() * scale
+        score = torch.empty(E, K, device=dev)
+        (st.edge_dot_heads_bf16 if bf16 else st.edge_dot_heads)(
+            score.data_ptr(), qs.data_ptr(), k.data_ptr(),
+            ch.row_indices.data_ptr(), ch.column_offset.data_ptr(), ch.src_s,
+            ch.dst_n, E, f, K)
+        # per-(destination, head) softmax, dual-emitted in CSC (alpha) and
+        # CSR (alpha_csr) edge order; cache = output
+        alpha = torch.empty(E, K, device=dev)
+        saved = {"q": q, "k": k, "v": v, "scale": scale, "alpha": alpha}
+        if drop:
+            # alpha stays the softmax; w, w_csr are the dropped weights
+            w = torch.empty(E, K, device=dev)
+            w_csr = torch.empty(E, K, device=dev)
+            st.edge_softmax_forward_drop(
+                w.data_ptr(), w_csr.data_ptr(), self._inv_perm_u32.data_ptr(),
+                score.data_ptr(), alpha.data_ptr(),
+                ch.column_offset.data_ptr(), ch.dst_n, E, K, *drop)
+            saved.update(w=w, w_csr=w_csr, p=drop[0], seed=drop[1])
+        else:
+            w = alpha
+            alpha_csr = torch.empty(E, K, device=dev)
+            st.edge_softmax_forward_dual(
+                alpha.data_ptr(), alpha_csr.data_ptr(),
+                self._inv_perm_u32.data_ptr(), score.data_ptr(),
+                alpha.data_ptr(), ch.column_offset.data_ptr(), ch.dst_n, K)
+            saved["alpha_csr"] = alpha_csr
+        y = torch.zeros(ch.dst_n, f, device=dev)
+        (st.gather_by_dst_from_src_heads_bf16 if bf16
+         else st.gather_by_dst_from_src_heads)(
+            v.data_ptr(), y.data_ptr(), w.data_ptr(),
+            ch.row_indices.data_ptr(), ch.column_offset.data_ptr(),
+            ch.src_s, ch.src_e, ch.dst_s, ch.dst_e, E, ch.dst_n, f, K)
+        return y, saved
+
+    def forward_fused(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                      scale=None):
+        """The forward for evaluation: y of forward(q, k, v, scale) and
+        nothing else.  One entry (Stream.dot_attention_forward_fused) reads
+        every k row and every v row once per edge with the softmax evaluated
+        online, so no [E, K] tensor is allocated, written or kept; there is
+        no `saved`, no dropout and no backward.  Inputs as for forward
+        (checked the same way, a bad one raises before any launch); either
+        softmax mode of the layer.  y is bit-reproducible from call to call,
+        split destinations included.  A head wider than 1024 columns runs
+        forward instead."""
+        ch, st, E, K = self.ch, self.stream, self.E, self.heads
+        f, scale = self._check_inputs(q, k, v, scale)
+        st.items_reuse(1)
+        y = torch.zeros(ch.dst_n, f, device=q.device)
+        ran = (st.dot_attention_forward_fused_bf16
+               if q.dtype == torch.bfloat16
+               else st.dot_attention_forward_fused)(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), y.data_ptr(), scale,
+            ch.row_indices.data_ptr(), ch.column_offset.data_ptr(), ch.src_s,
+            ch.dst_n, E, f, K)
+        if not ran:
+            return self.forward(q, k, v, scale)[0]
+        return y
+
+    def backward(self, grad_y: torch.Tensor, saved):
+        """Returns (grad_q[dst_n, K*C], grad_k[src_n, K*C], grad_v[src_n,
+        K*C]), all float32."""
+        ch, st, E, K = self.ch, self.stream, self.E, self.heads
+        q, k, v, scale = saved["q"], saved["k"], saved["v"], saved["scale"]
+        f = int(q.shape[1])
+        if not isinstance(grad_y, torch.Tensor) or grad_y.dim() != 2 \
+                or int(grad_y.shape[1]) != f:
+            raise ValueError("grad_y does not match the saved forward input")
+        self._check_rows("grad_y", grad_y, ch.dst_n, f)
+        dev = grad_y.device
+        bf16 = q.dtype == torch.bfloat16
+        st.items_reuse(1)
+        # through the aggregation: grad_v, and the per-head dot that is the
+        # gradient with respect to the gather's weights
+        dropped = "p" in saved   # then the weights are w and galpha is dL/dw
+        w_csr = saved["w_csr"] if dropped else saved["alpha_csr"]
+        csr = (ch.row_offset.data_ptr(), ch.column_indices.data_ptr(),
+               ch.src_s, ch.src_e, ch.dst_s, ch.dst_e, E, ch.src_n, f, K)
+        grad_v = torch.zeros(ch.src_n, f, device=dev)
+        st.gather_by_src_from_dst_heads(grad_y.data_ptr(), grad_v.data_ptr(),
+                                        w_csr.data_ptr(), *csr)
+        galpha = torch.empty(E, K, device=dev)
+        (st.edge_dot_heads_bf16 if bf16 else st.edge_dot_heads)(
+            galpha.data_ptr(), grad_y.data_ptr(), v.data_ptr(),
+            ch.row_indices.data_ptr(), ch.column_offset.data_ptr(), ch.src_s,
+            ch.dst_n, E, f, K)
+        # softmax backward without a leaky-relu mask, dual-emitted
+        gscore = torch.empty(E, K, device=dev)
+        gscore_csr = torch.empty(E, K, device=dev)
+        if dropped:
+            st.edge_softmax_backward_drop(
+                gscore.data_ptr(), gscore_csr.data_ptr(),
+                self._inv_perm_u32.data_ptr(), galpha.data_ptr(),
+                saved["alpha"].data_ptr(), None, 1.0,
+                ch.column_offset.data_ptr(), ch.dst_n, E, K, saved["p"],
+                saved["seed"], dst_sum=None)
+        else:
+            st.edge_softmax_backward_fused(
+                gscore.data_ptr(), gscore_csr.data_ptr(),
+                self._inv_perm_u32.data_ptr(), galpha.data_ptr(),
+                saved["alpha"].data_ptr(), None, 1.0,
+                ch.column_offset.data_ptr(), ch.dst_n, K, dst_sum=None)
+        # score = scale * q[d] . k[u]: the CSC gather of k and the CSR gather
+        # of q, weighted by the score gradient, scaled once per vertex
+        grad_q = torch.zeros(ch.dst_n, f, device=dev)
+        (st.gather_by_dst_from_src_heads_bf16 if bf16
+         else st.gather_by_dst_from_src_heads)(
+            k.data_ptr(), grad_q.data_ptr(), gscore.data_ptr(),
+            ch.row_indices.data_ptr(), ch.column_offset.data_ptr(),
+            ch.src_s, ch.src_e, ch.dst_s, ch.dst_e, E, ch.dst_n, f, K)
+        grad_k = torch.zeros(ch.src_n, f, device=dev)
+        (st.gather_by_src_from_dst_heads_bf16 if bf16
+         else st.gather_by_src_from_dst_heads)(
+            q.data_ptr(), grad_k.data_ptr(), gscore_csr.data_ptr(), *csr)
+        return grad_q.mul_(scale), grad_k.mul_(scale), grad_v
+
+
+class _AttendDotFn(torch.autograd.Function):
+    """torch.autograd bridge over DotAttentionLayer.forward/backward."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, layer, scale, dropout=0.0, seed=0):
+        y, saved = layer.forward(q.detach(), k.detach(), v.detach(), scale,
+                                 dropout, seed)
+        ctx.layer, ctx.saved = layer, saved
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        grads = ctx.layer.backward(grad_y.contiguous(), ctx.saved)
+        # fp32 out of the kernels; bf16 only if the rows themselves were
+        dt = ctx.saved["q"].dtype
+        return (*(g.to(dt) for g in grads), None, None, None, None)
+
+
+def attend_dot(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+               layer: DotAttentionLayer, scale=None, dropout: float = 0.0,
+               seed=None) -> torch.Tensor:
+    """Autograd-aware dot-product attention on `layer`'s graph,
+    differentiable in q [dst_n, K*C], k and v [src_n, K*C] (all float32 or
+    all bfloat16, their gradients in their own dtype; contiguous, on the
+    device; anything else raises before a launch).  The projections stay in
+    torch: q = x @ W_q and so on.  scale=None is C ** -0.5.  dropout, seed:
+    attention dropout as for `attend`.  Under torch.no_grad() with dropout ==
+    0 (evaluation) the call is layer.forward_fused: the same y, with no
+    [E, K] tensor allocated or kept."""
+    if not torch.is_grad_enabled() and dropout == 0:
+        _draw_seed(dropout, seed)   # the same argument checks
+        return layer.forward_fused(q, k, v, scale)
+    return _AttendDotFn.apply(q, k, v, layer, scale, dropout,
+                              _draw_seed(dropout, seed))

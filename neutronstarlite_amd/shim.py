@@ -152,6 +152,14 @@ def lib():
     l.nts_gatv2_forward_fused_bf16.restype = _i32
     l.nts_gatv2_forward_fused_plan.argtypes = (
         [_u32] * 2 + [_c.c_uint] * 3 + [_u32] * 2 + [_i32] + [_vp] * 6)
+    # fused dot-product attention forward (one pass over k and v)
+    for name in ("nts_dot_attention_forward_fused",
+                 "nts_dot_attention_forward_fused_bf16"):
+        getattr(l, name).argtypes = (
+            [_vp] + [_vp] * 4 + [_c.c_float] + [_vp] * 2 + [_u32] * 5)
+        getattr(l, name).restype = _i32
+    l.nts_dot_attention_forward_fused_plan.argtypes = (
+        l.nts_gatv2_forward_fused_plan.argtypes)
     # fused GAT training backward (recomputed weights, no per-edge state)
     l.nts_gat_backward_fused.argtypes = (
         [_vp] + [_vp] * 8 + [_c.c_float] + [_vp] * 4 + [_u32] * 7)
@@ -332,6 +340,25 @@ def gatv2_forward_fused_plan(f, heads, elem_bytes, row_alignment,
     out = [_i32(0) for _ in names]
     scratch = _c.c_ulonglong(0)
     lib().nts_gatv2_forward_fused_plan(
+        f, heads, elem_bytes, row_alignment, fp32_alignment, batch, edges,
+        1 if general else 0, *[_c.byref(o) for o in out], _c.byref(scratch))
+    plan = {n: o.value for n, o in zip(names, out)}
+    plan["scratch_bytes"] = scratch.value
+    return plan
+
+
+def dot_attention_forward_fused_plan(f, heads, elem_bytes, row_alignment,
+                                     fp32_alignment, batch, edges,
+                                     general=False):
+    """The launch decision of Stream.dot_attention_forward_fused[_bf16] (no
+    device access): the dict of gatv2_forward_fused_plan, whose geometry it
+    is.  row_alignment is the common alignment of q, k and v in bytes,
+    fp32_alignment that of the output."""
+    check_heads(f, heads)
+    names = ("form", "cols_per_lane", "lane_group", "slabs", "grid")
+    out = [_i32(0) for _ in names]
+    scratch = _c.c_ulonglong(0)
+    lib().nts_dot_attention_forward_fused_plan(
         f, heads, elem_bytes, row_alignment, fp32_alignment, batch, edges,
         1 if general else 0, *[_c.byref(o) for o in out], _c.byref(scratch))
     plan = {n: o.value for n, o in zip(names, out)}
@@ -877,6 +904,34 @@ class Stream:
         check_heads(f, heads)
         return self._lib.nts_gatv2_forward_fused_bf16(
             self.h, _vp(x_l_bf16), _vp(x_r_bf16), _vp(y_ptr), _vp(att), slope,
+            _vp(row_indices), _vp(column_offset), src_start, batch, edges, f,
+            heads)
+
+    # ---- fused dot-product attention forward: score, online softmax and
+    # aggregation from one load of every k row and every v row ----
+    def dot_attention_forward_fused(self, q, k, v, y_ptr, scale, row_indices,
+                                    column_offset, src_start, batch, edges, f,
+                                    heads):
+        """y[d, c] += sum over d's in-edges of softmax(scale * q[d, head] .
+        k[src, head])[e, c // C] * v[src, c]: edge_dot_heads on the scaled q,
+        the edge softmax and gather_by_dst_from_src_heads of v in one pass
+        that keeps nothing per edge and uses no atomics (bit-reproducible).
+        Honours edge_softmax_stable.  Returns 1 when it ran (or there was
+        nothing to do), 0 when C > 1024: nothing was launched and the caller
+        runs the three-entry chain."""
+        check_heads(f, heads)
+        return self._lib.nts_dot_attention_forward_fused(
+            self.h, _vp(q), _vp(k), _vp(v), _vp(y_ptr), scale,
+            _vp(row_indices), _vp(column_offset), src_start, batch, edges, f,
+            heads)
+
+    def dot_attention_forward_fused_bf16(self, q_bf16, k_bf16, v_bf16, y_ptr,
+                                         scale, row_indices, column_offset,
+                                         src_start, batch, edges, f, heads):
+        """dot_attention_forward_fused with q, k and v bfloat16."""
+        check_heads(f, heads)
+        return self._lib.nts_dot_attention_forward_fused_bf16(
+            self.h, _vp(q_bf16), _vp(k_bf16), _vp(v_bf16), _vp(y_ptr), scale,
             _vp(row_indices), _vp(column_offset), src_start, batch, edges, f,
             heads)
 

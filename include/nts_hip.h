@@ -1191,6 +1191,107 @@ void nts_gatv2_backward_fused_plan(nts_vid feature_size, nts_vid heads,
     int *lane_group, int *slabs, int *grid_csr, int *grid_csc,
     unsigned long long *scratch_bytes);
 
+/* ---- fused dot-product attention training (additive): no per-edge state ----
+ * nts_dot_attention_forward_fused_stats[_bf16] is
+ * nts_dot_attention_forward_fused[_bf16] (same plan, same launches'
+ * arithmetic, output bit-identical) whose kernels also leave the softmax
+ * statistics of every destination that has in-edges in ms, [batch_size,
+ * heads, 2] fp32, under the contract of nts_gatv2_forward_fused_stats:
+ * ms[d, h] = (M, S) with S = sum over d's in-edges of exp(score - M), M the
+ * running maximum in the stable mode and exactly 0 in the default mode.  An
+ * unsplit destination's item stores its own pair; the merge kernel stores
+ * (M, den) of a split one.  ms of a destination without in-edges is never
+ * written (and never read below).  ms must not be NULL.
+ *   nts_dot_attention_backward_fused[_bf16] is the backward for a caller that
+ * kept q, k, v, scale, the forward's output y and ms.  Per edge e = (u -> d)
+ * and head h over the head's columns c:
+ *   qs[c]   = scale * q[d, c]                ONE fp32 multiply, as the forward
+ *   score   = sum_c qs[c] * k[u, c]          the forward's fmaf chain and
+ *                                            butterfly
+ *   alpha   = exp(score - M[d, h]) / S[d, h]            a true division
+ *   gdot    = sum_c grad_output[d, c] * v[u, c]
+ *   D[d, h] = sum_c grad_output[d, c] * output[d, c]
+ *   gs      = alpha * (gdot - D[d, h])
+ *   grad_v[u, c] += alpha * grad_output[d, c]
+ *   grad_k[u, c] += gs * qs[c]
+ *   grad_q[d, c] += scale * sum_{e into d} gs * k[u, c]   scaled once per work
+ *                                                         item, at the store
+ * At the forward's form and R a recomputed score is the forward's bit for
+ * bit, so exp(score - M) never exceeds 1 in the stable mode.
+ *   Three launches.  (1) The record pass of nts_gatv2_backward_fused
+ * (NTS_KTAG_EDGE) writes {M, S, D, -} per (d, h) with in-edges, 16 bytes, into
+ * the stream-owned record scratch of nts_gat_backward_fused.  (2) The CSC walk
+ * (NTS_KTAG_BWD) over the items of column_offset keeps qs[d], grad_output[d]
+ * and d's record in registers and gathers k[u] and v[u] per in-edge: grad_q.
+ * (3) The CSR walk (NTS_KTAG_BWD) over the items of row_offset keeps k[u] and
+ * v[u] in registers and gathers q[d], grad_output[d] and d's record (one
+ * 16-byte load) per out-edge: grad_k and grad_v, two stores per item.
+ * column_indices holds global destination ids (d = column_indices[e] -
+ * dst_start).  Nothing sized by `edges` is allocated, read or written besides
+ * the two index lists; no dropout.
+ *   Forms and geometry are those of nts_dot_attention_forward_fused: fast (C
+ * a power of two, C / R <= 64; R = 4 / 2 / 1 the widest that divides C and
+ * that every pointer permits: R*4 bytes of alignment for grad_output, grad_q,
+ * grad_k, grad_v and fp32 rows, R*2 for bf16 rows), where every edge has two
+ * gathered rows in both walks, up to four edges are in flight with all their
+ * row loads issued before the first is consumed, and their partial scores and
+ * partial gdots are summed over the head's C / R lanes by one interleaved
+ * butterfly; general (any heads, C <= 1024, and whenever
+ * nts_heads_dbg_general is set), a wave per (item, head), lane l owning the
+ * head's columns l + 64*i, with 4 / 4 / 2 / 1 / 1 edges in flight for C up to
+ * 64 / 128 / 256 / 512 / 1024.  No sum spans work items: both walks run
+ * flattened (item, slab) tasks, without LDS.  A vertex that is one work item
+ * ends with a plain read-add-write, so its rows are bit-reproducible from call
+ * to call; a split one adds by fp32 atomics, one per (item, element), and
+ * needs no merge since every item holds the destination's whole (M, S, D).
+ *   All three gradients keep the += contract (the caller zeroes; rows without
+ * edges are untouched).  q, grad_q, output, grad_output and ms are
+ * destination-sized ([dst_end - dst_start, ...]), k, v, grad_k and grad_v
+ * source-sized ([src_end - src_start, feature_size]); q, k and v are all fp32
+ * or all bf16 (raw uint16_t, widened exactly), everything else is fp32.  The
+ * softmax mode is the stream's (it must be the forward's) and the call is
+ * recorded for nts_edge_softmax_stable_last.  The edge count is the caller's:
+ * no device-to-host copy, no synchronize beyond scratch growth.  Invalid
+ * heads abort as for the heads gathers.
+ *   Returns 1 when the backward ran or there was nothing to do (edges == 0 or
+ * no rows on either side: nothing launched or written); 0 when C > 1024:
+ * nothing is launched or written.
+ *   nts_dot_attention_backward_fused_plan reports the decision without
+ * touching a device (the launch takes it from the same function), with the
+ * outputs of nts_gatv2_backward_fused_plan; both grids are sized by items *
+ * slabs.  row_alignment_bytes is the common alignment of q, k and v,
+ * fp32_alignment_bytes that of grad_output, grad_q, grad_k and grad_v. */
+int nts_dot_attention_forward_fused_stats(nts_stream *s, const float *q,
+    const float *k, const float *v, float *output, float scale,
+    const nts_vid *row_indices, const nts_vid *column_offset,
+    nts_vid src_start, nts_vid batch_size, nts_vid edges,
+    nts_vid feature_size, nts_vid heads, float *ms);
+int nts_dot_attention_forward_fused_stats_bf16(nts_stream *s,
+    const uint16_t *q, const uint16_t *k, const uint16_t *v, float *output,
+    float scale, const nts_vid *row_indices, const nts_vid *column_offset,
+    nts_vid src_start, nts_vid batch_size, nts_vid edges,
+    nts_vid feature_size, nts_vid heads, float *ms);
+int nts_dot_attention_backward_fused(nts_stream *s, const float *q,
+    const float *k, const float *v, float scale, const float *output,
+    const float *ms, const float *grad_output, float *grad_q, float *grad_k,
+    float *grad_v, const nts_vid *row_indices, const nts_vid *column_offset,
+    const nts_vid *row_offset, const nts_vid *column_indices,
+    nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
+    nts_vid edges, nts_vid feature_size, nts_vid heads);
+int nts_dot_attention_backward_fused_bf16(nts_stream *s, const uint16_t *q,
+    const uint16_t *k, const uint16_t *v, float scale, const float *output,
+    const float *ms, const float *grad_output, float *grad_q, float *grad_k,
+    float *grad_v, const nts_vid *row_indices, const nts_vid *column_offset,
+    const nts_vid *row_offset, const nts_vid *column_indices,
+    nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
+    nts_vid edges, nts_vid feature_size, nts_vid heads);
+void nts_dot_attention_backward_fused_plan(nts_vid feature_size,
+    nts_vid heads, unsigned elem_bytes, unsigned row_alignment_bytes,
+    unsigned fp32_alignment_bytes, nts_vid src_rows, nts_vid dst_rows,
+    nts_vid edges, int general, int *form, int *cols_per_lane,
+    int *lane_group, int *slabs, int *grid_csr, int *grid_csc,
+    unsigned long long *scratch_bytes);
+
 /* Opt-in work-item reuse: with enable=1 the stream caches its two most
  * recent item decompositions keyed on (offset pointer, batch, edges) and
  * skips identical rebuilds.  ONLY safe while the caller keeps those

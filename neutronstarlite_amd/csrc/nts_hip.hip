@@ -2733,13 +2733,14 @@ __device__ __forceinline__ void dot_edges_seg(float &m, float &S,
 /* Fast form: the task and lane geometry of k_gatv2_fused_seg (a group of G
  * lanes per (item, slab of G*R columns), a head an aligned segment of L = C/R
  * lanes, lanes past the row's end whole segments that take no part). */
-template <int R, bool STABLE, typename T>
-NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_seg(
+template <int R, bool STABLE, bool STATS, typename T>
+NTS_NO_PK __device__ __forceinline__ void dot_fused_seg(
     const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
     const uint32_t *__restrict__ nbr, const T *__restrict__ q,
     const T *__restrict__ k, const T *__restrict__ v, float *__restrict__ out,
     float *__restrict__ scratch, float scale, uint32_t nbr_start, uint32_t f,
-    uint32_t K, uint32_t C, uint32_t G, uint32_t n_slabs) {
+    uint32_t K, uint32_t C, uint32_t G, uint32_t n_slabs,
+    float *__restrict__ ms) {
   const uint32_t n_items = *n_items_p;
   const uint32_t glane = threadIdx.x & (G - 1);
   const uint32_t L = C / R;
@@ -2767,6 +2768,13 @@ NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_seg(
 #pragma unroll
       for (int j = 0; j < R; ++j) acc[j] /= S;
       store_acc<R>(out + (uint64_t)im.v * f + col, acc, R, false);
+      if constexpr (STATS) {
+        if ((glane & (L - 1)) == 0) {
+          float *o = ms + 2 * ((uint64_t)im.v * K + col / C);
+          o[0] = m;
+          o[1] = S;
+        }
+      }
     } else {
       float *rec = scratch + (uint64_t)it * (f + 2 * K);
 #pragma unroll
@@ -2777,6 +2785,30 @@ NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_seg(
       }
     }
   }
+}
+template <int R, bool STABLE, typename T>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_seg(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ nbr, const T *__restrict__ q,
+    const T *__restrict__ k, const T *__restrict__ v, float *__restrict__ out,
+    float *__restrict__ scratch, float scale, uint32_t nbr_start, uint32_t f,
+    uint32_t K, uint32_t C, uint32_t G, uint32_t n_slabs) {
+  dot_fused_seg<R, STABLE, false, T>(items, n_items_p, nbr, q, k, v, out,
+                                     scratch, scale, nbr_start, f, K, C, G,
+                                     n_slabs, nullptr);
+}
+/* the training twin: an unsplit item also leaves its (m, S) in ms[d, k] */
+template <int R, bool STABLE, typename T>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_seg_stats(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ nbr, const T *__restrict__ q,
+    const T *__restrict__ k, const T *__restrict__ v, float *__restrict__ out,
+    float *__restrict__ scratch, float scale, uint32_t nbr_start, uint32_t f,
+    uint32_t K, uint32_t C, uint32_t G, uint32_t n_slabs,
+    float *__restrict__ ms) {
+  dot_fused_seg<R, STABLE, true, T>(items, n_items_p, nbr, q, k, v, out,
+                                    scratch, scale, nbr_start, f, K, C, G,
+                                    n_slabs, ms);
 }
 
 /* general form: NE consecutive edges of one (item, head) across the wave;
@@ -2817,13 +2849,13 @@ __device__ __forceinline__ void dot_edges_wave(float &m, float &S,
  * owns the head's columns l + 64*i, i < NCH, as in k_gatv2_fused_wave.  Two
  * gathered rows per edge: NE = 4 / 4 / 2 / 1 / 1 edges in flight at NCH = 1 /
  * 2 / 4 / 8 / 16, so that both rows of every edge stay in registers. */
-template <int NCH, bool STABLE, typename T>
-NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_wave(
+template <int NCH, bool STABLE, bool STATS, typename T>
+NTS_NO_PK __device__ __forceinline__ void dot_fused_wave(
     const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
     const uint32_t *__restrict__ nbr, const T *__restrict__ q,
     const T *__restrict__ k, const T *__restrict__ v, float *__restrict__ out,
     float *__restrict__ scratch, float scale, uint32_t nbr_start, uint32_t f,
-    uint32_t K, uint32_t C) {
+    uint32_t K, uint32_t C, float *__restrict__ ms) {
   constexpr int NE = NCH <= 2 ? 4 : NCH <= 8 ? 8 / NCH : 1;
   const uint32_t n_items = *n_items_p;
   const WaveId w = wave_id();
@@ -2851,6 +2883,13 @@ NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_wave(
 #pragma unroll
       for (int i = 0; i < NCH; ++i)
         if (w.lane + 64 * i < C) o[64 * i] += acc[i] / S;
+      if constexpr (STATS) {
+        if (w.lane == 0) {
+          float *p = ms + 2 * ((uint64_t)im.v * K + head);
+          p[0] = m;
+          p[1] = S;
+        }
+      }
     } else {
       float *rec = scratch + (uint64_t)it * (f + 2 * K);
 #pragma unroll
@@ -2862,6 +2901,27 @@ NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_wave(
       }
     }
   }
+}
+template <int NCH, bool STABLE, typename T>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_wave(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ nbr, const T *__restrict__ q,
+    const T *__restrict__ k, const T *__restrict__ v, float *__restrict__ out,
+    float *__restrict__ scratch, float scale, uint32_t nbr_start, uint32_t f,
+    uint32_t K, uint32_t C) {
+  dot_fused_wave<NCH, STABLE, false, T>(items, n_items_p, nbr, q, k, v, out,
+                                        scratch, scale, nbr_start, f, K, C,
+                                        nullptr);
+}
+template <int NCH, bool STABLE, typename T>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_wave_stats(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const uint32_t *__restrict__ nbr, const T *__restrict__ q,
+    const T *__restrict__ k, const T *__restrict__ v, float *__restrict__ out,
+    float *__restrict__ scratch, float scale, uint32_t nbr_start, uint32_t f,
+    uint32_t K, uint32_t C, float *__restrict__ ms) {
+  dot_fused_wave<NCH, STABLE, true, T>(items, n_items_p, nbr, q, k, v, out,
+                                       scratch, scale, nbr_start, f, K, C, ms);
 }
 
 /* ---- GAT training backward that recomputes the attention weights ---- */
@@ -3600,6 +3660,202 @@ NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_bwd_wave(
       }
       __syncthreads();
     }
+  }
+}
+
+/* ---- dot-product attention backward that recomputes the weights ---- */
+/* A score scale * q[d] . k[u] is a function of two rows, so with (M, S) per
+ * (destination, head) from the stats forward and D[d, h] = grad_y[d] . y[d]
+ * (k_gatv2_bwd_record's records, reused as they are) an edge's alpha =
+ * exp(score - M) / S and gs = alpha * (gdot - D), gdot = grad_y[d] . v[u], are
+ * recomputed from rows both walks gather anyway:
+ *   CSC walk (items of column_offset): qs[d] = scale * q[d], grad_y[d] and
+ *     d's record in registers, k[u] and v[u] gathered:
+ *     grad_q[d] += scale * sum gs * k[u]  (scaled once per item, at the store);
+ *   CSR walk (items of row_offset): k[u] and v[u] in registers, q[d] (scaled
+ *     as it arrives), grad_y[d] and d's record gathered:
+ *     grad_k[u] += sum gs * qs[d],  grad_v[u] += sum alpha * grad_y[d].
+ * In both an edge is (own pair o1, o2; gathered pair x1, x2) with score =
+ * qs . k over (o1, x1) and gdot = grad_y . v over (o2, x2), so one edge block
+ * serves both; the CSR walk only adds the second accumulator.  The score is
+ * the forward's expression, fmaf(qs[j], k[j], .) over the lane's columns in
+ * order and the forward's butterfly, so at the same form and R it is the
+ * forward's score bit for bit.  Up to four edges are in flight, all their row
+ * loads issued before the first is consumed, partial score and partial gdot
+ * summed by ONE interleaved butterfly (V2bSumSeg / V2bSumWave).
+ *   No sum spans items: both walks flatten (item, slab) tasks, there is no LDS
+ * and no atomic for an unsplit vertex (a plain read-add-write, bit-
+ * reproducible); a split vertex adds by fp32 atomics, one per (item, element),
+ * and needs no merge since every item holds the destination's whole
+ * (M, S, D).  Built without packed fp32 instructions. */
+template <typename T>
+struct DotBwd {
+  const uint32_t *__restrict__ nbr;
+  const T *__restrict__ q;
+  const T *__restrict__ k;
+  const T *__restrict__ v;
+  const float *__restrict__ gy;
+  const float4 *__restrict__ recs;
+  float *__restrict__ grad_1;   /* CSC: grad_q, CSR: grad_k */
+  float *__restrict__ grad_2;   /* CSR: grad_v */
+  float scale;
+  uint32_t nbr_start, f, K, C;
+};
+
+/* NE consecutive edges of one (item, lane's N columns).  CSC: o1 = qs[d], o2 =
+ * grad_y[d], x1 = k[u], x2 = v[u].  CSR: o1 = k[u], o2 = v[u], x1 = qs[d], x2
+ * = grad_y[d].  a1 += gs * x1 (grad_q unscaled / grad_k); CSR: a2 += alpha *
+ * x2 (grad_v). */
+template <int N, int NE, bool STABLE, bool CSR, typename T, class Load,
+          class Sum2>
+__device__ __forceinline__ void dotb_edges(float (&a1)[N], float (&a2)[N],
+                                           const DotBwd<T> &g, uint32_t e,
+                                           uint32_t col, uint32_t head,
+                                           const float (&o1)[N],
+                                           const float (&o2)[N],
+                                           const float4 &rec_own,
+                                           const Load &load, const Sum2 &sum2) {
+  uint64_t off[NE];
+  float x1[NE][N], x2[NE][N], sc[NE], gd[NE], alpha[NE], gs[NE];
+  float4 rec[NE];
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    const uint32_t n = g.nbr[e + k] - g.nbr_start;
+    off[k] = (uint64_t)n * g.f + col;
+    if constexpr (CSR) rec[k] = g.recs[(uint64_t)n * g.K + head];
+    else rec[k] = rec_own;
+  }
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    if constexpr (CSR) load(g.q + off[k], x1[k]);
+    else load(g.k + off[k], x1[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    if constexpr (CSR) load(g.gy + off[k], x2[k]);
+    else load(g.v + off[k], x2[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    sc[k] = gd[k] = 0.f;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      if constexpr (CSR) {
+        x1[k][j] *= g.scale;   /* qs = scale * q, one fp32 multiply */
+        sc[k] = fmaf(x1[k][j], o1[j], sc[k]);
+        gd[k] = fmaf(x2[k][j], o2[j], gd[k]);
+      } else {
+        sc[k] = fmaf(o1[j], x1[k][j], sc[k]);
+        gd[k] = fmaf(o2[j], x2[k][j], gd[k]);
+      }
+    }
+  }
+  sum2(sc, gd);
+  v2b_weights<NE, STABLE>(alpha, gs, sc, gd, rec);
+#pragma unroll
+  for (int k = 0; k < NE; ++k)
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      a1[j] = fmaf(gs[k], x1[k][j], a1[j]);
+      if constexpr (CSR) a2[j] = fmaf(alpha[k], x2[k][j], a2[j]);
+    }
+}
+
+/* all edges of one item into (a1, a2), NE at a time and then one by one; the
+ * item's own rows and (CSC) its record are loaded here and stay in registers */
+template <int N, int NE, bool STABLE, bool CSR, typename T, class Load,
+          class Sum2>
+__device__ __forceinline__ void dotb_item(float (&a1)[N], float (&a2)[N],
+                                          const DotBwd<T> &g, const Item &im,
+                                          uint32_t col, uint32_t head,
+                                          const Load &load, const Sum2 &sum2) {
+  const uint64_t own = (uint64_t)im.v * g.f + col;
+  float o1[N], o2[N];
+  float4 rec_own = make_float4(0.f, 1.f, 0.f, 0.f);
+  if constexpr (CSR) {
+    load(g.k + own, o1);
+    load(g.v + own, o2);
+  } else {
+    load(g.q + own, o1);
+#pragma unroll
+    for (int j = 0; j < N; ++j) o1[j] *= g.scale;
+    load(g.gy + own, o2);
+    rec_own = g.recs[(uint64_t)im.v * g.K + head];
+  }
+  const uint32_t e_end = im.e0 + im.cnt;
+  uint32_t e = im.e0;
+  for (; e + NE <= e_end; e += NE)
+    dotb_edges<N, NE, STABLE, CSR>(a1, a2, g, e, col, head, o1, o2, rec_own,
+                                   load, sum2);
+  for (; e < e_end; ++e)
+    dotb_edges<N, 1, STABLE, CSR>(a1, a2, g, e, col, head, o1, o2, rec_own,
+                                  load, sum2);
+  if constexpr (!CSR) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) a1[j] *= g.scale;
+  }
+}
+
+/* Fast form, C a power of two and L = C/R <= 64: the geometry of
+ * k_dot_fused_seg (G lanes per (item, slab) task, a lane R consecutive
+ * columns of one head, slabs of whole heads, lanes past the row's end whole
+ * segments that take no part); NE = edges in flight. */
+template <int R, int NE, bool STABLE, bool CSR, typename T>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_bwd_seg(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const DotBwd<T> g, uint32_t G, uint32_t n_slabs) {
+  const uint32_t n_items = *n_items_p;
+  const uint32_t glane = threadIdx.x & (G - 1);
+  const uint32_t L = g.C / R;
+  const uint64_t total = (uint64_t)n_items * n_slabs;
+  const uint64_t stride = (gridDim.x * NTS_BLOCK) / G;
+  for (uint64_t t = (blockIdx.x * NTS_BLOCK + threadIdx.x) / G; t < total;
+       t += stride) {
+    const uint32_t col = (uint32_t)(t % n_slabs) * G * R + glane * R;
+    if (col >= g.f) continue;
+    const Item im = load_item(items, (uint32_t)(t / n_slabs));
+    float a1[R] = {}, a2[R] = {};
+    dotb_item<R, NE, STABLE, CSR>(a1, a2, g, im, col, col / g.C,
+                                  V2bLoadSeg<R>{}, V2bSumSeg{L});
+    const uint64_t own = (uint64_t)im.v * g.f + col;
+    store_acc<R>(g.grad_1 + own, a1, R, im.shared);
+    if constexpr (CSR) store_acc<R>(g.grad_2 + own, a2, R, im.shared);
+  }
+}
+
+/* General form, any K and C <= 64*NCH: a wave per (item, head), lane l owns
+ * the head's columns l + 64*i (dead ones hold zeros and are never stored).
+ * Two gathered rows per edge beside the two own rows: NE = 4 / 4 / 2 / 1 / 1
+ * edges in flight at NCH = 1 / 2 / 4 / 8 / 16, as in k_dot_fused_wave, so
+ * that both rows of every edge stay in registers. */
+template <int NCH, bool STABLE, bool CSR, typename T>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_bwd_wave(
+    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
+    const DotBwd<T> g) {
+  constexpr int NE = NCH <= 2 ? 4 : NCH <= 8 ? 8 / NCH : 1;
+  const uint32_t n_items = *n_items_p;
+  const WaveId w = wave_id();
+  const uint64_t total = (uint64_t)n_items * g.K;
+  for (uint64_t t = w.wave; t < total; t += w.n_waves) {
+    const uint32_t head = (uint32_t)(t % g.K);
+    const Item im = load_item(items, (uint32_t)(t / g.K));
+    const uint32_t col = head * g.C + w.lane;
+    float a1[NCH] = {}, a2[NCH] = {};
+    dotb_item<NCH, NE, STABLE, CSR>(a1, a2, g, im, col, head,
+                                    V2bLoadWave<NCH>{w.lane, g.C},
+                                    V2bSumWave{});
+    const uint64_t own = (uint64_t)im.v * g.f + col;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+      if (w.lane + 64 * i < g.C) {
+        if (im.shared) {
+          atomicAdd(&g.grad_1[own + 64 * i], a1[i]);
+          if constexpr (CSR) atomicAdd(&g.grad_2[own + 64 * i], a2[i]);
+        } else {
+          g.grad_1[own + 64 * i] += a1[i];
+          if constexpr (CSR) g.grad_2[own + 64 * i] += a2[i];
+        }
+      }
   }
 }
 
@@ -5890,8 +6146,52 @@ void nts_gatv2_forward_fused_plan(nts_vid feature_size, nts_vid heads,
 
 /* ---- fused dot-product attention forward (additive; see nts_hip.h) ---- */
 extern "C++" {
+/* the launches of the stats entries: the twins that also store (M, S) */
+template <typename T>
+static void launch_dot_fused_stats(nts_stream *s, const Gatv2FusedPlan &pl,
+                                   const EdgeItems &p, const T *q, const T *k,
+                                   const T *v, float *out, float *scratch,
+                                   float scale, const nts_vid *row_indices,
+                                   const nts_vid *offset, nts_vid src_start,
+                                   nts_vid f, nts_vid K, float *ms) {
+  const bool st = s->softmax_stable;
+  const uint32_t C = f / K;
+  if (pl.form == 1) {
+#define NTS_K(RR)                                                             \
+  (st ? k_dot_fused_seg_stats<RR, true, T>                                    \
+      : k_dot_fused_seg_stats<RR, false, T>)
+    hipLaunchKernelGGL(pl.R == 4 ? NTS_K(4) : pl.R == 2 ? NTS_K(2) : NTS_K(1),
+                       dim3(pl.grid), dim3(NTS_BLOCK), 0, s->stream,
+                       p.ib->items, p.ib->counter, row_indices, q, k, v, out,
+                       scratch, scale, src_start, f, K, C, pl.G, pl.slabs, ms);
+#undef NTS_K
+  } else {
+    /* indexed by log2(NCH) */
+    static const decltype(&k_dot_fused_wave_stats<1, false, T>)
+        kernels[2][5] = {{k_dot_fused_wave_stats<1, false, T>,
+                          k_dot_fused_wave_stats<2, false, T>,
+                          k_dot_fused_wave_stats<4, false, T>,
+                          k_dot_fused_wave_stats<8, false, T>,
+                          k_dot_fused_wave_stats<16, false, T>},
+                         {k_dot_fused_wave_stats<1, true, T>,
+                          k_dot_fused_wave_stats<2, true, T>,
+                          k_dot_fused_wave_stats<4, true, T>,
+                          k_dot_fused_wave_stats<8, true, T>,
+                          k_dot_fused_wave_stats<16, true, T>}};
+    hipLaunchKernelGGL(kernels[st][__builtin_ctz(pl.nch)], dim3(pl.grid),
+                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                       p.ib->counter, row_indices, q, k, v, out, scratch,
+                       scale, src_start, f, K, C, ms);
+  }
+  if (scratch)
+    hipLaunchKernelGGL(k_gatv2_fused_merge_stats, dim3(p.grid),
+                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                       p.ib->counter, offset, scratch, out, NTS_SPLIT, f, K, C,
+                       ms);
+}
+
 /* The plan is plan_gatv2_fused's: q, k and v are the rows, the output the
- * only fp32 operand. */
+ * only fp32 operand.  ms != nullptr: the stats entries. */
 template <typename T>
 static int dot_attention_forward_fused(nts_stream *s, const char *entry,
                                        const T *q, const T *k, const T *v,
@@ -5899,7 +6199,8 @@ static int dot_attention_forward_fused(nts_stream *s, const char *entry,
                                        const nts_vid *row_indices,
                                        const nts_vid *offset,
                                        nts_vid src_start, nts_vid batch,
-                                       nts_vid edges, nts_vid f, nts_vid K) {
+                                       nts_vid edges, nts_vid f, nts_vid K,
+                                       float *ms = nullptr) {
   check_heads(entry, f, K);
   s->softmax_stable_last = s->softmax_stable;
   if (!batch || !edges) return 1;
@@ -5913,6 +6214,12 @@ static int dot_attention_forward_fused(nts_stream *s, const char *entry,
   const bool st = s->softmax_stable;
   const uint32_t C = f / K;
   Tic t(s, NTS_KTAG_FWD);
+  if (ms) {
+    launch_dot_fused_stats(s, pl, p, q, k, v, out, scratch, scale, row_indices,
+                           offset, src_start, f, K, ms);
+    dbg_sync(s, "k_dot_fused (stats)");
+    return 1;
+  }
   if (pl.form == 1) {
 #define NTS_K(RR)                                                             \
   (st ? k_dot_fused_seg<RR, true, T> : k_dot_fused_seg<RR, false, T>)
@@ -5970,6 +6277,32 @@ int nts_dot_attention_forward_fused_bf16(nts_stream *s, const uint16_t *q,
       s, "nts_dot_attention_forward_fused_bf16", q, k, v, output, scale,
       row_indices, column_offset, src_start, batch_size, edges, feature_size,
       heads);
+}
+
+int nts_dot_attention_forward_fused_stats(nts_stream *s, const float *q,
+                                          const float *k, const float *v,
+                                          float *output, float scale,
+                                          const nts_vid *row_indices,
+                                          const nts_vid *column_offset,
+                                          nts_vid src_start,
+                                          nts_vid batch_size, nts_vid edges,
+                                          nts_vid feature_size, nts_vid heads,
+                                          float *ms) {
+  return dot_attention_forward_fused(
+      s, "nts_dot_attention_forward_fused_stats", q, k, v, output, scale,
+      row_indices, column_offset, src_start, batch_size, edges, feature_size,
+      heads, ms);
+}
+
+int nts_dot_attention_forward_fused_stats_bf16(
+    nts_stream *s, const uint16_t *q, const uint16_t *k, const uint16_t *v,
+    float *output, float scale, const nts_vid *row_indices,
+    const nts_vid *column_offset, nts_vid src_start, nts_vid batch_size,
+    nts_vid edges, nts_vid feature_size, nts_vid heads, float *ms) {
+  return dot_attention_forward_fused(
+      s, "nts_dot_attention_forward_fused_stats_bf16", q, k, v, output, scale,
+      row_indices, column_offset, src_start, batch_size, edges, feature_size,
+      heads, ms);
 }
 
 void nts_dot_attention_forward_fused_plan(
@@ -6353,6 +6686,147 @@ void nts_gatv2_backward_fused_plan(nts_vid feature_size, nts_vid heads,
                                    unsigned long long *scratch_bytes) {
   check_heads("nts_gatv2_backward_fused_plan", feature_size, heads);
   const GatBwdPlan p = plan_gatv2_backward(
+      feature_size, heads, elem_bytes, row_alignment_bytes,
+      fp32_alignment_bytes, src_rows, dst_rows, edges, general != 0);
+  if (form) *form = p.form;
+  if (cols_per_lane) *cols_per_lane = (int)p.R;
+  if (lane_group) *lane_group = (int)p.G;
+  if (slabs) *slabs = (int)p.slabs;
+  if (grid_csr) *grid_csr = (int)p.grid_csr;
+  if (grid_csc) *grid_csc = (int)p.grid_csc;
+  if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+}
+
+/* ---- fused dot-product attention backward (additive; see nts_hip.h) ---- */
+extern "C++" {
+/* Edges in flight of the fast form's walks.  Four in both: the R = 4 fp32
+ * instantiations compile without scratch (DESIGN.md section 3 has the register
+ * counts). */
+constexpr int NTS_DOTB_NE_CSC = 4;
+constexpr int NTS_DOTB_NE_CSR = 4;
+
+template <bool CSR, typename T>
+static void launch_dot_bwd_walk(nts_stream *s, const EdgeItems &p,
+                                const GatBwdPlan &pl, uint32_t grid,
+                                const DotBwd<T> &g) {
+  const bool st = s->softmax_stable;
+  constexpr int NE = CSR ? NTS_DOTB_NE_CSR : NTS_DOTB_NE_CSC;
+  if (pl.form == 1) {
+#define NTS_K(RR)                                                             \
+  (st ? k_dot_bwd_seg<RR, NE, true, CSR, T>                                   \
+      : k_dot_bwd_seg<RR, NE, false, CSR, T>)
+    hipLaunchKernelGGL(pl.R == 4 ? NTS_K(4) : pl.R == 2 ? NTS_K(2) : NTS_K(1),
+                       dim3(grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                       p.ib->counter, g, pl.G, pl.slabs);
+#undef NTS_K
+  } else {
+    /* indexed by log2(NCH) */
+    static const decltype(&k_dot_bwd_wave<1, false, CSR, T>) kernels[2][5] = {
+        {k_dot_bwd_wave<1, false, CSR, T>, k_dot_bwd_wave<2, false, CSR, T>,
+         k_dot_bwd_wave<4, false, CSR, T>, k_dot_bwd_wave<8, false, CSR, T>,
+         k_dot_bwd_wave<16, false, CSR, T>},
+        {k_dot_bwd_wave<1, true, CSR, T>, k_dot_bwd_wave<2, true, CSR, T>,
+         k_dot_bwd_wave<4, true, CSR, T>, k_dot_bwd_wave<8, true, CSR, T>,
+         k_dot_bwd_wave<16, true, CSR, T>}};
+    hipLaunchKernelGGL(kernels[st][__builtin_ctz(pl.nch)], dim3(grid),
+                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                       p.ib->counter, g);
+  }
+}
+
+/* The plan is plan_gat_backward's: both walks flatten (item, slab) tasks.
+ * The record pass under NTS_KTAG_EDGE, the two walks under NTS_KTAG_BWD.
+ * Everything over the CSC items runs before the CSR items are asked for: the
+ * stream keeps two item buffers and a third request may rebuild the first. */
+template <typename T>
+static int dot_attention_backward_fused(
+    nts_stream *s, const char *entry, const T *q, const T *k, const T *v,
+    float scale, const float *y, const float *ms, const float *gy,
+    float *grad_q, float *grad_k, float *grad_v, const nts_vid *row_indices,
+    const nts_vid *column_offset, const nts_vid *row_offset,
+    const nts_vid *column_indices, nts_vid src_start, nts_vid src_end,
+    nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid f, nts_vid K) {
+  check_heads(entry, f, K);
+  s->softmax_stable_last = s->softmax_stable;
+  const uint32_t src_rows = src_end > src_start ? src_end - src_start : 0;
+  const uint32_t dst_rows = dst_end > dst_start ? dst_end - dst_start : 0;
+  if (!edges || !src_rows || !dst_rows) return 1;
+  const GatBwdPlan pl = plan_gat_backward(
+      f, K, sizeof(T), (uintptr_t)q | (uintptr_t)k | (uintptr_t)v,
+      (uintptr_t)gy | (uintptr_t)grad_q | (uintptr_t)grad_k |
+          (uintptr_t)grad_v,
+      src_rows, dst_rows, edges, s->heads_general);
+  if (!pl.form) return 0;
+  const uint32_t C = f / K;
+  const EdgeItems csc = edge_items_known(s, column_offset, dst_rows, edges);
+  float4 *recs = get_rec_scratch(s, pl.scratch_bytes);
+  {
+    Tic t(s, NTS_KTAG_EDGE);
+    uint32_t G = 1;
+    while (G < C && G < 64) G *= 2;
+    hipLaunchKernelGGL(k_gatv2_bwd_record,
+                       dim3(grid_for((uint64_t)dst_rows * K * G)),
+                       dim3(NTS_BLOCK), 0, s->stream, gy, y, ms, column_offset,
+                       recs, dst_rows, f, K, C, G);
+    dbg_sync(s, "k_gatv2_bwd_record (dot)");
+  }
+  {
+    Tic t(s, NTS_KTAG_BWD);
+    launch_dot_bwd_walk<false>(
+        s, csc, pl, pl.grid_csc,
+        DotBwd<T>{row_indices, q, k, v, gy, recs, grad_q, nullptr, scale,
+                  src_start, f, K, C});
+    dbg_sync(s, "k_dot_bwd (CSC walk)");
+  }
+  const EdgeItems csr = edge_items_known(s, row_offset, src_rows, edges);
+  Tic t(s, NTS_KTAG_BWD);
+  launch_dot_bwd_walk<true>(
+      s, csr, pl, pl.grid_csr,
+      DotBwd<T>{column_indices, q, k, v, gy, recs, grad_k, grad_v, scale,
+                dst_start, f, K, C});
+  dbg_sync(s, "k_dot_bwd (CSR walk)");
+  return 1;
+}
+}  // extern "C++"
+
+int nts_dot_attention_backward_fused(
+    nts_stream *s, const float *q, const float *k, const float *v, float scale,
+    const float *output, const float *ms, const float *grad_output,
+    float *grad_q, float *grad_k, float *grad_v, const nts_vid *row_indices,
+    const nts_vid *column_offset, const nts_vid *row_offset,
+    const nts_vid *column_indices, nts_vid src_start, nts_vid src_end,
+    nts_vid dst_start, nts_vid dst_end, nts_vid edges, nts_vid feature_size,
+    nts_vid heads) {
+  return dot_attention_backward_fused(
+      s, "nts_dot_attention_backward_fused", q, k, v, scale, output, ms,
+      grad_output, grad_q, grad_k, grad_v, row_indices, column_offset,
+      row_offset, column_indices, src_start, src_end, dst_start, dst_end,
+      edges, feature_size, heads);
+}
+
+int nts_dot_attention_backward_fused_bf16(
+    nts_stream *s, const uint16_t *q, const uint16_t *k, const uint16_t *v,
+    float scale, const float *output, const float *ms,
+    const float *grad_output, float *grad_q, float *grad_k, float *grad_v,
+    const nts_vid *row_indices, const nts_vid *column_offset,
+    const nts_vid *row_offset, const nts_vid *column_indices,
+    nts_vid src_start, nts_vid src_end, nts_vid dst_start, nts_vid dst_end,
+    nts_vid edges, nts_vid feature_size, nts_vid heads) {
+  return dot_attention_backward_fused(
+      s, "nts_dot_attention_backward_fused_bf16", q, k, v, scale, output, ms,
+      grad_output, grad_q, grad_k, grad_v, row_indices, column_offset,
+      row_offset, column_indices, src_start, src_end, dst_start, dst_end,
+      edges, feature_size, heads);
+}
+
+void nts_dot_attention_backward_fused_plan(
+    nts_vid feature_size, nts_vid heads, unsigned elem_bytes,
+    unsigned row_alignment_bytes, unsigned fp32_alignment_bytes,
+    nts_vid src_rows, nts_vid dst_rows, nts_vid edges, int general, int *form,
+    int *cols_per_lane, int *lane_group, int *slabs, int *grid_csr,
+    int *grid_csc, unsigned long long *scratch_bytes) {
+  check_heads("nts_dot_attention_backward_fused_plan", feature_size, heads);
+  const GatBwdPlan p = plan_gat_backward(
       feature_size, heads, elem_bytes, row_alignment_bytes,
       fp32_alignment_bytes, src_rows, dst_rows, edges, general != 0);
   if (form) *form = p.form;

@@ -70,6 +70,11 @@ evaluation (`forward_fused`, `attend_dot` under torch.no_grad()) is one entry
 of its own (nts_dot_attention_forward_fused[_bf16]) that reads k[src] and
 v[src] once per edge with the softmax evaluated online and keeps nothing per
 edge.  q, k and v are all float32 or all bfloat16.
+DotAttentionLayer.forward_recompute (`attend_dot` with recompute=True) trains
+without per-edge state as the GATv2 layer does: the fused forward also stores
+ms (nts_dot_attention_forward_fused_stats[_bf16]) and the backward
+(nts_dot_attention_backward_fused[_bf16]) recomputes every score from the
+rows its two walks gather; it keeps (q, k, v, scale, y, ms).
 
 bfloat16 feature rows: `h` of GATLayer and `x_l` / `x_r` of GATv2Layer may be
 torch.bfloat16.  The f-wide passes then read 2-byte rows through the *_bf16
@@ -1035,9 +1040,70 @@ class DotAttentionLayer(_EdgeLayer):
             return self.forward(q, k, v, scale)[0]
         return y
 
+    def forward_recompute(self, q: torch.Tensor, k: torch.Tensor,
+                          v: torch.Tensor, scale=None):
+        """The forward for training without per-edge state: y of
+        forward_fused (bit for bit) and a `saved` of (q, k, v, scale, y, ms)
+        alone, ms [dst_n, K, 2] being the softmax maximum and denominator per
+        (destination, head) that the forward's kernels leave behind
+        (Stream.dot_attention_forward_fused_stats).  `backward` recomputes
+        every score and weight from them
+        (Stream.dot_attention_backward_fused).  It reads saved["y"], which is
+        the returned tensor itself: do not modify y in place before the
+        backward (`attend_dot` saves it through autograd, which then raises).
+        Neither call allocates, writes or keeps an [E, K] tensor.  Inputs and
+        checks as for forward; either softmax mode; no dropout.  A head wider
+        than 1024 columns has no such form: then this is forward(q, k, v,
+        scale)."""
+        ch, st, E, K = self.ch, self.stream, self.E, self.heads
+        f, scale = self._check_inputs(q, k, v, scale)
+        bf16 = q.dtype == torch.bfloat16
+        if not shim.dot_attention_backward_fused_plan(
+                f, K, 2 if bf16 else 4, 256, 256, ch.src_n, ch.dst_n,
+                E)["form"]:
+            return self.forward(q, k, v, scale)
+        st.items_reuse(1)
+        y = torch.zeros(ch.dst_n, f, device=q.device)
+        # rows of destinations without in-edges are never written or read
+        ms = torch.empty(ch.dst_n, K, 2, device=q.device)
+        ran = (st.dot_attention_forward_fused_stats_bf16 if bf16
+               else st.dot_attention_forward_fused_stats)(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), y.data_ptr(), scale,
+            ch.row_indices.data_ptr(), ch.column_offset.data_ptr(), ch.src_s,
+            ch.dst_n, E, f, K, ms.data_ptr())
+        if not ran:   # the two plans share their width limit
+            raise RuntimeError(
+                "dot_attention_forward_fused_stats has no form here")
+        return y, {"q": q, "k": k, "v": v, "scale": scale, "y": y, "ms": ms,
+                   "recompute": True}
+
+    def _backward_recompute(self, grad_y, saved):
+        ch, st, E, K = self.ch, self.stream, self.E, self.heads
+        q, k, v = saved["q"], saved["k"], saved["v"]
+        f = int(q.shape[1])
+        dev = grad_y.device
+        st.items_reuse(1)
+        grad_q = torch.zeros(ch.dst_n, f, device=dev)
+        grad_k = torch.zeros(ch.src_n, f, device=dev)
+        grad_v = torch.zeros(ch.src_n, f, device=dev)
+        ran = (st.dot_attention_backward_fused_bf16
+               if q.dtype == torch.bfloat16
+               else st.dot_attention_backward_fused)(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), saved["scale"],
+            saved["y"].data_ptr(), saved["ms"].data_ptr(), grad_y.data_ptr(),
+            grad_q.data_ptr(), grad_k.data_ptr(), grad_v.data_ptr(),
+            ch.row_indices.data_ptr(), ch.column_offset.data_ptr(),
+            ch.row_offset.data_ptr(), ch.column_indices.data_ptr(), ch.src_s,
+            ch.src_e, ch.dst_s, ch.dst_e, E, f, K)
+        if not ran:   # forward_recompute never saves such a width
+            raise RuntimeError(
+                "dot_attention_backward_fused has no form for this width")
+        return grad_q, grad_k, grad_v
+
     def backward(self, grad_y: torch.Tensor, saved):
         """Returns (grad_q[dst_n, K*C], grad_k[src_n, K*C], grad_v[src_n,
-        K*C]), all float32."""
+        K*C]), all float32.  A `saved` of forward_recompute runs the
+        recomputing backward, with the same shapes and dtypes."""
         ch, st, E, K = self.ch, self.stream, self.E, self.heads
         q, k, v, scale = saved["q"], saved["k"], saved["v"], saved["scale"]
         f = int(q.shape[1])
@@ -1045,6 +1111,8 @@ class DotAttentionLayer(_EdgeLayer):
                 or int(grad_y.shape[1]) != f:
             raise ValueError("grad_y does not match the saved forward input")
         self._check_rows("grad_y", grad_y, ch.dst_n, f)
+        if "recompute" in saved:
+            return self._backward_recompute(grad_y, saved)
         dev = grad_y.device
         bf16 = q.dtype == torch.bfloat16
         st.items_reuse(1)
@@ -1097,23 +1165,35 @@ class _AttendDotFn(torch.autograd.Function):
     """torch.autograd bridge over DotAttentionLayer.forward/backward."""
 
     @staticmethod
-    def forward(ctx, q, k, v, layer, scale, dropout=0.0, seed=0):
-        y, saved = layer.forward(q.detach(), k.detach(), v.detach(), scale,
-                                 dropout, seed)
+    def forward(ctx, q, k, v, layer, scale, dropout=0.0, seed=0,
+                recompute=False):
+        args = (q.detach(), k.detach(), v.detach(), scale)
+        if recompute:
+            y, saved = layer.forward_recompute(*args)
+            if "recompute" in saved:
+                # the backward reads y: saved through autograd, so that an
+                # in-place change of attend_dot's output raises there
+                saved = {n: t for n, t in saved.items() if n != "y"}
+                ctx.save_for_backward(y)
+        else:
+            y, saved = layer.forward(*args, dropout, seed)
         ctx.layer, ctx.saved = layer, saved
         return y
 
     @staticmethod
     def backward(ctx, grad_y):
-        grads = ctx.layer.backward(grad_y.contiguous(), ctx.saved)
+        saved = ctx.saved
+        if "recompute" in saved:
+            saved = dict(saved, y=ctx.saved_tensors[0])
+        grads = ctx.layer.backward(grad_y.contiguous(), saved)
         # fp32 out of the kernels; bf16 only if the rows themselves were
         dt = ctx.saved["q"].dtype
-        return (*(g.to(dt) for g in grads), None, None, None, None)
+        return (*(g.to(dt) for g in grads), None, None, None, None, None)
 
 
 def attend_dot(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                layer: DotAttentionLayer, scale=None, dropout: float = 0.0,
-               seed=None) -> torch.Tensor:
+               seed=None, recompute: bool = False) -> torch.Tensor:
     """Autograd-aware dot-product attention on `layer`'s graph,
     differentiable in q [dst_n, K*C], k and v [src_n, K*C] (all float32 or
     all bfloat16, their gradients in their own dtype; contiguous, on the
@@ -1121,9 +1201,21 @@ def attend_dot(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     torch: q = x @ W_q and so on.  scale=None is C ** -0.5.  dropout, seed:
     attention dropout as for `attend`.  Under torch.no_grad() with dropout ==
     0 (evaluation) the call is layer.forward_fused: the same y, with no
-    [E, K] tensor allocated or kept."""
+    [E, K] tensor allocated or kept.
+    recompute=True trains without per-edge state
+    (DotAttentionLayer.forward_recompute and its backward): the same y and
+    gradients up to rounding, nothing of size E allocated in either
+    direction.  That path has no dropout: recompute=True with dropout > 0
+    raises ValueError before any launch.  recompute=False makes exactly the
+    calls described above."""
+    if recompute and dropout > 0:
+        raise ValueError(
+            "attend_dot(recompute=True) has no attention dropout")
     if not torch.is_grad_enabled() and dropout == 0:
         _draw_seed(dropout, seed)   # the same argument checks
         return layer.forward_fused(q, k, v, scale)
+    if recompute:
+        return _AttendDotFn.apply(q, k, v, layer, scale, 0.0,
+                                  _draw_seed(dropout, seed), True)
     return _AttendDotFn.apply(q, k, v, layer, scale, dropout,
                               _draw_seed(dropout, seed))

@@ -181,6 +181,20 @@ def lib():
         getattr(l, name).restype = _i32
     l.nts_gatv2_backward_fused_plan.argtypes = (
         l.nts_gat_backward_fused_plan.argtypes)
+    # fused dot-product attention training: the forward that also emits
+    # (M, S), the backward that recomputes the weights from them
+    for name in ("nts_dot_attention_forward_fused_stats",
+                 "nts_dot_attention_forward_fused_stats_bf16"):
+        getattr(l, name).argtypes = (
+            l.nts_dot_attention_forward_fused.argtypes + [_vp])
+        getattr(l, name).restype = _i32
+    for name in ("nts_dot_attention_backward_fused",
+                 "nts_dot_attention_backward_fused_bf16"):
+        getattr(l, name).argtypes = (
+            [_vp] + [_vp] * 3 + [_c.c_float] + [_vp] * 10 + [_u32] * 7)
+        getattr(l, name).restype = _i32
+    l.nts_dot_attention_backward_fused_plan.argtypes = (
+        l.nts_gat_backward_fused_plan.argtypes)
     l.nts_edge_softmax_stable.argtypes = [_vp, _i32]
     l.nts_edge_softmax_stable_last.argtypes = [_vp, _vp]
     # attention dropout
@@ -404,6 +418,27 @@ def gatv2_backward_fused_plan(f, heads, elem_bytes, row_alignment,
     out = [_i32(0) for _ in names]
     scratch = _c.c_ulonglong(0)
     lib().nts_gatv2_backward_fused_plan(
+        f, heads, elem_bytes, row_alignment, fp32_alignment, src_rows,
+        dst_rows, edges, 1 if general else 0, *[_c.byref(o) for o in out],
+        _c.byref(scratch))
+    plan = {n: o.value for n, o in zip(names, out)}
+    plan["scratch_bytes"] = scratch.value
+    return plan
+
+
+def dot_attention_backward_fused_plan(f, heads, elem_bytes, row_alignment,
+                                      fp32_alignment, src_rows, dst_rows,
+                                      edges, general=False):
+    """The launch decision of Stream.dot_attention_backward_fused[_bf16] (no
+    device access): the dict of gat_backward_fused_plan.  row_alignment is the
+    common alignment of q, k and v in bytes, fp32_alignment that of grad_y,
+    grad_q, grad_k and grad_v; both grids are sized by items * slabs."""
+    check_heads(f, heads)
+    names = ("form", "cols_per_lane", "lane_group", "slabs", "grid_csr",
+             "grid_csc")
+    out = [_i32(0) for _ in names]
+    scratch = _c.c_ulonglong(0)
+    lib().nts_dot_attention_backward_fused_plan(
         f, heads, elem_bytes, row_alignment, fp32_alignment, src_rows,
         dst_rows, edges, 1 if general else 0, *[_c.byref(o) for o in out],
         _c.byref(scratch))
@@ -1025,6 +1060,68 @@ class Stream:
             self.h, _vp(x_l_bf16), _vp(x_r_bf16), _vp(att), _vp(y_ptr),
             _vp(ms), _vp(grad_y), _vp(grad_x_l), _vp(grad_x_r), _vp(grad_att),
             slope, _vp(row_indices), _vp(column_offset), _vp(row_offset),
+            _vp(column_indices), src_s, src_e, dst_s, dst_e, edges, f, heads)
+
+    # ---- fused dot-product attention training: forward that also emits
+    # (M, S) per (destination, head), backward that recomputes the weights ----
+    def dot_attention_forward_fused_stats(self, q, k, v, y_ptr, scale,
+                                          row_indices, column_offset,
+                                          src_start, batch, edges, f, heads,
+                                          ms):
+        """dot_attention_forward_fused (y bit-identical) that also stores
+        ms[d, h] = (M, S), fp32 [batch, heads, 2], for every destination with
+        in-edges: what dot_attention_backward_fused needs besides y.  M is
+        exactly 0 in the default softmax mode."""
+        check_heads(f, heads)
+        return self._lib.nts_dot_attention_forward_fused_stats(
+            self.h, _vp(q), _vp(k), _vp(v), _vp(y_ptr), scale,
+            _vp(row_indices), _vp(column_offset), src_start, batch, edges, f,
+            heads, _vp(ms))
+
+    def dot_attention_forward_fused_stats_bf16(self, q_bf16, k_bf16, v_bf16,
+                                               y_ptr, scale, row_indices,
+                                               column_offset, src_start,
+                                               batch, edges, f, heads, ms):
+        """dot_attention_forward_fused_stats with q, k and v bfloat16."""
+        check_heads(f, heads)
+        return self._lib.nts_dot_attention_forward_fused_stats_bf16(
+            self.h, _vp(q_bf16), _vp(k_bf16), _vp(v_bf16), _vp(y_ptr), scale,
+            _vp(row_indices), _vp(column_offset), src_start, batch, edges, f,
+            heads, _vp(ms))
+
+    def dot_attention_backward_fused(self, q, k, v, scale, y_ptr, ms, grad_y,
+                                     grad_q, grad_k, grad_v, row_indices,
+                                     column_offset, row_offset,
+                                     column_indices, src_s, src_e, dst_s,
+                                     dst_e, edges, f, heads):
+        """The backward of dot_attention_forward_fused_stats from its inputs,
+        its output y and ms: grad_q, grad_k and grad_v are added to (the
+        caller zeroes).  A 16-byte record per (destination, head), one walk
+        over the CSC (grad_q) and one over the CSR (grad_k and grad_v), every
+        edge's score, weight and softmax gradient recomputed in registers;
+        nothing of size edges is allocated.  Honours edge_softmax_stable (as
+        the forward did).  Returns 1 when it ran (or there was nothing to
+        do), 0 when C > 1024: nothing was launched."""
+        check_heads(f, heads)
+        return self._lib.nts_dot_attention_backward_fused(
+            self.h, _vp(q), _vp(k), _vp(v), scale, _vp(y_ptr), _vp(ms),
+            _vp(grad_y), _vp(grad_q), _vp(grad_k), _vp(grad_v),
+            _vp(row_indices), _vp(column_offset), _vp(row_offset),
+            _vp(column_indices), src_s, src_e, dst_s, dst_e, edges, f, heads)
+
+    def dot_attention_backward_fused_bf16(self, q_bf16, k_bf16, v_bf16, scale,
+                                          y_ptr, ms, grad_y, grad_q, grad_k,
+                                          grad_v, row_indices, column_offset,
+                                          row_offset, column_indices, src_s,
+                                          src_e, dst_s, dst_e, edges, f,
+                                          heads):
+        """dot_attention_backward_fused over bfloat16 q, k and v (everything
+        else, every gradient included, stays float32)."""
+        check_heads(f, heads)
+        return self._lib.nts_dot_attention_backward_fused_bf16(
+            self.h, _vp(q_bf16), _vp(k_bf16), _vp(v_bf16), scale, _vp(y_ptr),
+            _vp(ms), _vp(grad_y), _vp(grad_q), _vp(grad_k), _vp(grad_v),
+            _vp(row_indices), _vp(column_offset), _vp(row_offset),
             _vp(column_indices), src_s, src_e, dst_s, dst_e, edges, f, heads)
 
     # ---- max / min aggregation; op is checked here, the library aborts on

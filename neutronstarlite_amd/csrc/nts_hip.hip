@@ -2333,11 +2333,13 @@ __global__ void k_edge_pair(const uint4 *__restrict__ items,
   }
 }
 
-/* ---- fused GATv2 inference forward: one row pass, online edge softmax ---- */
-/* A GATv2 score is an f-wide dot over the gathered row, so "denominators
- * first, then gather" (the GAT fused forward) would read every source row
- * twice.  Here the row a lane loads for an edge serves the score and then the
- * aggregation, and the softmax is evaluated online: per (lane, head) a running
+/* ---- fused attention forwards: one row pass, online edge softmax ---- */
+/* A GATv2 or dot-product score is an f-wide dot over the gathered row, so
+ * "denominators first, then gather" (the GAT fused forward) would read every
+ * source row twice.  Here the rows a lane loads for an edge serve the score
+ * and then the aggregation (V2Fwd and DotFwd below are the two score forms;
+ * items, lane geometry, record format, scratch and merge kernel are shared),
+ * and the softmax is evaluated online: per (lane, head) a running
  * maximum m, a running sum S = sum exp(s - m) and acc = sum exp(s - m) * x,
  * rescaled by exp(m - m') when the maximum moves (as flash attention does for
  * dense attention).  The default (unstable) softmax fixes m = 0 and never
@@ -2346,7 +2348,7 @@ __global__ void k_edge_pair(const uint4 *__restrict__ items,
  *   An unsplit item ends with out += acc / S (plain read-add-write).  A
  * shared item stores its partial record — acc (f floats), then (m, S) per
  * head (2K floats) — into row `it` of a stream scratch, and
- * k_gatv2_fused_merge folds the records of a split destination in item
+ * k_attn_fwd_merge folds the records of a split destination in item
  * order.  No atomics: the result is bit-reproducible, split rows included.
  *   The kernels are compiled without packed fp32 instructions (the rescale
  * and the R-wide fmaf are what the compiler would pair up): some packed
@@ -2378,44 +2380,274 @@ __device__ __forceinline__ void v2_update(float &m, float &S, float (&acc)[N],
   }
 }
 
-/* where the rows of one launch come from */
-template <typename T>
-struct V2Src {
-  const uint32_t *__restrict__ nbr;
-  const T *__restrict__ x_l;
-  uint32_t nbr_start, f;
+/* How a lane's N columns of one head lie in a row, and how the head's lanes
+ * sum: the two geometries of the fused forwards and the recompute backwards.
+ * cols(p, x) fills the lane's columns from the row pointer p, which already
+ * points at the lane's first column; sum(sc) takes NE partials to the head's
+ * sums in every lane, sum(sc, gd) two arrays by one interleaved butterfly.
+ * add and put are the forward's two stores. */
+
+/* fast form: a lane's R consecutive columns, the head's L lanes */
+template <int R>
+struct ColsSeg {
+  template <typename P>
+  __device__ __forceinline__ void operator()(const P *p, float (&x)[R]) const {
+    load_cols<R>(p, x);
+  }
+  /* o += acc / S, one R-float access */
+  __device__ __forceinline__ void add(float *o, float (&acc)[R],
+                                      float S) const {
+#pragma unroll
+    for (int j = 0; j < R; ++j) acc[j] /= S;
+    store_acc<R>(o, acc, R, false);
+  }
+  __device__ __forceinline__ void put(float *o, const float (&acc)[R]) const {
+#pragma unroll
+    for (int j = 0; j < R; ++j) o[j] = acc[j];
+  }
+};
+struct SumSeg {
+  uint32_t L;
+  /* the NE exchanges of a step are independent and overlap */
+  template <int NE>
+  __device__ __forceinline__ void operator()(float (&sc)[NE]) const {
+    for (uint32_t w = L >> 1; w >= 1; w >>= 1)
+#pragma unroll
+      for (int k = 0; k < NE; ++k) sc[k] += __shfl_xor(sc[k], w, 64);
+  }
+  template <int NE>
+  __device__ __forceinline__ void operator()(float (&sc)[NE],
+                                             float (&gd)[NE]) const {
+    for (uint32_t w = L >> 1; w >= 1; w >>= 1)
+#pragma unroll
+      for (int k = 0; k < NE; ++k) {
+        sc[k] += __shfl_xor(sc[k], w, 64);
+        gd[k] += __shfl_xor(gd[k], w, 64);
+      }
+  }
 };
 
-/* fast form: NE consecutive edges; index and row loads are issued before the
- * first row is consumed.  The score term and its operand order are those of
- * k_edge_pair_seg, the butterfly is seg_sum over the head's L lanes. */
-template <int R, int NE, bool STABLE, typename T>
-__device__ __forceinline__ void v2_edges_seg(float &m, float &S,
-                                             float (&acc)[R],
-                                             const V2Src<T> &g, uint32_t e,
-                                             uint32_t col, uint32_t L,
-                                             const float (&xr)[R],
-                                             const float (&av)[R],
-                                             const Gatv2Term &term) {
-  const T *p[NE];
-  float xv[NE][R], sc[NE];
+/* general form: lane l owns the head's columns l + 64*i, i < NCH; dead ones
+ * (l + 64*i >= C) hold zeros and are never stored */
+template <int NCH>
+struct ColsWave {
+  uint32_t lane, C;
+  template <typename P>
+  __device__ __forceinline__ void operator()(const P *p,
+                                             float (&x)[NCH]) const {
 #pragma unroll
-  for (int k = 0; k < NE; ++k)
-    p[k] = g.x_l + (uint64_t)(g.nbr[e + k] - g.nbr_start) * g.f + col;
-#pragma unroll
-  for (int k = 0; k < NE; ++k) load_cols<R>(p[k], xv[k]);
-#pragma unroll
-  for (int k = 0; k < NE; ++k) {
-    sc[k] = 0.f;
-#pragma unroll
-    for (int j = 0; j < R; ++j) sc[k] = term(av[j], xr[j], xv[k][j], sc[k]);
+    for (int i = 0; i < NCH; ++i)
+      x[i] = (lane + 64 * i < C) ? to_f32(p[64 * i]) : 0.f;
   }
-  /* seg_sum of the NE partials, step by step together: the NE exchanges of
-   * a step are independent and overlap */
-  for (uint32_t w = L >> 1; w >= 1; w >>= 1)
+  __device__ __forceinline__ void add(float *o, const float (&acc)[NCH],
+                                      float S) const {
 #pragma unroll
-    for (int k = 0; k < NE; ++k) sc[k] += __shfl_xor(sc[k], w, 64);
-  v2_update<R, NE, STABLE>(m, S, acc, sc, xv);
+    for (int i = 0; i < NCH; ++i)
+      if (lane + 64 * i < C) o[64 * i] += acc[i] / S;
+  }
+  __device__ __forceinline__ void put(float *o,
+                                      const float (&acc)[NCH]) const {
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+      if (lane + 64 * i < C) o[64 * i] = acc[i];
+  }
+};
+struct SumWave {
+  template <int NE>
+  __device__ __forceinline__ void operator()(float (&sc)[NE]) const {
+#pragma unroll
+    for (int k = 0; k < NE; ++k) sc[k] = wave_sum(sc[k]);
+  }
+  template <int NE>
+  __device__ __forceinline__ void operator()(float (&sc)[NE],
+                                             float (&gd)[NE]) const {
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1)
+#pragma unroll
+      for (int k = 0; k < NE; ++k) {
+        sc[k] += __shfl_xor(sc[k], w, 64);
+        gd[k] += __shfl_xor(gd[k], w, 64);
+      }
+  }
+};
+
+/* A score form is a model, passed to the kernels by value.  It owns what the
+ * forms differ in: Own<N>, what an item keeps in registers over the lane's N
+ * columns, and load_own, which fills it; edges, NE consecutive edges into the
+ * state (every index load, then every row load, issued before the first row
+ * is consumed; ends in v2_update); wave_edges, the general form's edges in
+ * flight at NCH.  row_alignment / fp32_alignment are the host's: the operands
+ * whose alignment bounds the columns per lane, beside the output. */
+
+/* GATv2: score = att . lrelu(x_l[u] + x_r[d]).  The score term and its
+ * operand order are those of k_edge_pair_seg. */
+template <typename T>
+struct V2Fwd {
+  using elem = T;
+  const uint32_t *__restrict__ nbr;
+  const T *__restrict__ x_l;
+  const T *__restrict__ x_r;
+  const float *__restrict__ att;
+  float slope;
+  uint32_t nbr_start, f, K, C;
+
+  uintptr_t row_alignment() const { return (uintptr_t)x_l | (uintptr_t)x_r; }
+  uintptr_t fp32_alignment() const { return (uintptr_t)att; }
+
+  /* fewer at the wide instantiations so that the rows stay in registers */
+  static constexpr int wave_edges(int nch) { return nch <= 4 ? 4 : 16 / nch; }
+
+  template <int N>
+  struct Own {
+    float xr[N], av[N];
+  };
+  template <int N, class Cols>
+  __device__ __forceinline__ void load_own(Own<N> &o, uint32_t v, uint32_t col,
+                                           const Cols &cols) const {
+    cols(x_r + (uint64_t)v * f + col, o.xr);
+    cols(att + col, o.av);
+  }
+  template <int N, int NE, bool STABLE, class Cols, class Sum>
+  __device__ __forceinline__ void edges(float &m, float &S, float (&acc)[N],
+                                        const Own<N> &o, uint32_t e,
+                                        uint32_t col, const Cols &cols,
+                                        const Sum &sum) const {
+    const Gatv2Term term{att, slope};
+    const T *p[NE];
+    float xv[NE][N], sc[NE];
+#pragma unroll
+    for (int k = 0; k < NE; ++k)
+      p[k] = x_l + (uint64_t)(nbr[e + k] - nbr_start) * f + col;
+#pragma unroll
+    for (int k = 0; k < NE; ++k) cols(p[k], xv[k]);
+#pragma unroll
+    for (int k = 0; k < NE; ++k) {
+      sc[k] = 0.f;
+#pragma unroll
+      for (int j = 0; j < N; ++j)
+        sc[k] = term(o.av[j], o.xr[j], xv[k][j], sc[k]);
+    }
+    sum(sc);
+    v2_update<N, NE, STABLE>(m, S, acc, sc, xv);
+  }
+};
+
+/* Dot-product attention: score[e, k] = scale * q[d, head k] . k[src(e), head
+ * k], y[d] += sum_e alpha_e * v[src(e)].  An edge reads two rows, k[u] for the
+ * score and v[u] for the value, each once.  The destination's row is scaled
+ * once when it is loaded, qs = scale * q[d] (one fp32 multiply), and stays in
+ * registers for the whole item; the partial dot of a lane is an fmaf chain of
+ * qs[j] * k[u, j] over its columns.
+ *   Edge block of the fast form (NE = 4): four index loads, then the four k
+ * loads AND the four v loads are issued before the first k is consumed, so
+ * eight row loads are in flight over the butterfly and the exps; the v rows
+ * cost 4*R registers that are live across the butterfly (DESIGN.md §3 has the
+ * register counts of this and of the variant that loads v after it). */
+template <typename T>
+struct DotFwd {
+  using elem = T;
+  const uint32_t *__restrict__ nbr;
+  const T *__restrict__ q;
+  const T *__restrict__ k;
+  const T *__restrict__ v;
+  float scale;
+  uint32_t nbr_start, f, K, C;
+
+  uintptr_t row_alignment() const {
+    return (uintptr_t)q | (uintptr_t)k | (uintptr_t)v;
+  }
+  uintptr_t fp32_alignment() const { return 0; }
+
+  /* two gathered rows per edge: 4 / 4 / 2 / 1 / 1 at NCH = 1 / 2 / 4 / 8 /
+   * 16, so that both rows of every edge stay in registers */
+  static constexpr int wave_edges(int nch) {
+    return nch <= 2 ? 4 : nch <= 8 ? 8 / nch : 1;
+  }
+
+  template <int N>
+  struct Own {
+    float qs[N];
+  };
+  template <int N, class Cols>
+  __device__ __forceinline__ void load_own(Own<N> &o, uint32_t d, uint32_t col,
+                                           const Cols &cols) const {
+    cols(q + (uint64_t)d * f + col, o.qs);
+#pragma unroll
+    for (int j = 0; j < N; ++j) o.qs[j] *= scale;
+  }
+  template <int N, int NE, bool STABLE, class Cols, class Sum>
+  __device__ __forceinline__ void edges(float &m, float &S, float (&acc)[N],
+                                        const Own<N> &o, uint32_t e,
+                                        uint32_t col, const Cols &cols,
+                                        const Sum &sum) const {
+    uint64_t off[NE];
+    float kv[NE][N], vv[NE][N], sc[NE];
+#pragma unroll
+    for (int i = 0; i < NE; ++i)
+      off[i] = (uint64_t)(nbr[e + i] - nbr_start) * f + col;
+#pragma unroll
+    for (int i = 0; i < NE; ++i) cols(k + off[i], kv[i]);
+#pragma unroll
+    for (int i = 0; i < NE; ++i) cols(v + off[i], vv[i]);
+#pragma unroll
+    for (int i = 0; i < NE; ++i) {
+      sc[i] = 0.f;
+#pragma unroll
+      for (int j = 0; j < N; ++j) sc[i] = fmaf(o.qs[j], kv[i][j], sc[i]);
+    }
+    sum(sc);
+    v2_update<N, NE, STABLE>(m, S, acc, sc, vv);
+  }
+};
+
+/* where a launch writes; ms only under STATS: (m, S) per (destination,
+ * head) */
+struct AttnFwdOut {
+  float *__restrict__ out;
+  float *__restrict__ scratch;
+  float *__restrict__ ms;
+};
+
+/* One item over a lane's N columns from col on, of head `head`: all its edges
+ * into (m, S, acc), NE at a time and then one by one, then the store.  An
+ * unsplit item adds acc / S to its output row, and under STATS the head's
+ * writer lane leaves (m, S) in ms[d, head]; a shared item writes its record
+ * into scratch row `it`. */
+template <int N, int NE, bool STABLE, bool STATS, class Model, class Cols,
+          class Sum>
+__device__ __forceinline__ void attn_fwd_item(const Model &g,
+                                              const AttnFwdOut &o,
+                                              const Item &im, uint32_t it,
+                                              uint32_t col, uint32_t head,
+                                              bool writer, const Cols &cols,
+                                              const Sum &sum) {
+  typename Model::template Own<N> own;
+  g.load_own(own, im.v, col, cols);
+  float acc[N] = {};
+  float m = STABLE ? -INFINITY : 0.f, S = 0.f;
+  const uint32_t e_end = im.e0 + im.cnt;
+  uint32_t e = im.e0;
+  for (; e + NE <= e_end; e += NE)
+    g.template edges<N, NE, STABLE>(m, S, acc, own, e, col, cols, sum);
+  for (; e < e_end; ++e)
+    g.template edges<N, 1, STABLE>(m, S, acc, own, e, col, cols, sum);
+  if (!im.shared) {
+    cols.add(o.out + (uint64_t)im.v * g.f + col, acc, S);
+    if constexpr (STATS) {
+      if (writer) {
+        float *q = o.ms + 2 * ((uint64_t)im.v * g.K + head);
+        q[0] = m;
+        q[1] = S;
+      }
+    }
+  } else {
+    float *rec = o.scratch + (uint64_t)it * (g.f + 2 * g.K);
+    cols.put(rec + col, acc);
+    if (writer) {
+      rec[g.f + 2 * head] = m;
+      rec[g.f + 2 * head + 1] = S;
+    }
+  }
 }
 
 /* Fast form, C a power of two and L = C/R <= 64 lanes per head: a group of G
@@ -2423,209 +2655,52 @@ __device__ __forceinline__ void v2_edges_seg(float &m, float &S,
  * of one head; slabs are whole heads (G >= L, both powers of two).  Lanes
  * past the row's end are whole segments and take no part.  The lanes of a
  * segment share their task, hence every trip count, so the butterfly only
- * ever reads lanes that run with it. */
-template <int R, bool STABLE, bool STATS, typename T>
-NTS_NO_PK __device__ __forceinline__ void gatv2_fused_seg(
+ * ever reads lanes that run with it.  Four edges in flight. */
+template <class Model, int R, bool STABLE, bool STATS>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_attn_fwd_seg(
     const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    const uint32_t *__restrict__ nbr, const T *__restrict__ x_l,
-    const T *__restrict__ x_r, const float *__restrict__ att,
-    float *__restrict__ out, float *__restrict__ scratch, float slope,
-    uint32_t nbr_start, uint32_t f, uint32_t K, uint32_t C, uint32_t G,
-    uint32_t n_slabs, float *__restrict__ ms) {
+    const Model g, const AttnFwdOut o, uint32_t G, uint32_t n_slabs) {
   const uint32_t n_items = *n_items_p;
   const uint32_t glane = threadIdx.x & (G - 1);
-  const uint32_t L = C / R;
-  const V2Src<T> g{nbr, x_l, nbr_start, f};
-  const Gatv2Term term{att, slope};
+  const uint32_t L = g.C / R;
   const uint64_t total = (uint64_t)n_items * n_slabs;
   const uint64_t stride = (gridDim.x * NTS_BLOCK) / G;
   for (uint64_t t = (blockIdx.x * NTS_BLOCK + threadIdx.x) / G; t < total;
        t += stride) {
     const uint32_t it = (uint32_t)(t / n_slabs);
     const uint32_t col = (uint32_t)(t % n_slabs) * G * R + glane * R;
-    if (col >= f) continue;
-    const Item im = load_item(items, it);
-    float xr[R], av[R], acc[R] = {};
-    load_cols<R>(x_r + (uint64_t)im.v * f + col, xr);
-    load_cols<R>(att + col, av);
-    float m = STABLE ? -INFINITY : 0.f, S = 0.f;
-    const uint32_t e_end = im.e0 + im.cnt;
-    uint32_t e = im.e0;
-    for (; e + 4 <= e_end; e += 4)
-      v2_edges_seg<R, 4, STABLE>(m, S, acc, g, e, col, L, xr, av, term);
-    for (; e < e_end; ++e)
-      v2_edges_seg<R, 1, STABLE>(m, S, acc, g, e, col, L, xr, av, term);
-    if (!im.shared) {
-#pragma unroll
-      for (int j = 0; j < R; ++j) acc[j] /= S;
-      store_acc<R>(out + (uint64_t)im.v * f + col, acc, R, false);
-      if constexpr (STATS) {
-        if ((glane & (L - 1)) == 0) {
-          float *q = ms + 2 * ((uint64_t)im.v * K + col / C);
-          q[0] = m;
-          q[1] = S;
-        }
-      }
-    } else {
-      float *rec = scratch + (uint64_t)it * (f + 2 * K);
-#pragma unroll
-      for (int j = 0; j < R; ++j) rec[col + j] = acc[j];
-      if ((glane & (L - 1)) == 0) {
-        rec[f + 2 * (col / C)] = m;
-        rec[f + 2 * (col / C) + 1] = S;
-      }
-    }
+    if (col >= g.f) continue;
+    attn_fwd_item<R, 4, STABLE, STATS>(g, o, load_item(items, it), it, col,
+                                       col / g.C, (glane & (L - 1)) == 0,
+                                       ColsSeg<R>{}, SumSeg{L});
   }
 }
-template <int R, bool STABLE, typename T>
-NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_fused_seg(
-    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    const uint32_t *__restrict__ nbr, const T *__restrict__ x_l,
-    const T *__restrict__ x_r, const float *__restrict__ att,
-    float *__restrict__ out, float *__restrict__ scratch, float slope,
-    uint32_t nbr_start, uint32_t f, uint32_t K, uint32_t C, uint32_t G,
-    uint32_t n_slabs) {
-  gatv2_fused_seg<R, STABLE, false, T>(items, n_items_p, nbr, x_l, x_r, att,
-                                       out, scratch, slope, nbr_start, f, K, C,
-                                       G, n_slabs, nullptr);
-}
-/* the training twin: an unsplit item also leaves its (m, S) in ms[d, k] */
-template <int R, bool STABLE, typename T>
-NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_fused_seg_stats(
-    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    const uint32_t *__restrict__ nbr, const T *__restrict__ x_l,
-    const T *__restrict__ x_r, const float *__restrict__ att,
-    float *__restrict__ out, float *__restrict__ scratch, float slope,
-    uint32_t nbr_start, uint32_t f, uint32_t K, uint32_t C, uint32_t G,
-    uint32_t n_slabs, float *__restrict__ ms) {
-  gatv2_fused_seg<R, STABLE, true, T>(items, n_items_p, nbr, x_l, x_r, att,
-                                      out, scratch, slope, nbr_start, f, K, C,
-                                      G, n_slabs, ms);
-}
 
-/* general form: NE consecutive edges of one (item, head) across the wave */
-template <int NCH, int NE, bool STABLE, typename T>
-__device__ __forceinline__ void v2_edges_wave(float &m, float &S,
-                                              float (&acc)[NCH],
-                                              const V2Src<T> &g, uint32_t e,
-                                              uint32_t col, uint32_t lane,
-                                              uint32_t C,
-                                              const float (&xr)[NCH],
-                                              const float (&av)[NCH],
-                                              const Gatv2Term &term) {
-  const T *p[NE];
-  float xv[NE][NCH], sc[NE];
-#pragma unroll
-  for (int k = 0; k < NE; ++k)
-    p[k] = g.x_l + (uint64_t)(g.nbr[e + k] - g.nbr_start) * g.f + col;
-#pragma unroll
-  for (int k = 0; k < NE; ++k)
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-      xv[k][i] = (lane + 64 * i < C) ? to_f32(p[k][64 * i]) : 0.f;
-#pragma unroll
-  for (int k = 0; k < NE; ++k) {
-    float pr = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) pr = term(av[i], xr[i], xv[k][i], pr);
-    sc[k] = wave_sum(pr);
-  }
-  v2_update<NCH, NE, STABLE>(m, S, acc, sc, xv);
-}
-
-/* General form, any K and C <= 64*NCH: a wave runs one (item, head), lane l
- * owns the head's columns l + 64*i, i < NCH (dead ones hold zeros and are
- * never stored); the score is a wave_sum.  NE = edges in flight, fewer at
- * the wide instantiations so that the rows stay in registers. */
-template <int NCH, bool STABLE, bool STATS, typename T>
-NTS_NO_PK __device__ __forceinline__ void gatv2_fused_wave(
+/* General form, any K and C <= 64*NCH: a wave runs one (item, head); the
+ * score is a wave_sum. */
+template <class Model, int NCH, bool STABLE, bool STATS>
+NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_attn_fwd_wave(
     const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    const uint32_t *__restrict__ nbr, const T *__restrict__ x_l,
-    const T *__restrict__ x_r, const float *__restrict__ att,
-    float *__restrict__ out, float *__restrict__ scratch, float slope,
-    uint32_t nbr_start, uint32_t f, uint32_t K, uint32_t C,
-    float *__restrict__ ms) {
-  constexpr int NE = NCH <= 4 ? 4 : 16 / NCH;
+    const Model g, const AttnFwdOut o) {
   const uint32_t n_items = *n_items_p;
   const WaveId w = wave_id();
-  const V2Src<T> g{nbr, x_l, nbr_start, f};
-  const Gatv2Term term{att, slope};
-  const uint64_t total = (uint64_t)n_items * K;
+  const uint64_t total = (uint64_t)n_items * g.K;
   for (uint64_t t = w.wave; t < total; t += w.n_waves) {
-    const uint32_t it = (uint32_t)(t / K), head = (uint32_t)(t % K);
-    const Item im = load_item(items, it);
-    const uint32_t col = head * C + w.lane;
-    float xr[NCH], av[NCH], acc[NCH] = {};
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      const bool live = w.lane + 64 * i < C;
-      xr[i] = live ? to_f32(x_r[(uint64_t)im.v * f + col + 64 * i]) : 0.f;
-      av[i] = live ? att[col + 64 * i] : 0.f;
-    }
-    float m = STABLE ? -INFINITY : 0.f, S = 0.f;
-    const uint32_t e_end = im.e0 + im.cnt;
-    uint32_t e = im.e0;
-    for (; e + NE <= e_end; e += NE)
-      v2_edges_wave<NCH, NE, STABLE>(m, S, acc, g, e, col, w.lane, C, xr, av,
-                                     term);
-    for (; e < e_end; ++e)
-      v2_edges_wave<NCH, 1, STABLE>(m, S, acc, g, e, col, w.lane, C, xr, av,
-                                    term);
-    if (!im.shared) {
-      float *o = out + (uint64_t)im.v * f + col;
-#pragma unroll
-      for (int i = 0; i < NCH; ++i)
-        if (w.lane + 64 * i < C) o[64 * i] += acc[i] / S;
-      if constexpr (STATS) {
-        if (w.lane == 0) {
-          float *q = ms + 2 * ((uint64_t)im.v * K + head);
-          q[0] = m;
-          q[1] = S;
-        }
-      }
-    } else {
-      float *rec = scratch + (uint64_t)it * (f + 2 * K);
-#pragma unroll
-      for (int i = 0; i < NCH; ++i)
-        if (w.lane + 64 * i < C) rec[col + 64 * i] = acc[i];
-      if (w.lane == 0) {
-        rec[f + 2 * head] = m;
-        rec[f + 2 * head + 1] = S;
-      }
-    }
+    const uint32_t it = (uint32_t)(t / g.K), head = (uint32_t)(t % g.K);
+    attn_fwd_item<NCH, Model::wave_edges(NCH), STABLE, STATS>(
+        g, o, load_item(items, it), it, head * g.C + w.lane, head,
+        w.lane == 0, ColsWave<NCH>{w.lane, g.C}, SumWave{});
   }
-}
-template <int NCH, bool STABLE, typename T>
-NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_fused_wave(
-    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    const uint32_t *__restrict__ nbr, const T *__restrict__ x_l,
-    const T *__restrict__ x_r, const float *__restrict__ att,
-    float *__restrict__ out, float *__restrict__ scratch, float slope,
-    uint32_t nbr_start, uint32_t f, uint32_t K, uint32_t C) {
-  gatv2_fused_wave<NCH, STABLE, false, T>(items, n_items_p, nbr, x_l, x_r, att,
-                                          out, scratch, slope, nbr_start, f, K,
-                                          C, nullptr);
-}
-template <int NCH, bool STABLE, typename T>
-NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_fused_wave_stats(
-    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    const uint32_t *__restrict__ nbr, const T *__restrict__ x_l,
-    const T *__restrict__ x_r, const float *__restrict__ att,
-    float *__restrict__ out, float *__restrict__ scratch, float slope,
-    uint32_t nbr_start, uint32_t f, uint32_t K, uint32_t C,
-    float *__restrict__ ms) {
-  gatv2_fused_wave<NCH, STABLE, true, T>(items, n_items_p, nbr, x_l, x_r, att,
-                                         out, scratch, slope, nbr_start, f, K,
-                                         C, ms);
 }
 
 /* The records of a split destination, merged by the wave that meets its
  * first item (shared && e0 == offset[v]): the n = ceil(deg / split) records
  * it .. it+n-1 are contiguous and in edge order in the item list.  One lane
  * per column:  M = max m_i,  y = sum_i exp(m_i - M) acc_i / sum_i exp(m_i -
- * M) S_i,  out += y.  Default-mode records carry m = 0 and exp(0) = 1. */
+ * M) S_i,  out += y.  Default-mode records carry m = 0 and exp(0) = 1.
+ * STATS: (M, den) of the split destination into stats[d, k]. */
 template <bool STATS>
-NTS_NO_PK __device__ __forceinline__ void gatv2_fused_merge(
+NTS_NO_PK __global__ void k_attn_fwd_merge(
     const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
     const uint32_t *__restrict__ offset, const float *__restrict__ scratch,
     float *__restrict__ out, uint32_t split, uint32_t f, uint32_t K,
@@ -2659,269 +2734,6 @@ NTS_NO_PK __device__ __forceinline__ void gatv2_fused_merge(
       }
     }
   }
-}
-NTS_NO_PK __global__ void k_gatv2_fused_merge(
-    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    const uint32_t *__restrict__ offset, const float *__restrict__ scratch,
-    float *__restrict__ out, uint32_t split, uint32_t f, uint32_t K,
-    uint32_t C) {
-  gatv2_fused_merge<false>(items, n_items_p, offset, scratch, out, split, f, K,
-                           C, nullptr);
-}
-/* the training twin: (M, den) of the split destination into ms[d, k] */
-NTS_NO_PK __global__ void k_gatv2_fused_merge_stats(
-    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    const uint32_t *__restrict__ offset, const float *__restrict__ scratch,
-    float *__restrict__ out, uint32_t split, uint32_t f, uint32_t K,
-    uint32_t C, float *__restrict__ stats) {
-  gatv2_fused_merge<true>(items, n_items_p, offset, scratch, out, split, f, K,
-                          C, stats);
-}
-
-/* ---- fused dot-product attention forward: one pass over k and v ---- */
-/* score[e, k] = scale * q[d, head k] . k[src(e), head k], softmax over d's
- * in-edges per head, y[d] += sum_e alpha_e * v[src(e)].  An edge reads two
- * rows, k[u] for the score and v[u] for the value, each once; everything
- * after the score is the online (m, S, acc) of the GATv2 fused forward
- * (v2_update), with the same items, lane geometry, record format, scratch
- * and merge kernel (k_gatv2_fused_merge), hence no atomics either.
- *   The destination's row is scaled once when it is loaded, qs = scale * q[d]
- * (one fp32 multiply), and stays in registers for the whole item; the
- * partial dot of a lane is an fmaf chain of qs[j] * k[u, j] over its columns.
- *   Edge block of the fast form (NE = 4): four index loads, then the four k
- * loads AND the four v loads are issued before the first k is consumed, so
- * eight row loads are in flight over the butterfly and the exps; the v rows
- * cost 4*R registers that are live across the butterfly (DESIGN.md §3 has the
- * register counts of this and of the variant that loads v after it). */
-template <typename T>
-struct DotSrc {
-  const uint32_t *__restrict__ nbr;
-  const T *__restrict__ k;
-  const T *__restrict__ v;
-  uint32_t nbr_start, f;
-};
-
-/* fast form: NE consecutive edges, the butterfly interleaved as in
- * v2_edges_seg */
-template <int R, int NE, bool STABLE, typename T>
-__device__ __forceinline__ void dot_edges_seg(float &m, float &S,
-                                              float (&acc)[R],
-                                              const DotSrc<T> &g, uint32_t e,
-                                              uint32_t col, uint32_t L,
-                                              const float (&qs)[R]) {
-  uint64_t off[NE];
-  float kv[NE][R], vv[NE][R], sc[NE];
-#pragma unroll
-  for (int k = 0; k < NE; ++k)
-    off[k] = (uint64_t)(g.nbr[e + k] - g.nbr_start) * g.f + col;
-#pragma unroll
-  for (int k = 0; k < NE; ++k) load_cols<R>(g.k + off[k], kv[k]);
-#pragma unroll
-  for (int k = 0; k < NE; ++k) load_cols<R>(g.v + off[k], vv[k]);
-#pragma unroll
-  for (int k = 0; k < NE; ++k) {
-    sc[k] = 0.f;
-#pragma unroll
-    for (int j = 0; j < R; ++j) sc[k] = fmaf(qs[j], kv[k][j], sc[k]);
-  }
-  for (uint32_t w = L >> 1; w >= 1; w >>= 1)
-#pragma unroll
-    for (int k = 0; k < NE; ++k) sc[k] += __shfl_xor(sc[k], w, 64);
-  v2_update<R, NE, STABLE>(m, S, acc, sc, vv);
-}
-
-/* Fast form: the task and lane geometry of k_gatv2_fused_seg (a group of G
- * lanes per (item, slab of G*R columns), a head an aligned segment of L = C/R
- * lanes, lanes past the row's end whole segments that take no part). */
-template <int R, bool STABLE, bool STATS, typename T>
-NTS_NO_PK __device__ __forceinline__ void dot_fused_seg(
-    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    const uint32_t *__restrict__ nbr, const T *__restrict__ q,
-    const T *__restrict__ k, const T *__restrict__ v, float *__restrict__ out,
-    float *__restrict__ scratch, float scale, uint32_t nbr_start, uint32_t f,
-    uint32_t K, uint32_t C, uint32_t G, uint32_t n_slabs,
-    float *__restrict__ ms) {
-  const uint32_t n_items = *n_items_p;
-  const uint32_t glane = threadIdx.x & (G - 1);
-  const uint32_t L = C / R;
-  const DotSrc<T> g{nbr, k, v, nbr_start, f};
-  const uint64_t total = (uint64_t)n_items * n_slabs;
-  const uint64_t stride = (gridDim.x * NTS_BLOCK) / G;
-  for (uint64_t t = (blockIdx.x * NTS_BLOCK + threadIdx.x) / G; t < total;
-       t += stride) {
-    const uint32_t it = (uint32_t)(t / n_slabs);
-    const uint32_t col = (uint32_t)(t % n_slabs) * G * R + glane * R;
-    if (col >= f) continue;
-    const Item im = load_item(items, it);
-    float qs[R], acc[R] = {};
-    load_cols<R>(q + (uint64_t)im.v * f + col, qs);
-#pragma unroll
-    for (int j = 0; j < R; ++j) qs[j] *= scale;
-    float m = STABLE ? -INFINITY : 0.f, S = 0.f;
-    const uint32_t e_end = im.e0 + im.cnt;
-    uint32_t e = im.e0;
-    for (; e + 4 <= e_end; e += 4)
-      dot_edges_seg<R, 4, STABLE>(m, S, acc, g, e, col, L, qs);
-    for (; e < e_end; ++e)
-      dot_edges_seg<R, 1, STABLE>(m, S, acc, g, e, col, L, qs);
-    if (!im.shared) {
-#pragma unroll
-      for (int j = 0; j < R; ++j) acc[j] /= S;
-      store_acc<R>(out + (uint64_t)im.v * f + col, acc, R, false);
-      if constexpr (STATS) {
-        if ((glane & (L - 1)) == 0) {
-          float *o = ms + 2 * ((uint64_t)im.v * K + col / C);
-          o[0] = m;
-          o[1] = S;
-        }
-      }
-    } else {
-      float *rec = scratch + (uint64_t)it * (f + 2 * K);
-#pragma unroll
-      for (int j = 0; j < R; ++j) rec[col + j] = acc[j];
-      if ((glane & (L - 1)) == 0) {
-        rec[f + 2 * (col / C)] = m;
-        rec[f + 2 * (col / C) + 1] = S;
-      }
-    }
-  }
-}
-template <int R, bool STABLE, typename T>
-NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_seg(
-    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    const uint32_t *__restrict__ nbr, const T *__restrict__ q,
-    const T *__restrict__ k, const T *__restrict__ v, float *__restrict__ out,
-    float *__restrict__ scratch, float scale, uint32_t nbr_start, uint32_t f,
-    uint32_t K, uint32_t C, uint32_t G, uint32_t n_slabs) {
-  dot_fused_seg<R, STABLE, false, T>(items, n_items_p, nbr, q, k, v, out,
-                                     scratch, scale, nbr_start, f, K, C, G,
-                                     n_slabs, nullptr);
-}
-/* the training twin: an unsplit item also leaves its (m, S) in ms[d, k] */
-template <int R, bool STABLE, typename T>
-NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_seg_stats(
-    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    const uint32_t *__restrict__ nbr, const T *__restrict__ q,
-    const T *__restrict__ k, const T *__restrict__ v, float *__restrict__ out,
-    float *__restrict__ scratch, float scale, uint32_t nbr_start, uint32_t f,
-    uint32_t K, uint32_t C, uint32_t G, uint32_t n_slabs,
-    float *__restrict__ ms) {
-  dot_fused_seg<R, STABLE, true, T>(items, n_items_p, nbr, q, k, v, out,
-                                    scratch, scale, nbr_start, f, K, C, G,
-                                    n_slabs, ms);
-}
-
-/* general form: NE consecutive edges of one (item, head) across the wave;
- * dead columns (lane + 64*i >= C) hold zeros in qs, kv and vv */
-template <int NCH, int NE, bool STABLE, typename T>
-__device__ __forceinline__ void dot_edges_wave(float &m, float &S,
-                                               float (&acc)[NCH],
-                                               const DotSrc<T> &g, uint32_t e,
-                                               uint32_t col, uint32_t lane,
-                                               uint32_t C,
-                                               const float (&qs)[NCH]) {
-  uint64_t off[NE];
-  float kv[NE][NCH], vv[NE][NCH], sc[NE];
-#pragma unroll
-  for (int k = 0; k < NE; ++k)
-    off[k] = (uint64_t)(g.nbr[e + k] - g.nbr_start) * g.f + col;
-#pragma unroll
-  for (int k = 0; k < NE; ++k)
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-      kv[k][i] = (lane + 64 * i < C) ? to_f32(g.k[off[k] + 64 * i]) : 0.f;
-#pragma unroll
-  for (int k = 0; k < NE; ++k)
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-      vv[k][i] = (lane + 64 * i < C) ? to_f32(g.v[off[k] + 64 * i]) : 0.f;
-#pragma unroll
-  for (int k = 0; k < NE; ++k) {
-    float pr = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) pr = fmaf(qs[i], kv[k][i], pr);
-    sc[k] = wave_sum(pr);
-  }
-  v2_update<NCH, NE, STABLE>(m, S, acc, sc, vv);
-}
-
-/* General form, any K and C <= 64*NCH: a wave runs one (item, head), lane l
- * owns the head's columns l + 64*i, i < NCH, as in k_gatv2_fused_wave.  Two
- * gathered rows per edge: NE = 4 / 4 / 2 / 1 / 1 edges in flight at NCH = 1 /
- * 2 / 4 / 8 / 16, so that both rows of every edge stay in registers. */
-template <int NCH, bool STABLE, bool STATS, typename T>
-NTS_NO_PK __device__ __forceinline__ void dot_fused_wave(
-    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    const uint32_t *__restrict__ nbr, const T *__restrict__ q,
-    const T *__restrict__ k, const T *__restrict__ v, float *__restrict__ out,
-    float *__restrict__ scratch, float scale, uint32_t nbr_start, uint32_t f,
-    uint32_t K, uint32_t C, float *__restrict__ ms) {
-  constexpr int NE = NCH <= 2 ? 4 : NCH <= 8 ? 8 / NCH : 1;
-  const uint32_t n_items = *n_items_p;
-  const WaveId w = wave_id();
-  const DotSrc<T> g{nbr, k, v, nbr_start, f};
-  const uint64_t total = (uint64_t)n_items * K;
-  for (uint64_t t = w.wave; t < total; t += w.n_waves) {
-    const uint32_t it = (uint32_t)(t / K), head = (uint32_t)(t % K);
-    const Item im = load_item(items, it);
-    const uint32_t col = head * C + w.lane;
-    float qs[NCH], acc[NCH] = {};
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-      qs[i] = (w.lane + 64 * i < C)
-                  ? scale * to_f32(q[(uint64_t)im.v * f + col + 64 * i])
-                  : 0.f;
-    float m = STABLE ? -INFINITY : 0.f, S = 0.f;
-    const uint32_t e_end = im.e0 + im.cnt;
-    uint32_t e = im.e0;
-    for (; e + NE <= e_end; e += NE)
-      dot_edges_wave<NCH, NE, STABLE>(m, S, acc, g, e, col, w.lane, C, qs);
-    for (; e < e_end; ++e)
-      dot_edges_wave<NCH, 1, STABLE>(m, S, acc, g, e, col, w.lane, C, qs);
-    if (!im.shared) {
-      float *o = out + (uint64_t)im.v * f + col;
-#pragma unroll
-      for (int i = 0; i < NCH; ++i)
-        if (w.lane + 64 * i < C) o[64 * i] += acc[i] / S;
-      if constexpr (STATS) {
-        if (w.lane == 0) {
-          float *p = ms + 2 * ((uint64_t)im.v * K + head);
-          p[0] = m;
-          p[1] = S;
-        }
-      }
-    } else {
-      float *rec = scratch + (uint64_t)it * (f + 2 * K);
-#pragma unroll
-      for (int i = 0; i < NCH; ++i)
-        if (w.lane + 64 * i < C) rec[col + 64 * i] = acc[i];
-      if (w.lane == 0) {
-        rec[f + 2 * head] = m;
-        rec[f + 2 * head + 1] = S;
-      }
-    }
-  }
-}
-template <int NCH, bool STABLE, typename T>
-NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_wave(
-    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    const uint32_t *__restrict__ nbr, const T *__restrict__ q,
-    const T *__restrict__ k, const T *__restrict__ v, float *__restrict__ out,
-    float *__restrict__ scratch, float scale, uint32_t nbr_start, uint32_t f,
-    uint32_t K, uint32_t C) {
-  dot_fused_wave<NCH, STABLE, false, T>(items, n_items_p, nbr, q, k, v, out,
-                                        scratch, scale, nbr_start, f, K, C,
-                                        nullptr);
-}
-template <int NCH, bool STABLE, typename T>
-NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_fused_wave_stats(
-    const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
-    const uint32_t *__restrict__ nbr, const T *__restrict__ q,
-    const T *__restrict__ k, const T *__restrict__ v, float *__restrict__ out,
-    float *__restrict__ scratch, float scale, uint32_t nbr_start, uint32_t f,
-    uint32_t K, uint32_t C, float *__restrict__ ms) {
-  dot_fused_wave<NCH, STABLE, true, T>(items, n_items_p, nbr, q, k, v, out,
-                                       scratch, scale, nbr_start, f, K, C, ms);
 }
 
 /* ---- GAT training backward that recomputes the attention weights ---- */
@@ -3081,7 +2893,7 @@ __device__ __forceinline__ void bwd_edges_seg(float (&acc)[R], float &acc_s,
 }
 
 /* Fast form, C a power of two and L = C/R <= 64 lanes per head: the geometry
- * of k_gatv2_fused_seg.  A group of G lanes owns a task (item, slab of G*R
+ * of k_attn_fwd_seg.  A group of G lanes owns a task (item, slab of G*R
  * columns), a lane R consecutive columns of one head; lanes past the row's
  * end are whole segments and take no part; the lanes of a segment share
  * their task, so the butterfly only reads lanes that run with it. */
@@ -3154,7 +2966,7 @@ __device__ __forceinline__ void bwd_edges_wave(float (&acc)[NCH], float &acc_s,
 
 /* General form, any K and C <= 64*NCH: a wave runs one (item, head), lane l
  * owns the head's columns l + 64*i, i < NCH (dead ones hold zeros and are
- * never stored); the dot is a wave_sum.  NE as in k_gatv2_fused_wave. */
+ * never stored); the dot is a wave_sum.  NE as V2Fwd::wave_edges. */
 template <int NCH, bool STABLE, bool CSR, typename TO, typename TG>
 NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gat_bwd_wave(
     const uint4 *__restrict__ items, const uint32_t *__restrict__ n_items_p,
@@ -3457,28 +3269,6 @@ __device__ __forceinline__ void v2b_item(float (&a1)[N], float (&a2)[N],
                                  rec_own, load, sum2);
 }
 
-/* fast form: a lane's R consecutive columns, the head's L lanes */
-template <int R>
-struct V2bLoadSeg {
-  template <typename P>
-  __device__ __forceinline__ void operator()(const P *p, float (&x)[R]) const {
-    load_cols<R>(p, x);
-  }
-};
-struct V2bSumSeg {
-  uint32_t L;
-  template <int NE>
-  __device__ __forceinline__ void operator()(float (&sc)[NE],
-                                             float (&gd)[NE]) const {
-    for (uint32_t w = L >> 1; w >= 1; w >>= 1)
-#pragma unroll
-      for (int k = 0; k < NE; ++k) {
-        sc[k] += __shfl_xor(sc[k], w, 64);
-        gd[k] += __shfl_xor(gd[k], w, 64);
-      }
-  }
-};
-
 /* one (item, slab) task of the fast form: returns through datt (CSC) */
 template <int R, bool STABLE, bool CSR, typename T>
 __device__ __forceinline__ void v2b_seg_task(const V2Bwd<T> &g, const Item &im,
@@ -3491,12 +3281,12 @@ __device__ __forceinline__ void v2b_seg_task(const V2Bwd<T> &g, const Item &im,
   if constexpr (CSR) {
     float a2[R] = {};
     v2b_item<R, 4, STABLE, true>(a1, a2, g, im, col, head, own, av,
-                                 V2bLoadSeg<R>{}, V2bSumSeg{L});
+                                 ColsSeg<R>{}, SumSeg{L});
 #pragma unroll
     for (int j = 0; j < R; ++j) a1[j] = fmaf(av[j], a2[j], a1[j]);
   } else {
     v2b_item<R, 4, STABLE, false>(a1, datt, g, im, col, head, own, av,
-                                  V2bLoadSeg<R>{}, V2bSumSeg{L});
+                                  ColsSeg<R>{}, SumSeg{L});
 #pragma unroll
     for (int j = 0; j < R; ++j) a1[j] *= av[j];
   }
@@ -3504,7 +3294,7 @@ __device__ __forceinline__ void v2b_seg_task(const V2Bwd<T> &g, const Item &im,
 }
 
 /* Fast form, C a power of two and L = C/R <= 64: the geometry of
- * k_gatv2_fused_seg (G lanes per task, a lane R consecutive columns of one
+ * k_attn_fwd_seg (G lanes per task, a lane R consecutive columns of one
  * head, slabs of whole heads, lanes past the row's end whole segments that
  * take no part).  CSR: tasks (item, slab) flattened.  CSC: slab outer, the
  * group's items inner, grad_att through LDS. */
@@ -3558,32 +3348,6 @@ NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_bwd_seg(
   }
 }
 
-/* general form: lane l owns the head's columns l + 64*i, i < NCH */
-template <int NCH>
-struct V2bLoadWave {
-  uint32_t lane, C;
-  template <typename P>
-  __device__ __forceinline__ void operator()(const P *p,
-                                             float (&x)[NCH]) const {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-      x[i] = (lane + 64 * i < C) ? to_f32(p[64 * i]) : 0.f;
-  }
-};
-struct V2bSumWave {
-  template <int NE>
-  __device__ __forceinline__ void operator()(float (&sc)[NE],
-                                             float (&gd)[NE]) const {
-#pragma unroll
-    for (int w = 32; w >= 1; w >>= 1)
-#pragma unroll
-      for (int k = 0; k < NE; ++k) {
-        sc[k] += __shfl_xor(sc[k], w, 64);
-        gd[k] += __shfl_xor(gd[k], w, 64);
-      }
-  }
-};
-
 /* one (item, head) task of the general form; dead columns hold zeros (att
  * too, so they add nothing to the score or the dot) and are never stored */
 template <int NCH, bool STABLE, bool CSR, typename T>
@@ -3594,18 +3358,18 @@ __device__ __forceinline__ void v2b_wave_task(const V2Bwd<T> &g,
                                               float (&datt)[NCH]) {
   constexpr int NE = NCH <= 4 ? 4 : 16 / NCH;
   const uint32_t col = head * g.C + lane;
-  const V2bLoadWave<NCH> load{lane, g.C};
+  const ColsWave<NCH> load{lane, g.C};
   float own[NCH], a1[NCH] = {};
   load(g.own + (uint64_t)im.v * g.f + col, own);
   if constexpr (CSR) {
     float a2[NCH] = {};
     v2b_item<NCH, NE, STABLE, true>(a1, a2, g, im, col, head, own, av, load,
-                                    V2bSumWave{});
+                                    SumWave{});
 #pragma unroll
     for (int i = 0; i < NCH; ++i) a1[i] = fmaf(av[i], a2[i], a1[i]);
   } else {
     v2b_item<NCH, NE, STABLE, false>(a1, datt, g, im, col, head, own, av, load,
-                                     V2bSumWave{});
+                                     SumWave{});
 #pragma unroll
     for (int i = 0; i < NCH; ++i) a1[i] *= av[i];
   }
@@ -3633,14 +3397,14 @@ NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_bwd_wave(
     for (uint64_t t = w.wave; t < total; t += w.n_waves) {
       const uint32_t head = (uint32_t)(t % g.K);
       float av[NCH], none[NCH];
-      V2bLoadWave<NCH>{w.lane, g.C}(g.att + head * g.C + w.lane, av);
+      ColsWave<NCH>{w.lane, g.C}(g.att + head * g.C + w.lane, av);
       v2b_wave_task<NCH, STABLE, true>(g, load_item(items, (uint32_t)(t / g.K)),
                                        head, w.lane, av, none);
     }
   } else {
     for (uint32_t head = 0; head < g.K; ++head) {
       float av[NCH], datt[NCH] = {};
-      V2bLoadWave<NCH>{w.lane, g.C}(g.att + head * g.C + w.lane, av);
+      ColsWave<NCH>{w.lane, g.C}(g.att + head * g.C + w.lane, av);
       for (uint32_t it = w.wave; it < n_items; it += w.n_waves)
         v2b_wave_task<NCH, STABLE, false>(g, load_item(items, it), head,
                                           w.lane, av, datt);
@@ -3682,7 +3446,7 @@ NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_gatv2_bwd_wave(
  * order and the forward's butterfly, so at the same form and R it is the
  * forward's score bit for bit.  Up to four edges are in flight, all their row
  * loads issued before the first is consumed, partial score and partial gdot
- * summed by ONE interleaved butterfly (V2bSumSeg / V2bSumWave).
+ * summed by ONE interleaved butterfly (SumSeg / SumWave).
  *   No sum spans items: both walks flatten (item, slab) tasks, there is no LDS
  * and no atomic for an unsplit vertex (a plain read-add-write, bit-
  * reproducible); a split vertex adds by fp32 atomics, one per (item, element),
@@ -3797,7 +3561,7 @@ __device__ __forceinline__ void dotb_item(float (&a1)[N], float (&a2)[N],
 }
 
 /* Fast form, C a power of two and L = C/R <= 64: the geometry of
- * k_dot_fused_seg (G lanes per (item, slab) task, a lane R consecutive
+ * k_attn_fwd_seg (G lanes per (item, slab) task, a lane R consecutive
  * columns of one head, slabs of whole heads, lanes past the row's end whole
  * segments that take no part); NE = edges in flight. */
 template <int R, int NE, bool STABLE, bool CSR, typename T>
@@ -3816,7 +3580,7 @@ NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_bwd_seg(
     const Item im = load_item(items, (uint32_t)(t / n_slabs));
     float a1[R] = {}, a2[R] = {};
     dotb_item<R, NE, STABLE, CSR>(a1, a2, g, im, col, col / g.C,
-                                  V2bLoadSeg<R>{}, V2bSumSeg{L});
+                                  ColsSeg<R>{}, SumSeg{L});
     const uint64_t own = (uint64_t)im.v * g.f + col;
     store_acc<R>(g.grad_1 + own, a1, R, im.shared);
     if constexpr (CSR) store_acc<R>(g.grad_2 + own, a2, R, im.shared);
@@ -3826,7 +3590,7 @@ NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_bwd_seg(
 /* General form, any K and C <= 64*NCH: a wave per (item, head), lane l owns
  * the head's columns l + 64*i (dead ones hold zeros and are never stored).
  * Two gathered rows per edge beside the two own rows: NE = 4 / 4 / 2 / 1 / 1
- * edges in flight at NCH = 1 / 2 / 4 / 8 / 16, as in k_dot_fused_wave, so
+ * edges in flight at NCH = 1 / 2 / 4 / 8 / 16, as DotFwd::wave_edges, so
  * that both rows of every edge stay in registers. */
 template <int NCH, bool STABLE, bool CSR, typename T>
 NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_bwd_wave(
@@ -3842,8 +3606,8 @@ NTS_NO_PK __global__ __launch_bounds__(NTS_BLOCK) void k_dot_bwd_wave(
     const uint32_t col = head * g.C + w.lane;
     float a1[NCH] = {}, a2[NCH] = {};
     dotb_item<NCH, NE, STABLE, CSR>(a1, a2, g, im, col, head,
-                                    V2bLoadWave<NCH>{w.lane, g.C},
-                                    V2bSumWave{});
+                                    ColsWave<NCH>{w.lane, g.C},
+                                    SumWave{});
     const uint64_t own = (uint64_t)im.v * g.f + col;
 #pragma unroll
     for (int i = 0; i < NCH; ++i)
@@ -5955,119 +5719,108 @@ static Gatv2FusedPlan plan_gatv2_fused(uint32_t f, uint32_t K,
   return p;
 }
 
-/* grown on demand, never cleared: a merge reads only records that the row
- * pass of the same call wrote in full */
-static float *get_v2_scratch(nts_stream *s, uint64_t bytes) {
-  if (s->v2_cap < bytes) {
-    NTS_CHECK(hipStreamSynchronize(s->stream));
-    if (s->v2_ws) NTS_CHECK(hipFree(s->v2_ws));
-    NTS_CHECK(hipMalloc(&s->v2_ws, bytes));
-    s->v2_cap = bytes;
-  }
-  return s->v2_ws;
+static void report_fused_plan(const Gatv2FusedPlan &p, int *form,
+                              int *cols_per_lane, int *lane_group, int *slabs,
+                              int *grid, unsigned long long *scratch_bytes) {
+  if (form) *form = p.form;
+  if (cols_per_lane) *cols_per_lane = (int)p.R;
+  if (lane_group) *lane_group = (int)p.G;
+  if (slabs) *slabs = (int)p.slabs;
+  if (grid) *grid = (int)p.grid;
+  if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
 }
 
-/* the launches of the stats entries: the twins that also store (M, S) */
-template <typename T>
-static void launch_gatv2_fused_stats(nts_stream *s, const Gatv2FusedPlan &pl,
-                                     const EdgeItems &p, const T *x_l,
-                                     const T *x_r, float *out,
-                                     const float *att, float *scratch,
-                                     float slope, const nts_vid *row_indices,
-                                     const nts_vid *offset, nts_vid src_start,
-                                     nts_vid f, nts_vid K, float *ms) {
-  const bool st = s->softmax_stable;
-  const uint32_t C = f / K;
+/* The instantiation of a fused walk, forward or backward, from its plan and
+ * the softmax mode: seg(R, STABLE) for the fast form, R in {4, 2, 1}, or
+ * wave(NCH, STABLE) for the general one, NCH in {1, 2, 4, 8, 16}, both as
+ * std::integral_constant values. */
+template <class Plan, class Seg, class Wave>
+static void dispatch_form(const Plan &pl, bool stable, const Seg &seg,
+                          const Wave &wave) {
+  const auto with_mode = [&](const auto &fn, auto n) {
+    if (stable) fn(n, std::true_type{});
+    else fn(n, std::false_type{});
+  };
+  using std::integral_constant;
   if (pl.form == 1) {
-#define NTS_K(RR)                                                             \
-  (st ? k_gatv2_fused_seg_stats<RR, true, T>                                  \
-      : k_gatv2_fused_seg_stats<RR, false, T>)
-    hipLaunchKernelGGL(pl.R == 4 ? NTS_K(4) : pl.R == 2 ? NTS_K(2) : NTS_K(1),
-                       dim3(pl.grid), dim3(NTS_BLOCK), 0, s->stream,
-                       p.ib->items, p.ib->counter, row_indices, x_l, x_r, att,
-                       out, scratch, slope, src_start, f, K, C, pl.G,
-                       pl.slabs, ms);
-#undef NTS_K
+    if (pl.R == 4) with_mode(seg, integral_constant<int, 4>{});
+    else if (pl.R == 2) with_mode(seg, integral_constant<int, 2>{});
+    else with_mode(seg, integral_constant<int, 1>{});
   } else {
-    /* indexed by log2(NCH) */
-    static const decltype(&k_gatv2_fused_wave_stats<1, false, T>)
-        kernels[2][5] = {{k_gatv2_fused_wave_stats<1, false, T>,
-                          k_gatv2_fused_wave_stats<2, false, T>,
-                          k_gatv2_fused_wave_stats<4, false, T>,
-                          k_gatv2_fused_wave_stats<8, false, T>,
-                          k_gatv2_fused_wave_stats<16, false, T>},
-                         {k_gatv2_fused_wave_stats<1, true, T>,
-                          k_gatv2_fused_wave_stats<2, true, T>,
-                          k_gatv2_fused_wave_stats<4, true, T>,
-                          k_gatv2_fused_wave_stats<8, true, T>,
-                          k_gatv2_fused_wave_stats<16, true, T>}};
-    hipLaunchKernelGGL(kernels[st][__builtin_ctz(pl.nch)], dim3(pl.grid),
-                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-                       p.ib->counter, row_indices, x_l, x_r, att, out, scratch,
-                       slope, src_start, f, K, C, ms);
+    switch (pl.nch) {
+      case 1: return with_mode(wave, integral_constant<int, 1>{});
+      case 2: return with_mode(wave, integral_constant<int, 2>{});
+      case 4: return with_mode(wave, integral_constant<int, 4>{});
+      case 8: return with_mode(wave, integral_constant<int, 8>{});
+      default: return with_mode(wave, integral_constant<int, 16>{});
+    }
   }
-  if (scratch)
-    hipLaunchKernelGGL(k_gatv2_fused_merge_stats, dim3(p.grid),
-                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-                       p.ib->counter, offset, scratch, out, NTS_SPLIT, f, K, C,
-                       ms);
 }
 
-/* ms != nullptr: the stats entries */
-template <typename T>
-static int gatv2_forward_fused(nts_stream *s, const char *entry, const T *x_l,
-                               const T *x_r, float *out, const float *att,
-                               float slope, const nts_vid *row_indices,
-                               const nts_vid *offset, nts_vid src_start,
-                               nts_vid batch, nts_vid edges, nts_vid f,
-                               nts_vid K, float *ms = nullptr) {
-  check_heads(entry, f, K);
+/* a stream buffer grown on demand; the stream drains before the old one
+ * goes */
+template <typename P>
+static P *grow_scratch(nts_stream *s, P *&ws, uint64_t &cap, uint64_t bytes) {
+  if (cap < bytes) {
+    NTS_CHECK(hipStreamSynchronize(s->stream));
+    if (ws) NTS_CHECK(hipFree(ws));
+    NTS_CHECK(hipMalloc(&ws, bytes));
+    cap = bytes;
+  }
+  return ws;
+}
+
+/* never cleared: a merge reads only records that the row pass of the same
+ * call wrote in full */
+static float *get_v2_scratch(nts_stream *s, uint64_t bytes) {
+  return grow_scratch(s, s->v2_ws, s->v2_cap, bytes);
+}
+
+/* One driver for every fused forward entry: g is the entry's model with C
+ * still open, ms != nullptr the stats entries. */
+template <class Model>
+static int attn_forward_fused(nts_stream *s, const char *entry, Model g,
+                              float *out, const nts_vid *offset, nts_vid batch,
+                              nts_vid edges, float *ms) {
+  check_heads(entry, g.f, g.K);
   s->softmax_stable_last = s->softmax_stable;
   if (!batch || !edges) return 1;
+  g.C = g.f / g.K;
   const Gatv2FusedPlan pl = plan_gatv2_fused(
-      f, K, sizeof(T), (uintptr_t)x_l | (uintptr_t)x_r,
-      (uintptr_t)att | (uintptr_t)out, batch, edges, s->heads_general);
+      g.f, g.K, sizeof(typename Model::elem), g.row_alignment(),
+      g.fp32_alignment() | (uintptr_t)out, batch, edges, s->heads_general);
   if (!pl.form) return 0;
   const EdgeItems p = edge_items_known(s, offset, batch, edges);
   float *scratch =
       pl.scratch_bytes ? get_v2_scratch(s, pl.scratch_bytes) : nullptr;
-  const bool st = s->softmax_stable;
-  const uint32_t C = f / K;
+  const AttnFwdOut o{out, scratch, ms};
   Tic t(s, NTS_KTAG_FWD);
-  if (ms) {
-    launch_gatv2_fused_stats(s, pl, p, x_l, x_r, out, att, scratch, slope,
-                             row_indices, offset, src_start, f, K, ms);
-    dbg_sync(s, "k_gatv2_fused (stats)");
-    return 1;
-  }
-  if (pl.form == 1) {
-#define NTS_K(RR)                                                             \
-  (st ? k_gatv2_fused_seg<RR, true, T> : k_gatv2_fused_seg<RR, false, T>)
-    hipLaunchKernelGGL(pl.R == 4 ? NTS_K(4) : pl.R == 2 ? NTS_K(2) : NTS_K(1),
-                       dim3(pl.grid), dim3(NTS_BLOCK), 0, s->stream,
-                       p.ib->items, p.ib->counter, row_indices, x_l, x_r, att,
-                       out, scratch, slope, src_start, f, K, C, pl.G,
-                       pl.slabs);
-#undef NTS_K
-  } else {
-    /* indexed by log2(NCH) */
-    static const decltype(&k_gatv2_fused_wave<1, false, T>) kernels[2][5] = {
-        {k_gatv2_fused_wave<1, false, T>, k_gatv2_fused_wave<2, false, T>,
-         k_gatv2_fused_wave<4, false, T>, k_gatv2_fused_wave<8, false, T>,
-         k_gatv2_fused_wave<16, false, T>},
-        {k_gatv2_fused_wave<1, true, T>, k_gatv2_fused_wave<2, true, T>,
-         k_gatv2_fused_wave<4, true, T>, k_gatv2_fused_wave<8, true, T>,
-         k_gatv2_fused_wave<16, true, T>}};
-    hipLaunchKernelGGL(kernels[st][__builtin_ctz(pl.nch)], dim3(pl.grid),
-                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-                       p.ib->counter, row_indices, x_l, x_r, att, out, scratch,
-                       slope, src_start, f, K, C);
-  }
-  if (scratch)
-    hipLaunchKernelGGL(k_gatv2_fused_merge, dim3(p.grid), dim3(NTS_BLOCK), 0,
-                       s->stream, p.ib->items, p.ib->counter, offset, scratch,
-                       out, NTS_SPLIT, f, K, C);
-  dbg_sync(s, "k_gatv2_fused");
+  const auto launch = [&](auto stats) {
+    constexpr bool STATS = decltype(stats)::value;
+    dispatch_form(
+        pl, s->softmax_stable,
+        [&](auto r, auto stable) {
+          const auto kernel = k_attn_fwd_seg<Model, decltype(r)::value,
+                                             decltype(stable)::value, STATS>;
+          hipLaunchKernelGGL(kernel, dim3(pl.grid), dim3(NTS_BLOCK), 0,
+                             s->stream, p.ib->items, p.ib->counter, g, o, pl.G,
+                             pl.slabs);
+        },
+        [&](auto nch, auto stable) {
+          const auto kernel = k_attn_fwd_wave<Model, decltype(nch)::value,
+                                              decltype(stable)::value, STATS>;
+          hipLaunchKernelGGL(kernel, dim3(pl.grid), dim3(NTS_BLOCK), 0,
+                             s->stream, p.ib->items, p.ib->counter, g, o);
+        });
+    if (scratch)
+      hipLaunchKernelGGL(k_attn_fwd_merge<STATS>, dim3(p.grid),
+                         dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
+                         p.ib->counter, offset, scratch, out, NTS_SPLIT, g.f,
+                         g.K, g.C, ms);
+  };
+  if (ms) launch(std::true_type{});
+  else launch(std::false_type{});
+  dbg_sync(s, entry);
   return 1;
 }
 }  // extern "C++"
@@ -6078,9 +5831,11 @@ int nts_gatv2_forward_fused(nts_stream *s, const float *x_l, const float *x_r,
                             const nts_vid *column_offset, nts_vid src_start,
                             nts_vid batch_size, nts_vid edges,
                             nts_vid feature_size, nts_vid heads) {
-  return gatv2_forward_fused(s, "nts_gatv2_forward_fused", x_l, x_r, output,
-                             att, slope, row_indices, column_offset, src_start,
-                             batch_size, edges, feature_size, heads);
+  return attn_forward_fused(
+      s, "nts_gatv2_forward_fused",
+      V2Fwd<float>{row_indices, x_l, x_r, att, slope, src_start, feature_size,
+                   heads},
+      output, column_offset, batch_size, edges, nullptr);
 }
 
 int nts_gatv2_forward_fused_bf16(nts_stream *s, const uint16_t *x_l,
@@ -6091,9 +5846,11 @@ int nts_gatv2_forward_fused_bf16(nts_stream *s, const uint16_t *x_l,
                                  nts_vid src_start, nts_vid batch_size,
                                  nts_vid edges, nts_vid feature_size,
                                  nts_vid heads) {
-  return gatv2_forward_fused(s, "nts_gatv2_forward_fused_bf16", x_l, x_r,
-                             output, att, slope, row_indices, column_offset,
-                             src_start, batch_size, edges, feature_size, heads);
+  return attn_forward_fused(
+      s, "nts_gatv2_forward_fused_bf16",
+      V2Fwd<uint16_t>{row_indices, x_l, x_r, att, slope, src_start,
+                      feature_size, heads},
+      output, column_offset, batch_size, edges, nullptr);
 }
 
 int nts_gatv2_forward_fused_stats(nts_stream *s, const float *x_l,
@@ -6104,10 +5861,11 @@ int nts_gatv2_forward_fused_stats(nts_stream *s, const float *x_l,
                                   nts_vid src_start, nts_vid batch_size,
                                   nts_vid edges, nts_vid feature_size,
                                   nts_vid heads, float *ms) {
-  return gatv2_forward_fused(s, "nts_gatv2_forward_fused_stats", x_l, x_r,
-                             output, att, slope, row_indices, column_offset,
-                             src_start, batch_size, edges, feature_size, heads,
-                             ms);
+  return attn_forward_fused(
+      s, "nts_gatv2_forward_fused_stats",
+      V2Fwd<float>{row_indices, x_l, x_r, att, slope, src_start, feature_size,
+                   heads},
+      output, column_offset, batch_size, edges, ms);
 }
 
 int nts_gatv2_forward_fused_stats_bf16(nts_stream *s, const uint16_t *x_l,
@@ -6118,10 +5876,11 @@ int nts_gatv2_forward_fused_stats_bf16(nts_stream *s, const uint16_t *x_l,
                                        nts_vid src_start, nts_vid batch_size,
                                        nts_vid edges, nts_vid feature_size,
                                        nts_vid heads, float *ms) {
-  return gatv2_forward_fused(s, "nts_gatv2_forward_fused_stats_bf16", x_l, x_r,
-                             output, att, slope, row_indices, column_offset,
-                             src_start, batch_size, edges, feature_size, heads,
-                             ms);
+  return attn_forward_fused(
+      s, "nts_gatv2_forward_fused_stats_bf16",
+      V2Fwd<uint16_t>{row_indices, x_l, x_r, att, slope, src_start,
+                      feature_size, heads},
+      output, column_offset, batch_size, edges, ms);
 }
 
 void nts_gatv2_forward_fused_plan(nts_vid feature_size, nts_vid heads,
@@ -6133,124 +5892,15 @@ void nts_gatv2_forward_fused_plan(nts_vid feature_size, nts_vid heads,
                                   int *lane_group, int *slabs, int *grid,
                                   unsigned long long *scratch_bytes) {
   check_heads("nts_gatv2_forward_fused_plan", feature_size, heads);
-  const Gatv2FusedPlan p = plan_gatv2_fused(
-      feature_size, heads, elem_bytes, row_alignment_bytes,
-      fp32_alignment_bytes, batch_size, edges, general != 0);
-  if (form) *form = p.form;
-  if (cols_per_lane) *cols_per_lane = (int)p.R;
-  if (lane_group) *lane_group = (int)p.G;
-  if (slabs) *slabs = (int)p.slabs;
-  if (grid) *grid = (int)p.grid;
-  if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+  report_fused_plan(
+      plan_gatv2_fused(feature_size, heads, elem_bytes, row_alignment_bytes,
+                       fp32_alignment_bytes, batch_size, edges, general != 0),
+      form, cols_per_lane, lane_group, slabs, grid, scratch_bytes);
 }
 
 /* ---- fused dot-product attention forward (additive; see nts_hip.h) ---- */
-extern "C++" {
-/* the launches of the stats entries: the twins that also store (M, S) */
-template <typename T>
-static void launch_dot_fused_stats(nts_stream *s, const Gatv2FusedPlan &pl,
-                                   const EdgeItems &p, const T *q, const T *k,
-                                   const T *v, float *out, float *scratch,
-                                   float scale, const nts_vid *row_indices,
-                                   const nts_vid *offset, nts_vid src_start,
-                                   nts_vid f, nts_vid K, float *ms) {
-  const bool st = s->softmax_stable;
-  const uint32_t C = f / K;
-  if (pl.form == 1) {
-#define NTS_K(RR)                                                             \
-  (st ? k_dot_fused_seg_stats<RR, true, T>                                    \
-      : k_dot_fused_seg_stats<RR, false, T>)
-    hipLaunchKernelGGL(pl.R == 4 ? NTS_K(4) : pl.R == 2 ? NTS_K(2) : NTS_K(1),
-                       dim3(pl.grid), dim3(NTS_BLOCK), 0, s->stream,
-                       p.ib->items, p.ib->counter, row_indices, q, k, v, out,
-                       scratch, scale, src_start, f, K, C, pl.G, pl.slabs, ms);
-#undef NTS_K
-  } else {
-    /* indexed by log2(NCH) */
-    static const decltype(&k_dot_fused_wave_stats<1, false, T>)
-        kernels[2][5] = {{k_dot_fused_wave_stats<1, false, T>,
-                          k_dot_fused_wave_stats<2, false, T>,
-                          k_dot_fused_wave_stats<4, false, T>,
-                          k_dot_fused_wave_stats<8, false, T>,
-                          k_dot_fused_wave_stats<16, false, T>},
-                         {k_dot_fused_wave_stats<1, true, T>,
-                          k_dot_fused_wave_stats<2, true, T>,
-                          k_dot_fused_wave_stats<4, true, T>,
-                          k_dot_fused_wave_stats<8, true, T>,
-                          k_dot_fused_wave_stats<16, true, T>}};
-    hipLaunchKernelGGL(kernels[st][__builtin_ctz(pl.nch)], dim3(pl.grid),
-                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-                       p.ib->counter, row_indices, q, k, v, out, scratch,
-                       scale, src_start, f, K, C, ms);
-  }
-  if (scratch)
-    hipLaunchKernelGGL(k_gatv2_fused_merge_stats, dim3(p.grid),
-                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-                       p.ib->counter, offset, scratch, out, NTS_SPLIT, f, K, C,
-                       ms);
-}
-
 /* The plan is plan_gatv2_fused's: q, k and v are the rows, the output the
- * only fp32 operand.  ms != nullptr: the stats entries. */
-template <typename T>
-static int dot_attention_forward_fused(nts_stream *s, const char *entry,
-                                       const T *q, const T *k, const T *v,
-                                       float *out, float scale,
-                                       const nts_vid *row_indices,
-                                       const nts_vid *offset,
-                                       nts_vid src_start, nts_vid batch,
-                                       nts_vid edges, nts_vid f, nts_vid K,
-                                       float *ms = nullptr) {
-  check_heads(entry, f, K);
-  s->softmax_stable_last = s->softmax_stable;
-  if (!batch || !edges) return 1;
-  const Gatv2FusedPlan pl = plan_gatv2_fused(
-      f, K, sizeof(T), (uintptr_t)q | (uintptr_t)k | (uintptr_t)v,
-      (uintptr_t)out, batch, edges, s->heads_general);
-  if (!pl.form) return 0;
-  const EdgeItems p = edge_items_known(s, offset, batch, edges);
-  float *scratch =
-      pl.scratch_bytes ? get_v2_scratch(s, pl.scratch_bytes) : nullptr;
-  const bool st = s->softmax_stable;
-  const uint32_t C = f / K;
-  Tic t(s, NTS_KTAG_FWD);
-  if (ms) {
-    launch_dot_fused_stats(s, pl, p, q, k, v, out, scratch, scale, row_indices,
-                           offset, src_start, f, K, ms);
-    dbg_sync(s, "k_dot_fused (stats)");
-    return 1;
-  }
-  if (pl.form == 1) {
-#define NTS_K(RR)                                                             \
-  (st ? k_dot_fused_seg<RR, true, T> : k_dot_fused_seg<RR, false, T>)
-    hipLaunchKernelGGL(pl.R == 4 ? NTS_K(4) : pl.R == 2 ? NTS_K(2) : NTS_K(1),
-                       dim3(pl.grid), dim3(NTS_BLOCK), 0, s->stream,
-                       p.ib->items, p.ib->counter, row_indices, q, k, v, out,
-                       scratch, scale, src_start, f, K, C, pl.G, pl.slabs);
-#undef NTS_K
-  } else {
-    /* indexed by log2(NCH) */
-    static const decltype(&k_dot_fused_wave<1, false, T>) kernels[2][5] = {
-        {k_dot_fused_wave<1, false, T>, k_dot_fused_wave<2, false, T>,
-         k_dot_fused_wave<4, false, T>, k_dot_fused_wave<8, false, T>,
-         k_dot_fused_wave<16, false, T>},
-        {k_dot_fused_wave<1, true, T>, k_dot_fused_wave<2, true, T>,
-         k_dot_fused_wave<4, true, T>, k_dot_fused_wave<8, true, T>,
-         k_dot_fused_wave<16, true, T>}};
-    hipLaunchKernelGGL(kernels[st][__builtin_ctz(pl.nch)], dim3(pl.grid),
-                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-                       p.ib->counter, row_indices, q, k, v, out, scratch,
-                       scale, src_start, f, K, C);
-  }
-  if (scratch)
-    hipLaunchKernelGGL(k_gatv2_fused_merge, dim3(p.grid), dim3(NTS_BLOCK), 0,
-                       s->stream, p.ib->items, p.ib->counter, offset, scratch,
-                       out, NTS_SPLIT, f, K, C);
-  dbg_sync(s, "k_dot_fused");
-  return 1;
-}
-}  // extern "C++"
-
+ * only fp32 operand. */
 int nts_dot_attention_forward_fused(nts_stream *s, const float *q,
                                     const float *k, const float *v,
                                     float *output, float scale,
@@ -6259,10 +5909,11 @@ int nts_dot_attention_forward_fused(nts_stream *s, const float *q,
                                     nts_vid src_start, nts_vid batch_size,
                                     nts_vid edges, nts_vid feature_size,
                                     nts_vid heads) {
-  return dot_attention_forward_fused(
-      s, "nts_dot_attention_forward_fused", q, k, v, output, scale,
-      row_indices, column_offset, src_start, batch_size, edges, feature_size,
-      heads);
+  return attn_forward_fused(
+      s, "nts_dot_attention_forward_fused",
+      DotFwd<float>{row_indices, q, k, v, scale, src_start, feature_size,
+                    heads},
+      output, column_offset, batch_size, edges, nullptr);
 }
 
 int nts_dot_attention_forward_fused_bf16(nts_stream *s, const uint16_t *q,
@@ -6273,10 +5924,11 @@ int nts_dot_attention_forward_fused_bf16(nts_stream *s, const uint16_t *q,
                                          nts_vid src_start, nts_vid batch_size,
                                          nts_vid edges, nts_vid feature_size,
                                          nts_vid heads) {
-  return dot_attention_forward_fused(
-      s, "nts_dot_attention_forward_fused_bf16", q, k, v, output, scale,
-      row_indices, column_offset, src_start, batch_size, edges, feature_size,
-      heads);
+  return attn_forward_fused(
+      s, "nts_dot_attention_forward_fused_bf16",
+      DotFwd<uint16_t>{row_indices, q, k, v, scale, src_start, feature_size,
+                       heads},
+      output, column_offset, batch_size, edges, nullptr);
 }
 
 int nts_dot_attention_forward_fused_stats(nts_stream *s, const float *q,
@@ -6288,10 +5940,11 @@ int nts_dot_attention_forward_fused_stats(nts_stream *s, const float *q,
                                           nts_vid batch_size, nts_vid edges,
                                           nts_vid feature_size, nts_vid heads,
                                           float *ms) {
-  return dot_attention_forward_fused(
-      s, "nts_dot_attention_forward_fused_stats", q, k, v, output, scale,
-      row_indices, column_offset, src_start, batch_size, edges, feature_size,
-      heads, ms);
+  return attn_forward_fused(
+      s, "nts_dot_attention_forward_fused_stats",
+      DotFwd<float>{row_indices, q, k, v, scale, src_start, feature_size,
+                    heads},
+      output, column_offset, batch_size, edges, ms);
 }
 
 int nts_dot_attention_forward_fused_stats_bf16(
@@ -6299,10 +5952,11 @@ int nts_dot_attention_forward_fused_stats_bf16(
     float *output, float scale, const nts_vid *row_indices,
     const nts_vid *column_offset, nts_vid src_start, nts_vid batch_size,
     nts_vid edges, nts_vid feature_size, nts_vid heads, float *ms) {
-  return dot_attention_forward_fused(
-      s, "nts_dot_attention_forward_fused_stats_bf16", q, k, v, output, scale,
-      row_indices, column_offset, src_start, batch_size, edges, feature_size,
-      heads, ms);
+  return attn_forward_fused(
+      s, "nts_dot_attention_forward_fused_stats_bf16",
+      DotFwd<uint16_t>{row_indices, q, k, v, scale, src_start, feature_size,
+                       heads},
+      output, column_offset, batch_size, edges, ms);
 }
 
 void nts_dot_attention_forward_fused_plan(
@@ -6312,15 +5966,10 @@ void nts_dot_attention_forward_fused_plan(
     int *cols_per_lane, int *lane_group, int *slabs, int *grid,
     unsigned long long *scratch_bytes) {
   check_heads("nts_dot_attention_forward_fused_plan", feature_size, heads);
-  const Gatv2FusedPlan p = plan_gatv2_fused(
-      feature_size, heads, elem_bytes, row_alignment_bytes,
-      fp32_alignment_bytes, batch_size, edges, general != 0);
-  if (form) *form = p.form;
-  if (cols_per_lane) *cols_per_lane = (int)p.R;
-  if (lane_group) *lane_group = (int)p.G;
-  if (slabs) *slabs = (int)p.slabs;
-  if (grid) *grid = (int)p.grid;
-  if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+  report_fused_plan(
+      plan_gatv2_fused(feature_size, heads, elem_bytes, row_alignment_bytes,
+                       fp32_alignment_bytes, batch_size, edges, general != 0),
+      form, cols_per_lane, lane_group, slabs, grid, scratch_bytes);
 }
 
 /* ---- fused GAT training backward (additive; see include/nts_hip.h) ---- */
@@ -6371,48 +6020,45 @@ static GatBwdPlan plan_gat_backward(uint32_t f, uint32_t K,
   return p;
 }
 
-/* grown on demand, never cleared: the record pass writes every record of
- * the call before a walk reads one */
+static void report_fused_plan(const GatBwdPlan &p, int *form,
+                              int *cols_per_lane, int *lane_group, int *slabs,
+                              int *grid_csr, int *grid_csc,
+                              unsigned long long *scratch_bytes) {
+  if (form) *form = p.form;
+  if (cols_per_lane) *cols_per_lane = (int)p.R;
+  if (lane_group) *lane_group = (int)p.G;
+  if (slabs) *slabs = (int)p.slabs;
+  if (grid_csr) *grid_csr = (int)p.grid_csr;
+  if (grid_csc) *grid_csc = (int)p.grid_csc;
+  if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+}
+
+/* never cleared: the record pass writes every record of the call before a
+ * walk reads one */
 static float4 *get_rec_scratch(nts_stream *s, uint64_t bytes) {
-  if (s->rec_cap < bytes) {
-    NTS_CHECK(hipStreamSynchronize(s->stream));
-    if (s->rec_ws) NTS_CHECK(hipFree(s->rec_ws));
-    NTS_CHECK(hipMalloc(&s->rec_ws, bytes));
-    s->rec_cap = bytes;
-  }
-  return s->rec_ws;
+  return grow_scratch(s, s->rec_ws, s->rec_cap, bytes);
 }
 
 template <bool CSR, typename TO, typename TG>
 static void launch_gat_bwd_walk(nts_stream *s, const EdgeItems &p,
                                 const GatBwdPlan &pl, uint32_t grid,
                                 const GatBwd<TO, TG> &g) {
-  const bool st = s->softmax_stable;
-  if (pl.form == 1) {
-#define NTS_K(RR)                                                             \
-  (st ? k_gat_bwd_seg<RR, true, CSR, TO, TG>                                  \
-      : k_gat_bwd_seg<RR, false, CSR, TO, TG>)
-    hipLaunchKernelGGL(pl.R == 4 ? NTS_K(4) : pl.R == 2 ? NTS_K(2) : NTS_K(1),
-                       dim3(grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-                       p.ib->counter, g, pl.G, pl.slabs);
-#undef NTS_K
-  } else {
-    /* indexed by log2(NCH) */
-    static const decltype(&k_gat_bwd_wave<1, false, CSR, TO, TG>)
-        kernels[2][5] = {{k_gat_bwd_wave<1, false, CSR, TO, TG>,
-                          k_gat_bwd_wave<2, false, CSR, TO, TG>,
-                          k_gat_bwd_wave<4, false, CSR, TO, TG>,
-                          k_gat_bwd_wave<8, false, CSR, TO, TG>,
-                          k_gat_bwd_wave<16, false, CSR, TO, TG>},
-                         {k_gat_bwd_wave<1, true, CSR, TO, TG>,
-                          k_gat_bwd_wave<2, true, CSR, TO, TG>,
-                          k_gat_bwd_wave<4, true, CSR, TO, TG>,
-                          k_gat_bwd_wave<8, true, CSR, TO, TG>,
-                          k_gat_bwd_wave<16, true, CSR, TO, TG>}};
-    hipLaunchKernelGGL(kernels[st][__builtin_ctz(pl.nch)], dim3(grid),
-                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-                       p.ib->counter, g);
-  }
+  dispatch_form(
+      pl, s->softmax_stable,
+      [&](auto r, auto stable) {
+        const auto kernel =
+            k_gat_bwd_seg<decltype(r)::value, decltype(stable)::value, CSR, TO,
+                          TG>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(NTS_BLOCK), 0, s->stream,
+                           p.ib->items, p.ib->counter, g, pl.G, pl.slabs);
+      },
+      [&](auto nch, auto stable) {
+        const auto kernel =
+            k_gat_bwd_wave<decltype(nch)::value, decltype(stable)::value, CSR,
+                           TO, TG>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(NTS_BLOCK), 0, s->stream,
+                           p.ib->items, p.ib->counter, g);
+      });
 }
 
 /* Pass 1 and the record pass under NTS_KTAG_EDGE, the two walks under
@@ -6528,16 +6174,12 @@ void nts_gat_backward_fused_plan(nts_vid feature_size, nts_vid heads,
                                  int *slabs, int *grid_csr, int *grid_csc,
                                  unsigned long long *scratch_bytes) {
   check_heads("nts_gat_backward_fused_plan", feature_size, heads);
-  const GatBwdPlan p = plan_gat_backward(
-      feature_size, heads, elem_bytes, row_alignment_bytes,
-      fp32_alignment_bytes, src_rows, dst_rows, edges, general != 0);
-  if (form) *form = p.form;
-  if (cols_per_lane) *cols_per_lane = (int)p.R;
-  if (lane_group) *lane_group = (int)p.G;
-  if (slabs) *slabs = (int)p.slabs;
-  if (grid_csr) *grid_csr = (int)p.grid_csr;
-  if (grid_csc) *grid_csc = (int)p.grid_csc;
-  if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+  report_fused_plan(
+      plan_gat_backward(feature_size, heads, elem_bytes, row_alignment_bytes,
+                        fp32_alignment_bytes, src_rows, dst_rows, edges,
+                        general != 0),
+      form, cols_per_lane, lane_group, slabs, grid_csr, grid_csc,
+      scratch_bytes);
 }
 
 /* ---- fused GATv2 training backward (additive; see include/nts_hip.h) ---- */
@@ -6563,27 +6205,37 @@ template <bool CSR, typename T>
 static void launch_gatv2_bwd_walk(nts_stream *s, const EdgeItems &p,
                                   const GatBwdPlan &pl, uint32_t grid,
                                   const V2Bwd<T> &g) {
-  const bool st = s->softmax_stable;
-  if (pl.form == 1) {
-#define NTS_K(RR)                                                             \
-  (st ? k_gatv2_bwd_seg<RR, true, CSR, T> : k_gatv2_bwd_seg<RR, false, CSR, T>)
-    hipLaunchKernelGGL(pl.R == 4 ? NTS_K(4) : pl.R == 2 ? NTS_K(2) : NTS_K(1),
-                       dim3(grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-                       p.ib->counter, g, pl.G, pl.slabs);
-#undef NTS_K
-  } else {
-    /* indexed by log2(NCH) */
-    static const decltype(&k_gatv2_bwd_wave<1, false, CSR, T>) kernels[2][5] =
-        {{k_gatv2_bwd_wave<1, false, CSR, T>, k_gatv2_bwd_wave<2, false, CSR, T>,
-          k_gatv2_bwd_wave<4, false, CSR, T>, k_gatv2_bwd_wave<8, false, CSR, T>,
-          k_gatv2_bwd_wave<16, false, CSR, T>},
-         {k_gatv2_bwd_wave<1, true, CSR, T>, k_gatv2_bwd_wave<2, true, CSR, T>,
-          k_gatv2_bwd_wave<4, true, CSR, T>, k_gatv2_bwd_wave<8, true, CSR, T>,
-          k_gatv2_bwd_wave<16, true, CSR, T>}};
-    hipLaunchKernelGGL(kernels[st][__builtin_ctz(pl.nch)], dim3(grid),
-                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-                       p.ib->counter, g);
-  }
+  dispatch_form(
+      pl, s->softmax_stable,
+      [&](auto r, auto stable) {
+        const auto kernel = k_gatv2_bwd_seg<decltype(r)::value,
+                                            decltype(stable)::value, CSR, T>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(NTS_BLOCK), 0, s->stream,
+                           p.ib->items, p.ib->counter, g, pl.G, pl.slabs);
+      },
+      [&](auto nch, auto stable) {
+        const auto kernel = k_gatv2_bwd_wave<decltype(nch)::value,
+                                             decltype(stable)::value, CSR, T>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(NTS_BLOCK), 0, s->stream,
+                           p.ib->items, p.ib->counter, g);
+      });
+}
+
+/* the record pass of the GATv2 and the dot backward, under NTS_KTAG_EDGE */
+static void launch_v2_bwd_record(nts_stream *s, const char *label,
+                                 const float *gy, const float *y,
+                                 const float *ms, const nts_vid *column_offset,
+                                 float4 *recs, uint32_t dst_rows, uint32_t f,
+                                 uint32_t K) {
+  Tic t(s, NTS_KTAG_EDGE);
+  const uint32_t C = f / K;
+  uint32_t G = 1;
+  while (G < C && G < 64) G *= 2;
+  hipLaunchKernelGGL(k_gatv2_bwd_record,
+                     dim3(grid_for((uint64_t)dst_rows * K * G)),
+                     dim3(NTS_BLOCK), 0, s->stream, gy, y, ms, column_offset,
+                     recs, dst_rows, f, K, C, G);
+  dbg_sync(s, label);
 }
 
 /* The record pass under NTS_KTAG_EDGE, the two walks under NTS_KTAG_BWD.
@@ -6616,16 +6268,8 @@ static int gatv2_backward_fused(nts_stream *s, const char *entry, const T *x_l,
   const uint32_t C = f / K;
   const EdgeItems csc = edge_items_known(s, column_offset, dst_rows, edges);
   float4 *recs = get_rec_scratch(s, pl.scratch_bytes);
-  {
-    Tic t(s, NTS_KTAG_EDGE);
-    uint32_t G = 1;
-    while (G < C && G < 64) G *= 2;
-    hipLaunchKernelGGL(k_gatv2_bwd_record,
-                       dim3(grid_for((uint64_t)dst_rows * K * G)),
-                       dim3(NTS_BLOCK), 0, s->stream, gy, y, ms, column_offset,
-                       recs, dst_rows, f, K, C, G);
-    dbg_sync(s, "k_gatv2_bwd_record");
-  }
+  launch_v2_bwd_record(s, "k_gatv2_bwd_record", gy, y, ms, column_offset, recs,
+                       dst_rows, f, K);
   {
     Tic t(s, NTS_KTAG_BWD);
     launch_gatv2_bwd_walk<false>(
@@ -6685,16 +6329,12 @@ void nts_gatv2_backward_fused_plan(nts_vid feature_size, nts_vid heads,
                                    int *slabs, int *grid_csr, int *grid_csc,
                                    unsigned long long *scratch_bytes) {
   check_heads("nts_gatv2_backward_fused_plan", feature_size, heads);
-  const GatBwdPlan p = plan_gatv2_backward(
-      feature_size, heads, elem_bytes, row_alignment_bytes,
-      fp32_alignment_bytes, src_rows, dst_rows, edges, general != 0);
-  if (form) *form = p.form;
-  if (cols_per_lane) *cols_per_lane = (int)p.R;
-  if (lane_group) *lane_group = (int)p.G;
-  if (slabs) *slabs = (int)p.slabs;
-  if (grid_csr) *grid_csr = (int)p.grid_csr;
-  if (grid_csc) *grid_csc = (int)p.grid_csc;
-  if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+  report_fused_plan(
+      plan_gatv2_backward(feature_size, heads, elem_bytes, row_alignment_bytes,
+                          fp32_alignment_bytes, src_rows, dst_rows, edges,
+                          general != 0),
+      form, cols_per_lane, lane_group, slabs, grid_csr, grid_csc,
+      scratch_bytes);
 }
 
 /* ---- fused dot-product attention backward (additive; see nts_hip.h) ---- */
@@ -6709,29 +6349,21 @@ template <bool CSR, typename T>
 static void launch_dot_bwd_walk(nts_stream *s, const EdgeItems &p,
                                 const GatBwdPlan &pl, uint32_t grid,
                                 const DotBwd<T> &g) {
-  const bool st = s->softmax_stable;
   constexpr int NE = CSR ? NTS_DOTB_NE_CSR : NTS_DOTB_NE_CSC;
-  if (pl.form == 1) {
-#define NTS_K(RR)                                                             \
-  (st ? k_dot_bwd_seg<RR, NE, true, CSR, T>                                   \
-      : k_dot_bwd_seg<RR, NE, false, CSR, T>)
-    hipLaunchKernelGGL(pl.R == 4 ? NTS_K(4) : pl.R == 2 ? NTS_K(2) : NTS_K(1),
-                       dim3(grid), dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-                       p.ib->counter, g, pl.G, pl.slabs);
-#undef NTS_K
-  } else {
-    /* indexed by log2(NCH) */
-    static const decltype(&k_dot_bwd_wave<1, false, CSR, T>) kernels[2][5] = {
-        {k_dot_bwd_wave<1, false, CSR, T>, k_dot_bwd_wave<2, false, CSR, T>,
-         k_dot_bwd_wave<4, false, CSR, T>, k_dot_bwd_wave<8, false, CSR, T>,
-         k_dot_bwd_wave<16, false, CSR, T>},
-        {k_dot_bwd_wave<1, true, CSR, T>, k_dot_bwd_wave<2, true, CSR, T>,
-         k_dot_bwd_wave<4, true, CSR, T>, k_dot_bwd_wave<8, true, CSR, T>,
-         k_dot_bwd_wave<16, true, CSR, T>}};
-    hipLaunchKernelGGL(kernels[st][__builtin_ctz(pl.nch)], dim3(grid),
-                       dim3(NTS_BLOCK), 0, s->stream, p.ib->items,
-                       p.ib->counter, g);
-  }
+  dispatch_form(
+      pl, s->softmax_stable,
+      [&](auto r, auto stable) {
+        const auto kernel = k_dot_bwd_seg<decltype(r)::value, NE,
+                                          decltype(stable)::value, CSR, T>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(NTS_BLOCK), 0, s->stream,
+                           p.ib->items, p.ib->counter, g, pl.G, pl.slabs);
+      },
+      [&](auto nch, auto stable) {
+        const auto kernel = k_dot_bwd_wave<decltype(nch)::value,
+                                           decltype(stable)::value, CSR, T>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(NTS_BLOCK), 0, s->stream,
+                           p.ib->items, p.ib->counter, g);
+      });
 }
 
 /* The plan is plan_gat_backward's: both walks flatten (item, slab) tasks.
@@ -6760,16 +6392,8 @@ static int dot_attention_backward_fused(
   const uint32_t C = f / K;
   const EdgeItems csc = edge_items_known(s, column_offset, dst_rows, edges);
   float4 *recs = get_rec_scratch(s, pl.scratch_bytes);
-  {
-    Tic t(s, NTS_KTAG_EDGE);
-    uint32_t G = 1;
-    while (G < C && G < 64) G *= 2;
-    hipLaunchKernelGGL(k_gatv2_bwd_record,
-                       dim3(grid_for((uint64_t)dst_rows * K * G)),
-                       dim3(NTS_BLOCK), 0, s->stream, gy, y, ms, column_offset,
-                       recs, dst_rows, f, K, C, G);
-    dbg_sync(s, "k_gatv2_bwd_record (dot)");
-  }
+  launch_v2_bwd_record(s, "k_gatv2_bwd_record (dot)", gy, y, ms, column_offset,
+                       recs, dst_rows, f, K);
   {
     Tic t(s, NTS_KTAG_BWD);
     launch_dot_bwd_walk<false>(
@@ -6826,16 +6450,12 @@ void nts_dot_attention_backward_fused_plan(
     int *cols_per_lane, int *lane_group, int *slabs, int *grid_csr,
     int *grid_csc, unsigned long long *scratch_bytes) {
   check_heads("nts_dot_attention_backward_fused_plan", feature_size, heads);
-  const GatBwdPlan p = plan_gat_backward(
-      feature_size, heads, elem_bytes, row_alignment_bytes,
-      fp32_alignment_bytes, src_rows, dst_rows, edges, general != 0);
-  if (form) *form = p.form;
-  if (cols_per_lane) *cols_per_lane = (int)p.R;
-  if (lane_group) *lane_group = (int)p.G;
-  if (slabs) *slabs = (int)p.slabs;
-  if (grid_csr) *grid_csr = (int)p.grid_csr;
-  if (grid_csc) *grid_csc = (int)p.grid_csc;
-  if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+  report_fused_plan(
+      plan_gat_backward(feature_size, heads, elem_bytes, row_alignment_bytes,
+                        fp32_alignment_bytes, src_rows, dst_rows, edges,
+                        general != 0),
+      form, cols_per_lane, lane_group, slabs, grid_csr, grid_csc,
+      scratch_bytes);
 }
 
 int nts_gather_by_src_from_dst_dot(nts_stream *s, const float *input,

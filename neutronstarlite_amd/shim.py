@@ -326,6 +326,32 @@ def _plan_heads(entry, f, heads, alignment, batch, edges):
     return {n: o.value for n, o in zip(names, out)}
 
 
+def _plan_fused(entry, names, f, heads, general, *args):
+    check_heads(f, heads)
+    out = [_i32(0) for _ in names]
+    scratch = _c.c_ulonglong(0)
+    entry(f, heads, *args, 1 if general else 0, *[_c.byref(o) for o in out],
+          _c.byref(scratch))
+    plan = {n: o.value for n, o in zip(names, out)}
+    plan["scratch_bytes"] = scratch.value
+    return plan
+
+
+def _plan_fused_fwd(entry, f, heads, elem_bytes, row_alignment,
+                    fp32_alignment, batch, edges, general):
+    return _plan_fused(entry, ("form", "cols_per_lane", "lane_group", "slabs",
+                               "grid"), f, heads, general, elem_bytes,
+                       row_alignment, fp32_alignment, batch, edges)
+
+
+def _plan_fused_bwd(entry, f, heads, elem_bytes, row_alignment,
+                    fp32_alignment, src_rows, dst_rows, edges, general):
+    return _plan_fused(entry, ("form", "cols_per_lane", "lane_group", "slabs",
+                               "grid_csr", "grid_csc"), f, heads, general,
+                       elem_bytes, row_alignment, fp32_alignment, src_rows,
+                       dst_rows, edges)
+
+
 def gather_plan_heads(f, heads, alignment, batch, edges):
     """The launch decision of a heads gather (no device access): dict of
     lane_group, vector_width (4, 2 or 1 dwords per lane) and grid."""
@@ -349,16 +375,8 @@ def gatv2_forward_fused_plan(f, heads, elem_bytes, row_alignment,
     scratch_bytes.  elem_bytes 4 or 2; row_alignment the common alignment of
     x_l and x_r in bytes, fp32_alignment that of att and the output; general
     as under Stream.heads_dbg_general."""
-    check_heads(f, heads)
-    names = ("form", "cols_per_lane", "lane_group", "slabs", "grid")
-    out = [_i32(0) for _ in names]
-    scratch = _c.c_ulonglong(0)
-    lib().nts_gatv2_forward_fused_plan(
-        f, heads, elem_bytes, row_alignment, fp32_alignment, batch, edges,
-        1 if general else 0, *[_c.byref(o) for o in out], _c.byref(scratch))
-    plan = {n: o.value for n, o in zip(names, out)}
-    plan["scratch_bytes"] = scratch.value
-    return plan
+    return _plan_fused_fwd(lib().nts_gatv2_forward_fused_plan, f, heads, elem_bytes, row_alignment,
+                           fp32_alignment, batch, edges, general)
 
 
 def dot_attention_forward_fused_plan(f, heads, elem_bytes, row_alignment,
@@ -368,16 +386,8 @@ def dot_attention_forward_fused_plan(f, heads, elem_bytes, row_alignment,
     device access): the dict of gatv2_forward_fused_plan, whose geometry it
     is.  row_alignment is the common alignment of q, k and v in bytes,
     fp32_alignment that of the output."""
-    check_heads(f, heads)
-    names = ("form", "cols_per_lane", "lane_group", "slabs", "grid")
-    out = [_i32(0) for _ in names]
-    scratch = _c.c_ulonglong(0)
-    lib().nts_dot_attention_forward_fused_plan(
-        f, heads, elem_bytes, row_alignment, fp32_alignment, batch, edges,
-        1 if general else 0, *[_c.byref(o) for o in out], _c.byref(scratch))
-    plan = {n: o.value for n, o in zip(names, out)}
-    plan["scratch_bytes"] = scratch.value
-    return plan
+    return _plan_fused_fwd(lib().nts_dot_attention_forward_fused_plan, f, heads, elem_bytes, row_alignment,
+                           fp32_alignment, batch, edges, general)
 
 
 def gat_backward_fused_plan(f, heads, elem_bytes, row_alignment,
@@ -390,18 +400,8 @@ def gat_backward_fused_plan(f, heads, elem_bytes, row_alignment,
     elem_bytes 4 or 2; row_alignment the alignment of h in bytes,
     fp32_alignment the common one of grad_y and grad_h; general as under
     Stream.heads_dbg_general."""
-    check_heads(f, heads)
-    names = ("form", "cols_per_lane", "lane_group", "slabs", "grid_csr",
-             "grid_csc")
-    out = [_i32(0) for _ in names]
-    scratch = _c.c_ulonglong(0)
-    lib().nts_gat_backward_fused_plan(
-        f, heads, elem_bytes, row_alignment, fp32_alignment, src_rows,
-        dst_rows, edges, 1 if general else 0, *[_c.byref(o) for o in out],
-        _c.byref(scratch))
-    plan = {n: o.value for n, o in zip(names, out)}
-    plan["scratch_bytes"] = scratch.value
-    return plan
+    return _plan_fused_bwd(lib().nts_gat_backward_fused_plan, f, heads, elem_bytes, row_alignment,
+                           fp32_alignment, src_rows, dst_rows, edges, general)
 
 
 def gatv2_backward_fused_plan(f, heads, elem_bytes, row_alignment,
@@ -412,18 +412,8 @@ def gatv2_backward_fused_plan(f, heads, elem_bytes, row_alignment,
     common alignment of x_l and x_r in bytes, fp32_alignment that of grad_y,
     att, grad_x_l and grad_x_r; grid_csc is sized by the items alone (that
     walk loops over the slabs itself)."""
-    check_heads(f, heads)
-    names = ("form", "cols_per_lane", "lane_group", "slabs", "grid_csr",
-             "grid_csc")
-    out = [_i32(0) for _ in names]
-    scratch = _c.c_ulonglong(0)
-    lib().nts_gatv2_backward_fused_plan(
-        f, heads, elem_bytes, row_alignment, fp32_alignment, src_rows,
-        dst_rows, edges, 1 if general else 0, *[_c.byref(o) for o in out],
-        _c.byref(scratch))
-    plan = {n: o.value for n, o in zip(names, out)}
-    plan["scratch_bytes"] = scratch.value
-    return plan
+    return _plan_fused_bwd(lib().nts_gatv2_backward_fused_plan, f, heads, elem_bytes, row_alignment,
+                           fp32_alignment, src_rows, dst_rows, edges, general)
 
 
 def dot_attention_backward_fused_plan(f, heads, elem_bytes, row_alignment,
@@ -433,18 +423,8 @@ def dot_attention_backward_fused_plan(f, heads, elem_bytes, row_alignment,
     device access): the dict of gat_backward_fused_plan.  row_alignment is the
     common alignment of q, k and v in bytes, fp32_alignment that of grad_y,
     grad_q, grad_k and grad_v; both grids are sized by items * slabs."""
-    check_heads(f, heads)
-    names = ("form", "cols_per_lane", "lane_group", "slabs", "grid_csr",
-             "grid_csc")
-    out = [_i32(0) for _ in names]
-    scratch = _c.c_ulonglong(0)
-    lib().nts_dot_attention_backward_fused_plan(
-        f, heads, elem_bytes, row_alignment, fp32_alignment, src_rows,
-        dst_rows, edges, 1 if general else 0, *[_c.byref(o) for o in out],
-        _c.byref(scratch))
-    plan = {n: o.value for n, o in zip(names, out)}
-    plan["scratch_bytes"] = scratch.value
-    return plan
+    return _plan_fused_bwd(lib().nts_dot_attention_backward_fused_plan, f, heads, elem_bytes, row_alignment,
+                           fp32_alignment, src_rows, dst_rows, edges, general)
 
 
 def check_dropout(p, seed):

@@ -1299,6 +1299,36 @@ void nts_dot_attention_backward_fused_plan(nts_vid feature_size,
  * nts_items_cache_clear drops the cache. */
 void nts_items_reuse(nts_stream *s, int enable);
 
+/* Coalesce the parallel edges of one direction of a static chunk, once, for
+ * the weighted gathers: (offset[batch_size + 1], nbr[edges], weight[edges])
+ * on the device -> (offset_out[batch_size + 1], nbr_out[E'], weight_out[E'])
+ * with one entry per distinct (list, neighbour) pair.  Inside each list the
+ * neighbours of the output ascend strictly; weight_out is the fp32 sum of
+ * the merged edges' weights taken as ONE running sum in ascending original
+ * edge position, so the same input gives the same bits on every run.
+ * Returns E'.  When E' == edges there is nothing to merge: the out arrays
+ * are left unwritten and the caller keeps its original arrays.  The out
+ * arrays are sized by the caller for the upper bound (batch_size + 1 and
+ * edges entries) and must not alias the inputs.  offset[0] == 0 and
+ * offset[batch_size] == edges, as for every gather.
+ * Setup code: a stable radix sort of (list << 32 | nbr) with the original
+ * position as payload, a head-flag pass, a scan, and one thread per distinct
+ * pair that sums its run serially.  Transient scratch (24 bytes per edge) is
+ * freed before the entry returns; it runs on the stream and
+ * synchronizes it.  A gather over the output rounds (w1 + w2) * x where the
+ * original list rounds w1 * x + w2 * x. */
+long long nts_coalesce_edges(nts_stream *s, const nts_vid *offset,
+    const nts_vid *nbr, const float *weight, nts_vid batch_size,
+    nts_vid edges, nts_vid *offset_out, nts_vid *nbr_out, float *weight_out);
+
+/* Whether a chunk of this many edges is handed to nts_coalesce_edges (no
+ * device access).  request: 1 always, -1 never, 0 automatic — then the
+ * environment's NTS_GATHER_COALESCE (1 / -1) if set, else edges >=
+ * NTS_COALESCE_MIN_EDGES: small chunks keep their lists, and with them
+ * launches that are bit-identical to the uncoalesced ones. */
+#define NTS_COALESCE_MIN_EDGES (1u << 24)
+int nts_coalesce_plan(nts_vid edges, int request);
+
 /* CSR backward gather that ALSO emits the per-edge dot
  * dot_out[dot_pos[e]] = dot(input[column_indices[e]-dst_start], dot_vec[src])
  * from the same streamed row bytes (the GAT attention-scalar gradient).

@@ -3752,13 +3752,16 @@ constexpr uint32_t NTS_AUTO_WINDOW_STAGED = 128;
  * to (a multiple of 4; unset/0 = NTS_STAGE_PITCH_UNIT); NTS_GATHER_STRIPE is
  * the stripe request of streams that set none (floats; -1 never, unset/0
  * automatic) and NTS_GATHER_STRIPE_RUN the tasks per wave of a striped launch
- * (unset/0 = the fewest that fit the grid cap). */
+ * (unset/0 = the fewest that fit the grid cap); NTS_GATHER_COALESCE is the
+ * coalescing request of chunks that set none (1 force, -1 never, unset/0
+ * automatic; nts_coalesce_plan). */
 struct GatherEnv {
   bool forced = false;
   int sched = 0, window = 0;
   int stage = 0;                /* NTS_GATHER_STAGE: 0 auto, 1 force, -1 never */
   uint32_t stage_pitch = 0;     /* NTS_GATHER_STAGE_PITCH, 0 = the default */
   int stripe = 0;               /* NTS_GATHER_STRIPE: floats, -1 never, 0 auto */
+  int coalesce = 0;             /* NTS_GATHER_COALESCE: 1 force, -1 never, 0 auto */
   uint32_t stripe_run = 0;      /* NTS_GATHER_STRIPE_RUN, 0 = from the grid cap */
   uint32_t split, max_blocks, gather_blocks;
 };
@@ -3778,6 +3781,8 @@ const GatherEnv &gather_env() {
     const char *sp = getenv("NTS_GATHER_STRIPE");
     if (sp && *sp) v.stripe = atoi(sp) < 0 ? -1 : atoi(sp);
     v.stripe_run = env_u32("NTS_GATHER_STRIPE_RUN", 0);
+    const char *co = getenv("NTS_GATHER_COALESCE");
+    if (co && *co) v.coalesce = atoi(co) > 0 ? 1 : atoi(co) < 0 ? -1 : 0;
     v.split = NTS_SPLIT;
     v.max_blocks = NTS_MAX_BLOCKS;
     v.gather_blocks = nts_gather_blocks();
@@ -4348,6 +4353,255 @@ void launch_reduce(nts_stream *s, int op, const float *in, float *out,
                        dim3(row_grid), dim3(NTS_BLOCK), 0, s->stream, offset,
                        batch, NTS_SPLIT, out, arg, keys, f);
   dbg_sync(s, "k_gather_reduce");
+}
+
+/* ---- coalescing a static chunk's parallel edges (nts_coalesce_edges) ----
+ * Setup kernels, run once per chunk and direction: a stable LSD radix sort
+ * of (list << 32 | nbr) with the original position as payload, written here
+ * because the library sorts carry code objects of other architectures into
+ * the binary; then a rank of the runs' heads and one thread per run. */
+constexpr int NTS_CO_BITS = 4;                     /* radix digit */
+constexpr int NTS_CO_BINS = 1 << NTS_CO_BITS;
+constexpr int NTS_CO_ITEMS = 16;                   /* elements per thread */
+constexpr int NTS_CO_TILE = NTS_BLOCK * NTS_CO_ITEMS; /* per workgroup */
+constexpr uint32_t NTS_CO_NONE = 0xffu;            /* digit of a slot past n */
+
+/* key[e] = list of e << 32 | nbr[e], pos[e] = e, *nbr_max = max nbr.  The
+ * list is the last v with offset[v] <= e (empty lists share their offset
+ * with the next one). */
+__global__ void k_coalesce_keys(const uint32_t *__restrict__ offset,
+                                const uint32_t *__restrict__ nbr,
+                                uint32_t batch, uint64_t edges,
+                                unsigned long long *__restrict__ key,
+                                uint32_t *__restrict__ pos,
+                                uint32_t *__restrict__ nbr_max) {
+  uint32_t mx = 0;
+  for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < edges;
+       e += (uint64_t)gridDim.x * blockDim.x) {
+    uint32_t lo = 0, hi = batch; /* offset[lo] <= e < offset[hi] */
+    while (hi - lo > 1) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (offset[mid] <= e) lo = mid; else hi = mid;
+    }
+    const uint32_t n = nbr[e];
+    mx = max(mx, n);
+    key[e] = ((unsigned long long)lo << 32) | n;
+    pos[e] = (uint32_t)e;
+  }
+  atomicMax(nbr_max, mx);
+}
+
+/* the digit at `shift` of the key with its two halves packed together:
+ * list << nbr_bits | nbr */
+__device__ __forceinline__ uint32_t co_digit(unsigned long long key,
+                                             int nbr_bits, int shift) {
+  const unsigned long long packed =
+      ((key >> 32) << nbr_bits) | (key & 0xffffffffull);
+  return (uint32_t)(packed >> shift) & (NTS_CO_BINS - 1);
+}
+
+/* One tile of a radix pass.  Thread t owns the NTS_CO_ITEMS consecutive
+ * elements from t * NTS_CO_ITEMS on, so that (thread, element) order is
+ * index order.  Leaves the tile's digits in dig[], in hist[bin * NTS_BLOCK +
+ * t] the count of `bin` among the elements of the threads before t, and in
+ * tot[bin] the tile's count. */
+__device__ void co_tile_ranks(const unsigned long long *__restrict__ key,
+                              uint64_t base, uint64_t n, int nbr_bits,
+                              int shift, uint8_t *dig, uint32_t *hist,
+                              uint32_t *tot) {
+  const uint32_t t = threadIdx.x;
+  for (int j = 0; j < NTS_CO_ITEMS; ++j) {
+    const uint32_t i = j * NTS_BLOCK + t; /* coalesced */
+    const uint64_t g = base + i;
+    dig[i] = (uint8_t)(g < n ? co_digit(key[g], nbr_bits, shift)
+                             : NTS_CO_NONE);
+  }
+  for (int b = 0; b < NTS_CO_BINS; ++b) hist[b * NTS_BLOCK + t] = 0;
+  __syncthreads();
+  for (int k = 0; k < NTS_CO_ITEMS; ++k) {
+    const uint32_t d = dig[t * NTS_CO_ITEMS + k];
+    if (d != NTS_CO_NONE) hist[d * NTS_BLOCK + t] += 1;
+  }
+  __syncthreads();
+  if (t < NTS_CO_BINS) {
+    uint32_t run = 0;
+    for (int j = 0; j < NTS_BLOCK; ++j) {
+      const uint32_t c = hist[t * NTS_BLOCK + j];
+      hist[t * NTS_BLOCK + j] = run;
+      run += c;
+    }
+    tot[t] = run;
+  }
+  __syncthreads();
+}
+
+/* tile_hist[bin * n_tiles + tile] = the tile's count of `bin`: bin-major, so
+ * that one exclusive scan of the array gives every (bin, tile) its base */
+__global__ __launch_bounds__(NTS_BLOCK) void k_coalesce_hist(
+    const unsigned long long *__restrict__ key, uint64_t n, int nbr_bits,
+    int shift, uint32_t n_tiles, uint32_t *__restrict__ tile_hist) {
+  __shared__ uint8_t dig[NTS_CO_TILE];
+  __shared__ uint32_t hist[NTS_CO_BINS * NTS_BLOCK];
+  __shared__ uint32_t tot[NTS_CO_BINS];
+  co_tile_ranks(key, (uint64_t)blockIdx.x * NTS_CO_TILE, n, nbr_bits, shift,
+                dig, hist, tot);
+  if (threadIdx.x < NTS_CO_BINS)
+    tile_hist[(uint64_t)threadIdx.x * n_tiles + blockIdx.x] = tot[threadIdx.x];
+}
+
+/* in-place exclusive scan of a[m] by ONE workgroup (m is tiles * bins) */
+__global__ __launch_bounds__(NTS_BLOCK) void k_coalesce_scan(
+    uint32_t *__restrict__ a, uint64_t m) {
+  __shared__ uint32_t part[NTS_BLOCK];
+  const uint32_t t = threadIdx.x;
+  const uint64_t chunk = (m + NTS_BLOCK - 1) / NTS_BLOCK;
+  const uint64_t lo = min((uint64_t)t * chunk, m), hi = min(lo + chunk, m);
+  uint32_t sum = 0;
+  for (uint64_t i = lo; i < hi; ++i) sum += a[i];
+  part[t] = sum;
+  __syncthreads();
+  if (t == 0) {
+    uint32_t run = 0;
+    for (int j = 0; j < NTS_BLOCK; ++j) {
+      const uint32_t c = part[j];
+      part[j] = run;
+      run += c;
+    }
+  }
+  __syncthreads();
+  uint32_t run = part[t];
+  for (uint64_t i = lo; i < hi; ++i) {
+    const uint32_t c = a[i];
+    a[i] = run;
+    run += c;
+  }
+}
+
+/* the stable scatter of one pass: element -> base of its (bin, tile) + its
+ * rank among the tile's earlier elements of that bin */
+__global__ __launch_bounds__(NTS_BLOCK) void k_coalesce_scatter(
+    const unsigned long long *__restrict__ key_in,
+    const uint32_t *__restrict__ pos_in, uint64_t n, int nbr_bits, int shift,
+    uint32_t n_tiles, const uint32_t *__restrict__ tile_base,
+    unsigned long long *__restrict__ key_out, uint32_t *__restrict__ pos_out) {
+  __shared__ uint8_t dig[NTS_CO_TILE];
+  __shared__ uint32_t hist[NTS_CO_BINS * NTS_BLOCK];
+  __shared__ uint32_t tot[NTS_CO_BINS];
+  __shared__ uint32_t dest[NTS_CO_TILE];
+  const uint32_t t = threadIdx.x;
+  const uint64_t base = (uint64_t)blockIdx.x * NTS_CO_TILE;
+  co_tile_ranks(key_in, base, n, nbr_bits, shift, dig, hist, tot);
+  for (int k = 0; k < NTS_CO_ITEMS; ++k) {
+    const uint32_t i = t * NTS_CO_ITEMS + k;
+    const uint32_t d = dig[i];
+    if (d == NTS_CO_NONE) continue;
+    dest[i] = tile_base[(uint64_t)d * n_tiles + blockIdx.x] +
+              hist[d * NTS_BLOCK + t];
+    hist[d * NTS_BLOCK + t] += 1;
+  }
+  __syncthreads();
+  for (int j = 0; j < NTS_CO_ITEMS; ++j) {
+    const uint32_t i = j * NTS_BLOCK + t;
+    const uint64_t g = base + i;
+    if (g >= n) continue;
+    const uint32_t to = dest[i];
+    if (to >= n) continue; /* cannot happen: the bases partition [0, n) */
+    key_out[to] = key_in[g];
+    pos_out[to] = pos_in[g];
+  }
+}
+
+/* heads of runs of equal keys: tile_heads[tile] = their count in the tile */
+__global__ __launch_bounds__(NTS_BLOCK) void k_coalesce_head_count(
+    const unsigned long long *__restrict__ key, uint64_t n,
+    uint32_t *__restrict__ tile_heads) {
+  __shared__ uint32_t cnt;
+  if (threadIdx.x == 0) cnt = 0;
+  __syncthreads();
+  const uint64_t base = (uint64_t)blockIdx.x * NTS_CO_TILE;
+  uint32_t mine = 0;
+  for (int j = 0; j < NTS_CO_ITEMS; ++j) {
+    const uint64_t g = base + j * NTS_BLOCK + threadIdx.x;
+    if (g < n && (g == 0 || key[g] != key[g - 1])) ++mine;
+  }
+  atomicAdd(&cnt, mine);
+  __syncthreads();
+  if (threadIdx.x == 0) tile_heads[blockIdx.x] = cnt;
+}
+
+/* rank[i] = heads at sorted positions <= i, from the scanned tile counts */
+__global__ __launch_bounds__(NTS_BLOCK) void k_coalesce_rank(
+    const unsigned long long *__restrict__ key, uint64_t n,
+    const uint32_t *__restrict__ tile_base, uint32_t *__restrict__ rank) {
+  __shared__ uint8_t head[NTS_CO_TILE];
+  __shared__ uint32_t part[NTS_BLOCK];
+  __shared__ uint32_t r[NTS_CO_TILE];
+  const uint32_t t = threadIdx.x;
+  const uint64_t base = (uint64_t)blockIdx.x * NTS_CO_TILE;
+  for (int j = 0; j < NTS_CO_ITEMS; ++j) {
+    const uint32_t i = j * NTS_BLOCK + t;
+    const uint64_t g = base + i;
+    head[i] = (g < n && (g == 0 || key[g] != key[g - 1])) ? 1 : 0;
+  }
+  __syncthreads();
+  uint32_t sum = 0;
+  for (int k = 0; k < NTS_CO_ITEMS; ++k) sum += head[t * NTS_CO_ITEMS + k];
+  part[t] = sum;
+  __syncthreads();
+  if (t == 0) {
+    uint32_t run = tile_base[blockIdx.x];
+    for (int j = 0; j < NTS_BLOCK; ++j) {
+      const uint32_t c = part[j];
+      part[j] = run;
+      run += c;
+    }
+  }
+  __syncthreads();
+  uint32_t run = part[t];
+  for (int k = 0; k < NTS_CO_ITEMS; ++k) {
+    run += head[t * NTS_CO_ITEMS + k];
+    r[t * NTS_CO_ITEMS + k] = run;
+  }
+  __syncthreads();
+  for (int j = 0; j < NTS_CO_ITEMS; ++j) {
+    const uint32_t i = j * NTS_BLOCK + t;
+    if (base + i < n) rank[base + i] = r[i];
+  }
+}
+
+/* rank = inclusive scan of head.  The thread of a run's head writes the
+ * run's entry: its neighbour, and its weights added one by one in sorted
+ * order, which is ascending original position (the sort is stable). */
+__global__ void k_coalesce_merge(const unsigned long long *__restrict__ key,
+                                 const uint32_t *__restrict__ pos,
+                                 const uint32_t *__restrict__ rank,
+                                 const float *__restrict__ ew, uint64_t edges,
+                                 uint32_t *__restrict__ nbr_out,
+                                 float *__restrict__ ew_out) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < edges;
+       i += (uint64_t)gridDim.x * blockDim.x) {
+    const unsigned long long k = key[i];
+    if (i != 0 && key[i - 1] == k) continue;
+    float sum = ew[pos[i]];
+    for (uint64_t j = i + 1; j < edges && key[j] == k; ++j) sum += ew[pos[j]];
+    const uint32_t slot = rank[i] - 1; /* rank counts the heads <= i */
+    if (slot >= edges) continue;       /* cannot happen: 1 <= rank <= i + 1 */
+    nbr_out[slot] = (uint32_t)k;
+    ew_out[slot] = sum;
+  }
+}
+
+/* offset_out[v] = runs before list v = rank of the last edge before it (the
+ * sort keeps the lists contiguous and in order) */
+__global__ void k_coalesce_offsets(const uint32_t *__restrict__ offset,
+                                   const uint32_t *__restrict__ rank,
+                                   uint32_t batch, uint64_t edges,
+                                   uint32_t *__restrict__ offset_out) {
+  for (uint64_t v = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       v <= batch; v += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t e = min((uint64_t)offset[v], edges);
+    offset_out[v] = e ? rank[e - 1] : 0u;
+  }
 }
 }  // namespace
 
@@ -6544,6 +6798,83 @@ void nts_permute_f32(nts_stream *s, float *out, const float *in,
   hipLaunchKernelGGL(k_permute_f32, dim3(grid_for((uint64_t)n)),
                      dim3(NTS_BLOCK), 0, s->stream, out, in, index,
                      (uint64_t)n);
+}
+
+long long nts_coalesce_edges(nts_stream *s, const nts_vid *offset,
+                             const nts_vid *nbr, const float *weight,
+                             nts_vid batch_size, nts_vid edges,
+                             nts_vid *offset_out, nts_vid *nbr_out,
+                             float *weight_out) {
+  if (!batch_size || edges < 2) return edges;
+  const uint64_t E = edges;
+  const uint32_t n_tiles = (uint32_t)((E + NTS_CO_TILE - 1) / NTS_CO_TILE);
+  const uint64_t hist_n = (uint64_t)n_tiles * NTS_CO_BINS;
+  unsigned long long *key = nullptr, *key_alt = nullptr;
+  uint32_t *pos = nullptr, *pos_alt = nullptr, *tile_hist = nullptr;
+  NTS_CHECK(hipMalloc(&key, E * sizeof(*key)));
+  NTS_CHECK(hipMalloc(&key_alt, E * sizeof(*key_alt)));
+  NTS_CHECK(hipMalloc(&pos, E * sizeof(*pos)));
+  NTS_CHECK(hipMalloc(&pos_alt, E * sizeof(*pos_alt)));
+  NTS_CHECK(hipMalloc(&tile_hist, (hist_n + 1) * sizeof(*tile_hist)));
+  uint32_t *nbr_max_d = tile_hist + hist_n, nbr_max = 0;
+  NTS_CHECK(hipMemsetAsync(nbr_max_d, 0, sizeof(uint32_t), s->stream));
+  hipLaunchKernelGGL(k_coalesce_keys, dim3(grid_for(E)), dim3(NTS_BLOCK), 0,
+                     s->stream, offset, nbr, batch_size, E, key, pos,
+                     nbr_max_d);
+  NTS_CHECK(hipMemcpyAsync(&nbr_max, nbr_max_d, sizeof(nbr_max),
+                           hipMemcpyDeviceToHost, s->stream));
+  NTS_CHECK(hipStreamSynchronize(s->stream));
+  /* only the bits a key can have set: the neighbour's and the list's */
+  const int nbr_bits = nbr_max ? 32 - __builtin_clz(nbr_max) : 0;
+  const int bits =
+      nbr_bits + (batch_size > 1 ? 32 - __builtin_clz(batch_size - 1) : 0);
+  for (int shift = 0; shift < bits; shift += NTS_CO_BITS) {
+    hipLaunchKernelGGL(k_coalesce_hist, dim3(n_tiles), dim3(NTS_BLOCK), 0,
+                       s->stream, key, E, nbr_bits, shift, n_tiles, tile_hist);
+    hipLaunchKernelGGL(k_coalesce_scan, dim3(1), dim3(NTS_BLOCK), 0, s->stream,
+                       tile_hist, hist_n);
+    hipLaunchKernelGGL(k_coalesce_scatter, dim3(n_tiles), dim3(NTS_BLOCK), 0,
+                       s->stream, key, pos, E, nbr_bits, shift, n_tiles,
+                       tile_hist, key_alt, pos_alt);
+    std::swap(key, key_alt);
+    std::swap(pos, pos_alt);
+  }
+  /* (key, pos) is sorted; the other key buffer is free and holds the ranks */
+  uint32_t *rank = (uint32_t *)key_alt;
+  hipLaunchKernelGGL(k_coalesce_head_count, dim3(n_tiles), dim3(NTS_BLOCK), 0,
+                     s->stream, key, E, tile_hist);
+  hipLaunchKernelGGL(k_coalesce_scan, dim3(1), dim3(NTS_BLOCK), 0, s->stream,
+                     tile_hist, (uint64_t)n_tiles);
+  hipLaunchKernelGGL(k_coalesce_rank, dim3(n_tiles), dim3(NTS_BLOCK), 0,
+                     s->stream, key, E, tile_hist, rank);
+  uint32_t merged = 0;
+  NTS_CHECK(hipMemcpyAsync(&merged, rank + (E - 1), sizeof(merged),
+                           hipMemcpyDeviceToHost, s->stream));
+  NTS_CHECK(hipStreamSynchronize(s->stream));
+  if (merged != edges) {
+    hipLaunchKernelGGL(k_coalesce_merge, dim3(grid_for(E)), dim3(NTS_BLOCK), 0,
+                       s->stream, key, pos, rank, weight, E, nbr_out,
+                       weight_out);
+    hipLaunchKernelGGL(k_coalesce_offsets,
+                       dim3(grid_for((uint64_t)batch_size + 1)),
+                       dim3(NTS_BLOCK), 0, s->stream, offset, rank, batch_size,
+                       E, offset_out);
+    NTS_CHECK(hipStreamSynchronize(s->stream));
+  }
+  NTS_CHECK(hipGetLastError());
+  NTS_CHECK(hipFree(tile_hist));
+  NTS_CHECK(hipFree(pos_alt));
+  NTS_CHECK(hipFree(pos));
+  NTS_CHECK(hipFree(key_alt));
+  NTS_CHECK(hipFree(key));
+  return merged;
+}
+
+int nts_coalesce_plan(nts_vid edges, int request) {
+  if (request) return request > 0;
+  const GatherEnv &env = gather_env();
+  if (env.coalesce) return env.coalesce > 0;
+  return edges >= NTS_COALESCE_MIN_EDGES;
 }
 
 int nts_device_count(void) {

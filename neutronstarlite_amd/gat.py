@@ -104,7 +104,7 @@ class _EdgeLayer:
         self.stable = stable
         self.v = v
         self.np_ch = ch
-        self.ch = DeviceChunk(ch, device)
+        self.ch = DeviceChunk(ch, device, coalesce=False)
         self.stream = shim.Stream.wrap_torch_current()
         if stable:
             self.stream.edge_softmax_stable(1)

@@ -34,9 +34,17 @@ def _u32_cuda(a: np.ndarray, device) -> torch.Tensor:
 class DeviceChunk:
     """A Chunk's CSC+CSR+weights resident in HBM
     (CSC_segment_pinned::CopyGraphToDevice equivalent,
-    /root/reference/core/GraphSegment.cpp:178-220)."""
+    /root/reference/core/GraphSegment.cpp:178-220).
 
-    def __init__(self, ch: Chunk, device):
+    coalesce: merge each direction's parallel edges once, for the weighted
+    gathers of HipEngine (None: shim.coalesce_plan decides, True / False
+    force it).  A direction that has repeats gets the extra attributes
+    csc_coalesced / csr_coalesced = (offset, nbr, weights, edges'); one
+    without keeps None and with it exactly the original launch.  The
+    original arrays stay as they are: the edge-valued paths (GAT, max / min,
+    mirror lists, unweighted gathers) treat parallel edges as separate."""
+
+    def __init__(self, ch: Chunk, device, coalesce=None):
         self.src_s, self.src_e = ch.src_s, ch.src_e
         self.dst_s, self.dst_e = ch.dst_s, ch.dst_e
         self.edge_size = ch.edge_size
@@ -46,6 +54,12 @@ class DeviceChunk:
         self.row_offset = _u32_cuda(ch.row_offset, device)
         self.column_indices = _u32_cuda(ch.column_indices, device)
         self.w_bwd = torch.from_numpy(ch.edge_weight_backward).to(device)
+        self.csc_coalesced = self.csr_coalesced = None
+        if shim.coalesce_plan(self.edge_size, coalesce):
+            self.csc_coalesced = _coalesce(
+                self.column_offset, self.row_indices, self.w_fwd)
+            self.csr_coalesced = _coalesce(
+                self.row_offset, self.column_indices, self.w_bwd)
 
     @property
     def dst_n(self):
@@ -54,6 +68,28 @@ class DeviceChunk:
     @property
     def src_n(self):
         return self.src_e - self.src_s
+
+
+def _coalesce(offset: torch.Tensor, nbr: torch.Tensor, w: torch.Tensor):
+    """(offset', nbr', w', edges') of shim.Stream.coalesce_edges at their
+    exact sizes, or None when the lists hold no repeated neighbour."""
+    assert offset.is_cuda and nbr.is_cuda and w.is_cuda
+    assert w.dtype == torch.float32 and w.numel() == nbr.numel()
+    batch, edges = offset.numel() - 1, nbr.numel()
+    offset_c = torch.empty_like(offset)
+    nbr_ub, w_ub = torch.empty_like(nbr), torch.empty_like(w)
+    with torch.cuda.device(offset.device):
+        stream = shim.Stream.wrap_torch_current()
+        try:
+            merged = stream.coalesce_edges(
+                offset.data_ptr(), nbr.data_ptr(), w.data_ptr(), batch, edges,
+                offset_c.data_ptr(), nbr_ub.data_ptr(), w_ub.data_ptr())
+        finally:
+            stream.destroy()
+    if merged == edges:
+        return None
+    # the upper-bound buffers go back to the allocator here
+    return offset_c, nbr_ub[:merged].clone(), w_ub[:merged].clone(), merged
 
 
 def gather_entry(stream: "shim.Stream", forward: bool, inp: torch.Tensor,
@@ -76,6 +112,13 @@ def gather_entry(stream: "shim.Stream", forward: bool, inp: torch.Tensor,
         f"gather input must be float32 or bfloat16, got {inp.dtype}")
 
 
+def _gather_lists(coalesced, with_weight, original):
+    """(offset, nbr, weights, edges) a gather walks: the coalesced lists
+    where the chunk has them and the gather is weighted (an unweighted one
+    counts every parallel edge), else the original ones."""
+    return coalesced if with_weight and coalesced is not None else original
+
+
 class HipEngine:
     """The product aggregation engine: HIP kernels via the C-ABI on the
     current torch stream."""
@@ -92,11 +135,14 @@ class HipEngine:
         assert x_block.is_contiguous() and y.is_contiguous()
         assert x_block.shape[0] == ch.src_n and y.shape[0] == ch.dst_n
         assert x_block.shape[1] == f
+        offset, nbr, w, edges = _gather_lists(
+            ch.csc_coalesced, with_weight,
+            (ch.column_offset, ch.row_indices, ch.w_fwd, ch.edge_size))
         gather(
-            x_block.data_ptr(), y.data_ptr(), ch.w_fwd.data_ptr(),
-            ch.row_indices.data_ptr(), ch.column_offset.data_ptr(),
+            x_block.data_ptr(), y.data_ptr(), w.data_ptr(),
+            nbr.data_ptr(), offset.data_ptr(),
             ch.src_s, ch.src_e, ch.dst_s, ch.dst_e,
-            ch.edge_size, ch.dst_n, f, with_weight)
+            edges, ch.dst_n, f, with_weight)
 
     def csr_backward(self, ch: DeviceChunk, grad_block: torch.Tensor,
                      out: torch.Tensor, with_weight=True):
@@ -107,12 +153,14 @@ class HipEngine:
         assert grad_block.is_contiguous() and out.is_contiguous()
         assert grad_block.shape[0] == ch.dst_n and out.shape[0] == ch.src_n
         assert grad_block.shape[1] == f
+        offset, nbr, w, edges = _gather_lists(
+            ch.csr_coalesced, with_weight,
+            (ch.row_offset, ch.column_indices, ch.w_bwd, ch.edge_size))
         gather(
-            grad_block.data_ptr(), out.data_ptr(), ch.w_bwd.data_ptr(),
-            ch.row_offset.data_ptr(), ch.column_indices.data_ptr(),
+            grad_block.data_ptr(), out.data_ptr(), w.data_ptr(),
+            offset.data_ptr(), nbr.data_ptr(),
             ch.src_s, ch.src_e, ch.dst_s, ch.dst_e,
-            ch.edge_size, ch.src_n, f, with_weight)
-
+            edges, ch.src_n, f, with_weight)
 
     def csc_reduce(self, ch: DeviceChunk, x: torch.Tensor, y: torch.Tensor,
                    arg: torch.Tensor, op="max", message=False):

@@ -214,6 +214,10 @@ def lib():
     l.nts_reduce_backward.argtypes = [_vp] + [_vp] * 3 + [_u32, _vp] + [_u32] * 2
     l.nts_reduce_plan.argtypes = [_u32] * 4 + [_vp] * 4
     l.nts_items_reuse.argtypes = [_vp, _i32]
+    l.nts_coalesce_edges.argtypes = [_vp] + [_vp] * 3 + [_u32] * 2 + [_vp] * 3
+    l.nts_coalesce_edges.restype = _c.c_longlong
+    l.nts_coalesce_plan.argtypes = [_u32, _i32]
+    l.nts_coalesce_plan.restype = _i32
     l.nts_weight_sum.argtypes = [_vp, _vp, _vp, _vp, _u32]
     l.nts_permute_f32.argtypes = [_vp, _vp, _vp, _vp, _i64]
     l.nts_sample_reservoir.argtypes = [_vp, _vp, _vp, _vp, _u32, _u32,
@@ -483,6 +487,21 @@ def reduce_plan(f, alignment, batch, edges, op="max"):
     return plan
 
 
+# NTS_COALESCE_MIN_EDGES in include/nts_hip.h
+COALESCE_MIN_EDGES = 1 << 24
+
+
+def coalesce_plan(edges, coalesce=None):
+    """Whether a chunk of `edges` edges is handed to Stream.coalesce_edges (no
+    device access).  coalesce: True always, False never, None automatic: the
+    environment's NTS_GATHER_COALESCE (1 / -1) if set, else edges >=
+    COALESCE_MIN_EDGES."""
+    if coalesce is not None and not isinstance(coalesce, bool):
+        raise ValueError(f"coalesce={coalesce!r} must be None, True or False")
+    request = 0 if coalesce is None else 1 if coalesce else -1
+    return bool(lib().nts_coalesce_plan(edges, request))
+
+
 _live_streams = weakref.WeakSet()
 
 
@@ -729,6 +748,17 @@ class Stream:
     def items_reuse(self, enable):
         """Opt-in work-item caching; caller must pin its topology buffers."""
         self._lib.nts_items_reuse(self.h, 1 if enable else 0)
+
+    def coalesce_edges(self, offset, nbr, weights, batch, edges, offset_out,
+                       nbr_out, weights_out):
+        """Merge the parallel edges of (offset, nbr, weights) into the out
+        arrays (sized batch + 1 and edges by the caller): one entry per
+        distinct (list, neighbour) pair, neighbours ascending inside a list,
+        weights summed in original edge order.  Returns the merged edge
+        count; when it equals `edges` nothing was written.  Synchronizes."""
+        return self._lib.nts_coalesce_edges(
+            self.h, _vp(offset), _vp(nbr), _vp(weights), batch, edges,
+            _vp(offset_out), _vp(nbr_out), _vp(weights_out))
 
     def weight_sum(self, out, weights, offset, batch):
         self._lib.nts_weight_sum(self.h, _vp(out), _vp(weights), _vp(offset),
